@@ -10,9 +10,15 @@ synthetic seeded weights, on-device Philox noise).  With --gpus N > 1 the driver
 collects the results at the end of every step.
 
 Prints one JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel = the fused
-per-molecule sampler kernel, bound = fp32 matrix cores, fraction = ISSUED matrix FLOPs / time / peak),
-`secondary` (short C2, C4 and C3-at-1024 passes, N=1 only) and `cpu_baseline` (the C++/OpenMP restatement
-oracle/gaudi_cpu.cpp timed on this host's cores, N=1 only).
+per-molecule sampler kernel, bound = fp32 matrix cores, fraction = ISSUED matrix FLOPs / time / peak, from the
+timed calls themselves).  A plain run does only that: set up, warm up, time --steps calls, print the line.
+With --full it also runs the untimed `parity_gate` (one full-batch step against the C++ port, non-zero exit
+on a failure), `secondary` (short C2, C4, C3-at-1024, fp32-instruction and closure passes, N=1 only) and
+`cpu_baseline` (the C++/OpenMP restatement oracle/gaudi_cpu.cpp timed on this host's cores, N=1 only).
+
+--dump-outputs DIR writes what the last timed call returned (x and h of every molecule; the stability
+workload: its flags) as DIR/<name>.npy in float32; the inputs are fixed by the arguments, so two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ import numpy as np  # noqa: E402
 PEAK_FP32_MATRIX_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_* = vector fp32 peak
 PEAK_HBM_GBPS = 8000.0
 NOMINAL_CLOCK_MHZ = 2400.0  # the clock the guide's peak figures are quoted at
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
 
 
 def parse():
@@ -46,15 +53,36 @@ def parse():
     ap.add_argument("--nodes", type=int, default=11, help="c2 / c3: rings of the cata molecules (BASELINE: 11; fully connected graphs)")
     ap.add_argument("--diffusion-steps", type=int, default=1000)
     ap.add_argument("--steps-per-launch", type=int, default=25)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-gate", action="store_true", help="skip the untimed full-batch step against the CPU restatement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, the secondary passes and the CPU baseline (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed call returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity-gate", action="store_true", help="--full: skip the untimed full-batch step against the CPU restatement")
     ap.add_argument("--closure", default=None, choices=["linear", "nonlinear"],
                     help="c3 only, diagnostic: run the timed calls through sampling_edm.sample_guidance with a reference-form closure")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short C2 / C4 / C3-at-1024 passes after the headline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short C2 / C4 / C3-at-1024 passes after the headline")
     ap.add_argument("--dist", action="store_true",
                     help="N = 1 only: route the run through the SAME distributed code as N > 1 (init_process_group('nccl', "
                          "world_size=1), the RCCL all_gather of every call, barrier + MAX all_reduce around the timed region)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  Over DUMP_LIMIT_BYTES in all, the same seeded sample of
+    leading-axis rows (molecules) is kept of every array."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(arrays.values())).shape[0]
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, n * DUMP_LIMIT_BYTES // total), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def cpu_quota():
@@ -203,12 +231,15 @@ def bench_stability(a, emit):
     want = g[f"{ds}_flags"].astype(bool)[idx]
     for _ in range(max(a.warmup, 1)):
         flags = analyze.check_stability_batch(X, T, nn, 0.1, ds, engine=eng)
-    assert np.array_equal(flags, want), "stability flags differ from the reference's (g11 fixture)"
+    if a.full:
+        assert np.array_equal(flags, want), "stability flags differ from the reference's (g11 fixture)"
     eng.profile_reset(True)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        analyze.check_stability_batch(X, T, nn, 0.1, ds, engine=eng)
+        flags = analyze.check_stability_batch(X, T, nn, 0.1, ds, engine=eng)
     wall = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"flags": flags})
     n_launch, kernel_ms = eng.stability_profile_get()
     kernel_s = kernel_ms / 1e3 / max(n_launch, 1)
     bytes_per_mol = X.shape[1] * 3 * 4 + X.shape[1] * 4 + 4 + 5
@@ -220,7 +251,7 @@ def bench_stability(a, emit):
                              frac=M * bytes_per_mol / kernel_s / 1e9 / PEAK_HBM_GBPS, traffic=None,
                              kernel="stability_kernel", avg_launch_ms=kernel_s * 1e3, launches=n_launch,
                              algorithmic_bytes_per_molecule=bytes_per_mol, kernel_molecules_per_s=M / kernel_s))
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         from oracle import stability_oracle as S  # baseline leg only
         m, t0 = 0, time.perf_counter()
         while m < M and (m < 64 or time.perf_counter() - t0 < 10.0):
@@ -283,9 +314,10 @@ def graph_meta8(nm, em):
 
 
 def run_workload(a, eng_cache, workload, B, steps, warmup, rank, world, dev, backend, T, K=5, edge_math=None, use_dist=False,
-                 gate=False, closure=None):
+                 gate=False, closure=None, outputs=None):
     """Time `steps` complete sampling calls of one workload; returns the contract fields + roofline of its kernel.
-    edge_math="fp32": a handle created with GAUDI_EDGE_MATH=fp32 (edge GEMMs on fp32 matrix instructions)."""
+    edge_math="fp32": a handle created with GAUDI_EDGE_MATH=fp32 (edge GEMMs on fp32 matrix instructions).
+    outputs: a dict that receives x and h of the last timed call."""
     import torch
     import torch.distributed as dist
     from gaudi_amd import dist as gdist
@@ -415,6 +447,8 @@ def run_workload(a, eng_cache, workload, B, steps, warmup, rank, world, dev, bac
     clock_mhz = eng.profile_clock_mhz()  # shader clock the chip held during the last profiled launch (0: not available)
     eng.profile_reset(False)
     assert x.shape[0] == B * world and np.isfinite(x).all()
+    if outputs is not None:
+        outputs.update(x=x, h=h)
     if rank != 0:
         return None
     value = steps * B * world / dt
@@ -626,8 +660,10 @@ def main():
     # (C5): 1024 guided samples per GPU, 8192 over 8 GPUs.
     B = a.batch or (1024 if (a.workload in ("c4", "c4x") or world > 1) else 256)
     engines = {}
+    outputs = {}
     out = run_workload(a, engines, a.workload, B, a.steps, a.warmup, rank, world, dev, backend, T, use_dist=use_dist,
-                       gate=not a.no_parity_gate, closure=a.closure if a.workload == "c3" and world == 1 else None)
+                       gate=a.full and not a.no_parity_gate, closure=a.closure if a.workload == "c3" and world == 1 else None,
+                       outputs=outputs)
     gate_failed = rank == 0 and "parity_gate" in out and not out["parity_gate"]["passed"]
     if use_dist:  # every rank leaves with the same exit code (the gate runs on rank 0: one CPU step, not one per GPU)
         flag = [gate_failed]
@@ -639,10 +675,12 @@ def main():
             emit({"error": "parity gate failed", "parity_gate": out["parity_gate"]})
         os._exit(3)
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, outputs)
         if use_dist:
             out["config"]["collective"] = (f"{backend} all_gather per call (world {world}"
                                            + (f", RCCL {'.'.join(map(str, torch.cuda.nccl.version()))}" if backend == "nccl" else "") + ")")
-        if world == 1 and not a.no_secondary and a.workload == "c3":
+        if world == 1 and a.full and not a.no_secondary and a.workload == "c3":
             # the other single-GPU configurations, timed by the same harness (short: one or two calls each)
             sec = {}
             # (every line is gated like the headline: one teacher-forced full-batch step of the engine that is about to be timed
@@ -677,7 +715,7 @@ def main():
                 except Exception as exc:  # a secondary line must not cost the headline
                     sec[wl] = {"error": repr(exc)}
             out["secondary"] = sec
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             guided = a.workload in ("c3", "c4", "c4x")
             ref8 = 0.058 if guided else 0.175  # the reference's own PyTorch-CPU path on the 8-core build container
             try:  # the baseline leg must never cost the measured line (no g++ / no AVX2 / a stale build on this host)

@@ -9,6 +9,11 @@ if ROOT not in sys.path:
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# torch ships its own HIP runtime under the same soname as ROCm's.  Whichever is loaded first serves libgaudi_hip.so too;
+# if the library is loaded before torch, the process ends up with two HIP runtimes and gaudi_create finds no device.
+# Every GPU test and bench.py import torch first, so the whole suite must too, whatever order its modules run in.
+import torch  # noqa: E402,F401
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run on the GPU box with -m gpu)")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # C4 (hetero 3-10 rings, B = 1024) with the default packing against forced wide groups (GAUDI_PAIRS=2), half ring and full ring
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --workload c4 --diffusion-steps 250"
+B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --workload c4 --diffusion-steps 250"
 for rep in 1 2; do
   for cfg in "default:" "wide_full:GAUDI_PAIRS=2" "wide_half:GAUDI_PAIRS=2 GAUDI_WIDE_FULL=0"; do
     name=${cfg%%:*}; envs=${cfg#*:}

@@ -4,7 +4,7 @@ tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd - >/dev/null
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary"
 for step in "$@"; do
   case $step in
     mb_node) timeout 300 gaudi_amd/ngemm_mb > $out/ngemm_mb.txt 2>&1 ;;
@@ -18,9 +18,9 @@ for step in "$@"; do
     tests_r3) timeout 2400 python3 -m pytest tests/test_gpu_round3.py -x -q -m gpu -s > $out/tests_r3.txt 2>&1
               timeout 600 python3 -m pytest tests/test_gpu_round2.py -x -q -m gpu -k "nan or fresh" >> $out/tests_r3.txt 2>&1 ;;
     repro_gn) for w in tiny default; do for e in "GAUDI_WAVES=4" "GAUDI_FORCE_GN=1"; do echo "== $w $e" >> $out/repro_gn.txt; env $e timeout 300 python3 tools/repro_gn.py $w >> $out/repro_gn.txt 2>&1; done; done ;;
-    stamps) GAUDI_LIB=$PWD/gaudi_amd/libgaudi_hip_stamps.so GAUDI_PRINT_STAMPS=1 timeout 900 python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --diffusion-steps 100 > $out/stamps.json 2> $out/stamps.txt ;;
+    stamps) GAUDI_LIB=$PWD/gaudi_amd/libgaudi_hip_stamps.so GAUDI_PRINT_STAMPS=1 timeout 900 python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --diffusion-steps 100 > $out/stamps.json 2> $out/stamps.txt ;;
     spl) for k in 25 100 250; do timeout 600 $B --steps-per-launch $k > $out/bench_spl$k.json 2> $out/bench_spl$k.err; done ;;
-    bench) timeout 900 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/bench.json 2> $out/bench.err ;;
+    bench) timeout 900 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/bench.json 2> $out/bench.err ;;
     bench_dist) timeout 600 $B --dist > $out/bench_dist.json 2> $out/bench_dist.err ;;
     *) echo "unknown step $step" ;;
   esac

@@ -4,7 +4,7 @@ tag=$1; shift
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp 2>/dev/null; export TMPDIR=/tmp; cd - >/dev/null
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary"
 ab() {  # ab <name> <bench args...>: variant libraries named in GAUDI_VARIANTS, then the tree's own library, twice each (A B A B)
   name=$1; shift
   for rep in 1 2; do
@@ -48,7 +48,7 @@ for step in "$@"; do
     tests_core) timeout 2400 python3 -m pytest tests/test_gpu_parity.py tests/test_gpu_round2.py tests/test_gpu_split.py tests/test_gpu_round5.py -x -q -m gpu > $out/tests_core.txt 2>&1 ;;
     tests_v8g) timeout 2400 python3 -m pytest tests/test_gpu_round4.py tests/test_gpu_round3.py -x -q -m gpu -k "v8g or large or n40 or dense or callback_targets" > $out/tests_v8g.txt 2>&1 ;;
     tests_all) timeout 3400 python3 -m pytest tests -x -q -m gpu > $out/tests_all.txt 2>&1 ;;
-    bench) timeout 1200 python3 bench.py > $out/bench.json 2> $out/bench.err ;;
+    bench) timeout 1200 python3 bench.py --full > $out/bench.json 2> $out/bench.err ;;
     *) echo "unknown step $step" ;;
   esac
 done

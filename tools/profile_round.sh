@@ -13,7 +13,7 @@ $R -d $out/c3 -- $B > $out/c3_bench.json 2> $out/c3.log
 $R -d $out/c2 -- $B --workload c2 > $out/c2_bench.json 2> $out/c2.log
 $R -d $out/c4 -- $B --workload c4 > $out/c4_bench.json 2> $out/c4.log
 GAUDI_EDGE_MATH=fp32 $R -d $out/c3fp32 -- $B > $out/c3fp32_bench.json 2> $out/c3fp32.log  # the fp32-instruction kernel beside it
-$R -d $out/stab -- python3 bench.py --workload stability --steps 20 --warmup 1 --no-cpu-baseline > $out/stab_bench.json 2> $out/stab.log
+$R -d $out/stab -- python3 bench.py --full --workload stability --steps 20 --warmup 1 --no-cpu-baseline > $out/stab_bench.json 2> $out/stab.log
 for wl in c3 c2 c4; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_${wl}_$c -- $B --diffusion-steps 100 --workload $wl \
