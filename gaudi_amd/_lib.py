@@ -110,10 +110,14 @@ EXPORTS = {
     "gaudi_last_keep_h": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "gaudi_host_pack_plan": (C.c_int, [C.c_int, C.c_int, FP, FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]),
+    "gaudi_edm_nll": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, IP, FP, FP, C.c_uint64, C.c_int64, FP, FP, FP]),
+    "gaudi_host_nll_terms": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, FP, FP, FP,
+                                       IP, FP]),
 }
 
 ABI_VERSION = 7  # include/gaudi_hip.h: GAUDI_ABI_VERSION
 _ROUND6_EXPORTS = ("gaudi_last_warning", "gaudi_abi_version", "gaudi_last_family_split", "gaudi_profile_clock", "gaudi_last_keep_h")  # an older A/B library (GAUDI_LIB) lacks them
+_NLL_EXPORTS = ("gaudi_edm_nll",)  # ... and the NLL entry point (same ABI version: no existing signature changed)
 
 _lib = None
 
@@ -141,7 +145,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory

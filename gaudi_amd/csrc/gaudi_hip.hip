@@ -2622,3 +2622,4 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 
 #include "pred_host.inc"
 #include "stability.inc"
+#include "nll_host.inc"

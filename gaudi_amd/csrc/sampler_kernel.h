@@ -13,7 +13,7 @@
 
 namespace gaudi {
 
-enum Mode { MODE_PHI = 0, MODE_SAMPLE = 1, MODE_PRED_FWD = 2, MODE_PRED_GRAD = 3, MODE_GUIDE = 4 };
+enum Mode { MODE_PHI = 0, MODE_SAMPLE = 1, MODE_PRED_FWD = 2, MODE_PRED_GRAD = 3, MODE_GUIDE = 4, MODE_NLL = 5 };
 
 struct KParams {
   int mode, B, N, F, EW;   // B workgroups (molecules, or groups of them), N node slots per workgroup
@@ -500,6 +500,89 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
   };
 
   if constexpr (HPE > 0) {
+    if constexpr (HPP == 0) {
+      if (mode == MODE_NLL) {
+        // Eval-mode negative log-likelihood (en_diffusion.py:646-805, t0_always): two EDM passes per molecule -- z_t from raw
+        // draw 0 at t = t_in[b], z_0 from raw draw 1 at t = 0 -- and three per-molecule sums -> pred_out[molecule][4]:
+        // [0] sum (eps - phi(z_t, t))^2 over every entry (compute_error, :507-515), [1] the same over the x columns of pass 2
+        // (:597-599), [2] log p(h | z_0) of the true classes (:620-636; include_charges = False: no integer part).  The
+        // network-free terms are the host's (nll_host.inc).  z_in holds the un-normalised [x | onehot], alpha_sigma [b][2]
+        // alpha_t / sigma_t of each molecule (draw_base = 0: the forward-noising prologue has already built z_t and left eps in
+        // sNz).  Scratch: per-slot partial sums go to sEps once a pass has consumed it.
+        // The host never packs these launches (t differs between molecules; one EDM pass takes one t per workgroup), but
+        // every sum runs per component, over the component's slots in slot order (= its node order): no atomics.
+        const EdmDev edm = P.edm;
+        const float nv0 = P.nv0, nv1 = P.nv1, sig_cat = P.sigma0 * P.nv1;
+        const int F = P.F;
+        float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;  // thread k < ncomp: the sums of component k
+        for (int pass = 0; pass < 2; ++pass) {
+          if (pass == 1) {  // (pass 0: the forward-noising prologue above built z_t from draw 0 = draw_base)
+            __syncthreads();
+            combined_noise(1, 1.0f);  // sNz <- eps_0
+            const float a0 = P.alpha0, s0 = P.sigma0;
+            for (int e = tid; e < N * D; e += kThreads) {
+              const int n = e / D, d = e % D;
+              const long long gi = gidx(n, d, D);
+              const float raw = gi < 0 ? 0.f : P.z_in[gi];
+              const float xh = d < 3 ? raw / nv0 : (raw - 0.0f) / nv1 * sMask[n];  // normalize (:384-392)
+              sZ[e] = gi < 0 ? 0.f : a0 * xh + s0 * sNz[e];
+            }
+            __syncthreads();
+          }
+          V::template edm<HPE>(edm, mg, net, sZ, sEps, sMean, pass == 0 ? P.t_in[b] : 0.f, tid STAMP_ARGS,
+                               V::kGlobalNodes ? P.gnode + (size_t)blockIdx.x * P.gnode_stride : nullptr);
+          __syncthreads();
+          float v0 = 0.f, v1 = 0.f;  // this thread's slot (N <= threads per workgroup)
+          const int n = tid;
+          if (n < N && sRow[n] >= 0) {
+            const float* ep = sNz + n * D;
+            const float* ph = sEps + n * D;
+            const int dn = pass == 0 ? D : 3;
+            for (int d = 0; d < dn; ++d) {
+              const float df = ep[d] - ph[d];
+              v0 += df * df;
+            }
+            if (pass == 1) {
+              // categorical log-likelihood: Phi-integrals of N(z_0,h * nv1, sigma_0 * nv1) over [c - 0.5, c + 0.5] around
+              // each class, normalised over the classes (logsumexp), read at the true class (:612-636)
+              const float* zh = sZ + n * D + 3;
+              auto lp = [=](int k) {
+                const float c = (zh[k] * nv1 + 0.0f) - 1.0f;
+                const float hi = 0.5f * (1.0f + erff(((c + 0.5f) / sig_cat) / 1.41421356237309515f));
+                const float lo = 0.5f * (1.0f + erff(((c - 0.5f) / sig_cat) / 1.41421356237309515f));
+                return logf(hi - lo + 1e-10f);
+              };
+              float m = -INFINITY;
+              for (int k = 0; k < F; ++k) m = fmaxf(m, lp(k));
+              float se = 0.f;
+              for (int k = 0; k < F; ++k) se += expf(lp(k) - m);
+              const float logz = logf(se) + m;
+              const float mk = sMask[n];
+              for (int k = 0; k < F; ++k) {
+                const long long gi = gidx(n, 3 + k, D);
+                const float oh = ((P.z_in[gi] - 0.0f) / nv1 * mk) * nv1 + 0.0f;  // h["categorical"] un-normalised back (:607)
+                v1 += (lp(k) - logz) * oh * mk;
+              }
+            }
+          }
+          __syncthreads();  // every read of sEps done
+          if (n < N) { sEps[n] = v0; sEps[N + n] = v1; }
+          __syncthreads();
+          if (tid < ncomp) {
+            for (int i = 0; i < N; ++i)
+              if (comp_of(sRow[i]) == tid) {
+                if (pass == 0) acc0 += sEps[i];
+                else { acc1 += sEps[i]; acc2 += sEps[N + i]; }
+              }
+          }
+        }
+        if (tid < ncomp) {
+          float* o = P.pred_out + (size_t)sCmol[tid] * 4;
+          o[0] = acc0; o[1] = acc1; o[2] = acc2; o[3] = 0.f;
+        }
+        return;
+      }
+    }
     if (mode == MODE_PHI || mode == MODE_SAMPLE) {
       const EdmDev edm = P.edm;
       const int guided = P.guided, T = P.T, s_hi = P.s_hi;

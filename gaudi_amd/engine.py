@@ -288,6 +288,27 @@ class Engine:
                                                   fptr(pred)), "gaudi_predict_noised")
         return zt, pred
 
+    def edm_nll(self, x, onehot, t_int, node_mask, edge_mask, *, seed, sample_offset, noise=None, return_terms=False):
+        """The EDM's negative log-likelihood of (x, onehot) in one launch (include/gaudi_hip.h: gaudi_edm_nll) -> nll [B], or
+        (nll [B], terms [B,6]) with return_terms: kl_prior, loss_t, neg_log_constants, loss_term_0, delta_log_px, error.
+        x [B,N,3] un-normalised, masked, mean-free; onehot [B,N,F]; t_int [B] in 1..T; noise [2,B,N,3+F] raw draws or None
+        (Philox draws 0 / 1 of (seed, sample_offset + b))."""
+        x = f32(x)
+        B, N = x.shape[0], x.shape[1]
+        oh = f32(onehot).reshape(B, N, self.F)
+        nm, em = self._masks(f32(node_mask).reshape(B, N), edge_mask, B, N)
+        ti = np.ascontiguousarray(np.broadcast_to(np.asarray(t_int).reshape(-1), (B,)), dtype=np.int32)
+        nz = None
+        if noise is not None:
+            nz = f32(noise)
+            if nz.shape != (2, B, N, 3 + self.F):
+                raise GaudiError(f"noise must be [2,B,N,3+F] = {(2, B, N, 3 + self.F)}, got {nz.shape}")
+        nll = np.empty(B, np.float32)
+        terms = np.empty((B, 6), np.float32)
+        self._check(self.lib.gaudi_edm_nll(self.h, B, N, fptr(x), fptr(oh), ti.ctypes.data_as(_lib.IP), fptr(nm), fptr(em),
+                                           int(seed), int(sample_offset), fptr(nz), fptr(nll), fptr(terms)), "gaudi_edm_nll")
+        return (nll, terms) if return_terms else nll
+
     def sample_callback(self, node_mask, edge_mask, target_grad, *, seed=0, sample_offset=0, noise=None, std=1.0,
                         scale=1.0, return_z0=False, with_z=False):
         """Guided chain for an arbitrary target: ``target_grad(pred [B,K], t) -> dT/dpred [B,K]`` is called once per

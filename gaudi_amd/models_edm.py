@@ -275,7 +275,7 @@ def target_function_opv(cond_predictor, prop_dist: PropertyNorm) -> LinearTarget
 
 class GaudiModel:
     """Stands in for EnVariationalDiffusion on the sampling path: .sample / .sample_guidance / .normalize /
-    .unnormalize / .T with the reference's signatures."""
+    .unnormalize / .T with the reference's signatures, and model(x, h, node_mask, edge_mask) -> the eval-mode NLL."""
 
     def __init__(self, args, state_dict, device: int = 0):
         self.args = checkpoint.args_dict(args)
@@ -386,6 +386,45 @@ class GaudiModel:
 
     def eval(self):
         return self
+
+    def train(self, mode: bool = True):
+        """Training (the t0_always=False estimator and any backward pass through the weights) is not part of this port."""
+        if not mode:
+            return self
+        raise GaudiError("training is out of scope: GaudiModel evaluates the eval-mode NLL only (call model.eval())")
+
+    # ---- en_diffusion.py:777-805 (eval mode)
+    def forward(self, x, h, node_mask=None, edge_mask=None, context=None):
+        """EnVariationalDiffusion.forward in eval mode -> the negative log-likelihood per molecule, a torch tensor [B].
+        t_int ~ U{1..T} is drawn with torch.randint as the reference draws it (torch.manual_seed reproduces its t); the two noise
+        draws come from this model's stream (next_stream), or from injected_noise when that holds [2,B,N,3+F] raw draws."""
+        import torch
+        if context is not None:
+            raise GaudiError("context conditioning is not part of this port")
+        if not isinstance(h, dict) or "categorical" not in h:
+            raise GaudiError('h must be the reference\'s dict {"categorical": [B,N,F], "integer": ...}')
+        hi = h.get("integer")
+        if hi is not None and np.size(_to_numpy(hi)) != 0:
+            raise GaudiError("include_charges is False for GaUDI checkpoints (models_edm.py:94): h['integer'] must be empty")
+        xn = _to_numpy(x).astype(np.float32)
+        B, N = xn.shape[0], xn.shape[1]
+        if node_mask is None or edge_mask is None:
+            raise GaudiError("node_mask and edge_mask are required")
+        nm = _to_numpy(node_mask).astype(np.float32).reshape(B, N)
+        em = _to_numpy(edge_mask).astype(np.float32).reshape(B, N, N)
+        hc = _to_numpy(h["categorical"]).astype(np.float32).reshape(B, N, self.in_node_nf)
+        assert_correctly_masked(hc, nm)
+        assert_mean_zero_with_mask(xn, nm)  # (compute_loss asserts it on z_t, en_diffusion.py:680)
+        t_int = torch.randint(1, self.T + 1, size=(B, 1)).float()  # t0_always: lowest_t = 1 (:651-659)
+        noise = self.injected_noise
+        if noise is None or np.shape(noise)[0] != 2:
+            noise = None
+        seed, off = self.next_stream(B)
+        nll = self.engine.edm_nll(xn, hc, t_int.numpy().reshape(B).astype(np.int32), nm, em, seed=seed, sample_offset=off,
+                                  noise=noise)
+        return _like_ref(nll)
+
+    __call__ = forward
 
     # ---- en_diffusion.py:384-415
     def normalize(self, x, h, node_mask):
@@ -519,6 +558,25 @@ class GaudiModel:
     def sample_guidance(self, n_samples, target_function, node_mask, edge_mask, scale=1, fix_noise=False, std=1.0):
         """EnVariationalDiffusion.sample_guidance (en_diffusion.py:1010-1067)."""
         return self._run(n_samples, node_mask, edge_mask, std, target_function, scale, fix_noise)
+
+
+def assert_correctly_masked(variable, node_mask):
+    """utils.py:63-66 as a GaudiError: no value outside the mask."""
+    v = _to_numpy(variable).astype(np.float32)
+    nm = _to_numpy(node_mask).astype(np.float32).reshape(v.shape[0], v.shape[1], 1)
+    if v.size and float(np.abs(v * (1 - nm)).max()) >= 1e-4:
+        raise GaudiError("Variables not masked properly.")
+
+
+def assert_mean_zero_with_mask(x, node_mask, eps=1e-10):
+    """utils.py:52-60 as a GaudiError: the masked positions have zero centre of gravity."""
+    assert_correctly_masked(x, node_mask)
+    x = _to_numpy(x).astype(np.float32)
+    largest = float(np.abs(x).max()) if x.size else 0.0
+    err = float(np.abs(x.sum(1, keepdims=True)).max()) if x.size else 0.0
+    rel = err / (largest + eps)
+    if not rel < 1e-2:
+        raise GaudiError(f"Mean is not zero, relative_error {rel}")
 
 
 class CondPredictor:

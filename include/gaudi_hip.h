@@ -126,6 +126,17 @@ int gaudi_predict_noised(gaudi_handle* h, int B, int N, const float* x, const fl
                          const float* node_mask, const float* edge_mask, uint64_t seed, int64_t sample_offset,
                          const float* noise, float* zt_out /* [B,N,3+F] or NULL */, float* pred_out /* [B,K] or NULL */);
 
+/* The EDM's negative log-likelihood of data: EnVariationalDiffusion.forward in eval mode (en_diffusion.py:777-805, compute_loss
+ * with t0_always = True).  x [B,N,3] (un-normalised, masked, mean-free), onehot [B,N,F], t_int [B] in 1..T (refused otherwise).
+ * One launch of the EDM-only kernels evaluates the network twice per molecule: at z_t = alpha_t * xh + sigma_t * eps and
+ * t = t_int/T, and at z_0 = alpha_0 * xh + sigma_0 * eps_0 and t = 0.  eps / eps_0 = combined position/feature noise from the
+ * injected raw draws `noise` [2,B,N,3+F], or Philox draws 0 / 1 of (seed, sample_offset + b) when NULL.
+ * nll_out [B] = kl_prior + loss_t + neg_log_constants + loss_term_0 - delta_log_px; terms_out [B][6] = those five terms in
+ * that order, then error = sum (eps - phi(z_t, t))^2.  Either output may be NULL. */
+int gaudi_edm_nll(gaudi_handle* h, int B, int N, const float* x, const float* onehot, const int32_t* t_int, const float* node_mask,
+                  const float* edge_mask, uint64_t seed, int64_t sample_offset, const float* noise /* [2,B,N,3+F] or NULL */,
+                  float* nll_out /* [B] or NULL */, float* terms_out /* [B][6] or NULL */);
+
 /* One teacher-forced reverse step z_t -> z_s with s = s_idx/T, t = (s_idx+1)/T:
  * sample_p_zs_given_zt (en_diffusion.py:807-852) when target_w == NULL, else
  * sample_p_zs_given_zt_guidance (:854-935) for the target  T(pred) = target_w . pred  scaled by `scale`.
@@ -224,6 +235,11 @@ int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, i
 /* ---- Device-free host logic (no handle, no GPU): exposed so the CPU test suite can check it. ----
  * gamma [T+1] and (optionally) the per-step table [T][4] exactly as gaudi_load_edm builds them. */
 int gaudi_host_schedule(int T, float noise_power /* 0 = cosine */, float noise_precision, float* gamma_out, float* coef_out);
+/* The network-free terms of gaudi_edm_nll, computed by the same function: terms_out [B][4] = kl_prior, neg_log_constants,
+ * delta_log_px and the SNR weight SNR(gamma_s - gamma_t) - 1 of t_int[b] (1..T) for the schedule of gaudi_host_schedule and
+ * normalize_factors (norm_x, norm_h). */
+int gaudi_host_nll_terms(int T, float noise_power, float noise_precision, float norm_x, float norm_h, int B, int N, int F,
+                         const float* x, const float* onehot, const float* node_mask, const int32_t* t_int, float* terms_out);
 /* The live-edge metadata gaudi_* calls derive from (node_mask, edge_mask): per-wave capacity EW (multiple of 32),
  * launch order [B] (heaviest first), 32-edge passes per wave [B][4], per-node segment word [B][N]
  * (wave<<30 | start<<15 | len), the padded per-wave edge lists [B][4][EW] (i | j<<8) with their mask values, and

@@ -1194,6 +1194,103 @@ def g21_direct_z_target():
     save("g21_direct_z_target", **out)
 
 
+def g25_nll():
+    """The EDM's eval-mode negative log-likelihood (EnVariationalDiffusion.forward, en_diffusion.py:646-805 with t0_always): the
+    reference's model(x, h, node_mask, edge_mask) in eval() driven by a fixed t_int (torch.randint patched) and InjectNoise([eps,
+    eps_0]); the six terms recomputed with the reference's own methods from the values its two phi passes saw, and phi at both
+    passes.  Cases: tiny cata / hetero (mixed sizes, t_int including 1 and T), the default widths on the C3 weights, a
+    g18-like N = 40 hetero batch (V8G), a schedule whose categorical term is NOT saturated, and sin_embedding."""
+    out = {}
+    cases = [  # name, dataset, nodes, max_nodes, over, weight seed, amplify
+        ("cata_tiny", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50), 2500, True),
+        ("hetro_tiny", "hetro", [3, 9, 6, 10], None, dict(TINY, diffusion_steps=50), 2501, True),
+        ("cata_default", "cata", [11, 9, 11, 7, 11, 4], 11, {}, 0, False),
+        ("hetro_large", "hetro", [20, 14], None, {}, 2503, False),
+        ("hetro_soft", "hetro", [5, 8, 10], None, dict(TINY, diffusion_steps=50, diffusion_noise_precision=9e-4,
+                                                          normalize_factors=[3, 4, 1]), 2504, False),
+        ("cata_se_tiny", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50, sin_embedding=True), 2505, False),
+    ]
+    for ci, (name, ds, nodes, mx, over, wseed, amp) in enumerate(cases):
+        F = synth.num_node_features(ds)
+        esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=wseed, amplify_coord=amp)
+        a, model = build_ref_edm(ds, esd, **over)
+        model.eval()
+        nm, em, z = case_inputs(ds, nodes, mx, seed=2520 + ci, guidance_pad=mx is None)
+        B, N, D = z.shape
+        if name == "hetro_large":
+            assert N == 40
+        T = a.diffusion_steps
+        rng = np.random.default_rng(2530 + ci)
+        x = (z[:, :, :3] * 3.0).astype(np.float32)                      # un-normalised, masked, mean-free positions
+        h = (np.eye(F, dtype=np.float32)[rng.integers(0, F, (B, N))] * nm).astype(np.float32)
+        t_int = rng.integers(1, T + 1, B)
+        t_int[0], t_int[-1] = 1, T
+        eps, eps0 = rng_noise(2540 + ci, (B, N, D)), rng_noise(2550 + ci, (B, N, D))
+        tx, th, tnm, tem = (torch.from_numpy(v) for v in (x, h, nm, em))
+        hd = {"categorical": th, "integer": torch.zeros(0)}
+        rec = {"phi": [], "noise": []}
+        phi0, noise0, randint0 = model.phi, model.sample_combined_position_feature_noise, torch.randint
+
+        def phi_rec(zz, tt, *rest):
+            o = phi0(zz, tt, *rest)
+            rec["phi"].append((zz.clone(), tt.clone(), o.clone()))
+            return o
+
+        def noise_rec(*args, **kw):
+            o = noise0(*args, **kw)
+            rec["noise"].append(o.clone())
+            return o
+
+        def randint_fixed(low, high, size, device=None, **kw):
+            assert (low, high, tuple(size)) == (1, T + 1, (B, 1)), (low, high, size)
+            return torch.from_numpy(t_int.reshape(B, 1)).long()
+
+        model.phi, model.sample_combined_position_feature_noise = phi_rec, noise_rec
+        torch.randint = randint_fixed
+        try:
+            with InjectNoise([eps, eps0]), torch.no_grad():
+                nll = model(tx, hd, tnm, tem.view(B, N * N))
+        finally:
+            torch.randint = randint0
+            del model.phi, model.sample_combined_position_feature_noise
+        assert len(rec["phi"]) == 2 and len(rec["noise"]) == 2
+        (zt, tt, net_t), (z0, t0, net_0) = rec["phi"]
+        e_t, e_0 = rec["noise"]
+        with torch.no_grad():  # the six terms, by the reference's own methods on what its passes saw
+            xn, hn, dlp = model.normalize(tx, hd, tnm)
+            xh = torch.cat([xn, hn["categorical"], hn["integer"]], dim=2)
+            ti = torch.from_numpy(t_int.reshape(B, 1)).float()
+            g_t = model.inflate_batch_array(model.gamma(ti / T), xn)
+            g_s = model.inflate_batch_array(model.gamma((ti - 1) / T), xn)
+            g_0 = model.inflate_batch_array(model.gamma(torch.zeros(B, 1)), xn)
+            error = model.compute_error(net_t, g_t, e_t)
+            snr = (model.SNR(g_s - g_t) - 1).squeeze(1).squeeze(1)
+            loss_t = T * (0.5 * snr * error)
+            nlc = -model.log_constants_p_x_given_z0(xn, tnm)
+            kl = model.kl_prior(xh, tnm)
+            lpxh = model.log_pxh_given_z0_without_constants(xn, hn, z0, g_0, e_0, net_0, tnm)
+            lpx = -0.5 * model.compute_error(net_0[:, :, :3], g_0, e_0[:, :, :3])
+            total = kl + loss_t + nlc - lpxh - dlp
+        assert torch.allclose(total, nll, rtol=1e-5, atol=1e-5), (total, nll)
+        log_ph = (lpxh - lpx).numpy()
+        if name == "hetro_soft":
+            assert np.abs(log_ph).max() > 1e-3, log_ph
+        else:
+            out[name + "_log_ph_max"] = np.float32(np.abs(log_ph).max())
+        out[name + "_cfg"] = np.array(json.dumps(dict(dataset=ds, over=over, wseed=wseed, amp=amp, nodes=nodes, T=T)))
+        out[name + "_x"], out[name + "_h"], out[name + "_node_mask"], out[name + "_edge_mask"] = x, h, nm, em
+        out[name + "_t_int"] = t_int.astype(np.int32)
+        out[name + "_noise"] = np.stack([eps, eps0])
+        out[name + "_nll"] = nll.numpy()
+        out[name + "_terms"] = torch.stack([kl, loss_t, nlc, -lpxh, dlp, error], dim=1).numpy()
+        out[name + "_snr_weight"] = snr.numpy()
+        out[name + "_log_ph"] = log_ph
+        out[name + "_zt"], out[name + "_z0"] = zt.numpy(), z0.numpy()
+        out[name + "_phi_t"], out[name + "_phi_0"] = net_t.numpy(), net_0.numpy()
+        print(f"g25 {name}: nll {nll.numpy()} max|log p(h|z0)| {np.abs(log_ph).max():.3g}")
+    save("g25_nll", **out)
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1218,8 +1315,8 @@ def g8_checkpoint_roundtrip():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g22"]
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll)
+    which = sys.argv[1:] or list(fns)
     for w in which:
         fns[w]()
