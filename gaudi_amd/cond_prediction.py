@@ -1,9 +1,11 @@
 """Host mirror of the predictor-evaluation path: sample_edm_t / compute_loss (cond_prediction/train_cond_predictor.py:47-81)
 and val_epoch / the t-sweep of eval_cond_predictor.py:34-113, on top of gaudi_predict_noised (forward noising fused into the
-predictor-forward launch).  Evaluation only: there is no backward pass through the weights here (training is out of scope)."""
+predictor-forward launch).  Training (train_epoch, :84-125): with the predictor in train mode, compute_loss returns a loss whose
+backward() fills every parameter's .grad from gaudi_predictor_loss_grad (None where the tensor has no gradient path)."""
 from __future__ import annotations
 
 import numpy as np
+import torch
 
 from ._lib import GaudiError
 from .models_edm import _like_ref, _to_numpy
@@ -47,14 +49,75 @@ def compute_loss(model, x, h, node_mask, edge_mask, target, edm_model, edm_args,
         t_int = torch.randint(0, T + 1, size=(B, 1)).float()  # the reference's draw (torch RNG stream)
     else:
         t_int = torch.ones(B, 1).float() * float(t_fix)
+    if getattr(model, "training", False):
+        return _loss_with_grad(model, edm_model, x, h, node_mask, edge_mask, t_int.numpy().reshape(-1), target, noise)
     zt, pred = _run(model, edm_model, x, h, node_mask, edge_mask, t_int / T, noise)
     err = np.abs(pred - _to_numpy(target).astype(np.float32))
     return _like_ref(np.float32(err.mean())), _like_ref(err)
 
 
+def _loss_with_grad(model, edm_model, x, h, node_mask, edge_mask, t_int, target, noise):
+    """compute_loss in train mode: loss and gradients in one call; loss.backward() hands the gradients to torch."""
+    import torch
+    if model.engine is not edm_model.engine:
+        raise GaudiError("the predictor must be attached to this model (get_cond_predictor_model(..., model=model))")
+    x = _to_numpy(x).astype(np.float32)
+    B, N = x.shape[0], x.shape[1]
+    nm = _to_numpy(node_mask).astype(np.float32).reshape(B, N)
+    em = (nm[:, :, None] * nm[:, None, :] * (1 - np.eye(N, dtype=np.float32)) if edge_mask is None
+          else _to_numpy(edge_mask).astype(np.float32).reshape(B, N, N))
+    y = _to_numpy(target).astype(np.float32).reshape(B, -1)
+    seed, off = edm_model.next_stream(B)
+    names, params = zip(*model.named_parameters())
+    loss, pred, grads = model.engine.predictor_loss_grad(x, _to_numpy(h).astype(np.float32), np.round(t_int).astype(np.int32),
+                                                         nm, em, y, seed=seed, sample_offset=off, noise=noise)
+    g = tuple(None if grads[n] is None else torch.from_numpy(grads[n]) for n in names)
+    return _L1.apply(torch.tensor(loss), g, *params), _like_ref(np.abs(pred - y))
+
+
+class _L1(torch.autograd.Function):
+    """The loss of gaudi_predictor_loss_grad as a function of the parameters: backward hands over the device gradients
+    (scaled by the incoming gradient), None where a tensor has no gradient path."""
+
+    @staticmethod
+    def forward(ctx, loss, grads, *params):
+        ctx.grads = grads
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        return (None, None) + tuple(None if g is None else g * go for g in ctx.grads)
+
+
+def train_epoch(epoch, cond_predictor, edm_model, dataloader, optimizer, args, writer, edm_args):
+    """cond_prediction/train_cond_predictor.py:84-125 over a loader of (x, node_mask, edge_mask, node_features, y)."""
+    import time
+    cond_predictor.train()
+    start = time.time()
+    loss_list, rl_loss = [], []
+    for x, node_mask, edge_mask, node_features, y in dataloader:
+        x = _to_numpy(x).astype(np.float32)
+        nm3 = _to_numpy(node_mask).astype(np.float32).reshape(x.shape[0], x.shape[1], 1)
+        x = x - (x * nm3).sum(1, keepdims=True) / np.maximum(nm3.sum(1, keepdims=True), 1) * nm3  # remove_mean_with_mask
+        loss, _ = compute_loss(cond_predictor, x, node_features, nm3, edge_mask, y, edm_model, edm_args)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        loss_list.append(loss.item())
+        rescale = getattr(dataloader.dataset, "rescale_loss", None)
+        rl_loss.append(float(rescale(loss)) if rescale is not None else loss.item())
+    print(f"[{epoch}|train] loss: {np.mean(loss_list):.4f}+-{np.std(loss_list):.4f}, "
+          f"L1 (rescaled): {np.mean(rl_loss):.4f},  in {int(time.time() - start)} secs")
+    if writer is not None:
+        writer.add_scalar("Train loss", np.mean(loss_list), epoch)
+        writer.add_scalar("Train L1 (rescaled)", np.mean(rl_loss), epoch)
+    return loss_list
+
+
 def val_epoch(tag, cond_predictor, edm_model, dataloader, args, edm_args, t_fix=None):
     """eval_cond_predictor.py:34-89: mean absolute error (rescaled by the dataset std) over a loader of
     (x, node_mask, edge_mask, node_features, y) batches."""
+    cond_predictor.eval()  # eval_cond_predictor.py:35: the forward-only path
     losses, errors = [], []
     for x, node_mask, edge_mask, node_features, y in dataloader:
         x = _to_numpy(x).astype(np.float32)

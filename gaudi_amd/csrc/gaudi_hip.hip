@@ -119,6 +119,7 @@ struct gaudi_handle {
   bool fix_noise = false;     // en_diffusion.py:562-566: one raw draw per call, broadcast over the batch
   long long fix_key = 0;      // global sample index whose Philox stream is shared
   int readout_n = 0;  // padded N the predictor readout divides by (0 = the call's N)
+  struct PredTrainState* pt = nullptr;  // the predictor in torch layout for gaudi_predictor_loss_grad (pred_train_host.inc)
   // Plan hint (gaudi_set_plan_hint): the kernel family and the edge-GEMM arithmetic of a call follow from batch-wide maxima
   // (edge slots, a node's live edges).  A shard of a larger logical batch plans with the WHOLE batch's figures, so that a
   // molecule's rounding does not depend on where the batch was cut.  call_* = the same, set by gaudi_sample for its own
@@ -209,6 +210,11 @@ static int fail(gaudi_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;
   return code;
 }
+
+// pred_train_host.inc
+static void pt_release(gaudi_handle* h);
+static int pt_load(gaudi_handle* h, const gaudi_pred_config* cfg, int n, const char* const* names, const float* const* tensors,
+                   const int64_t* numel);
 
 // -------------------------------------------------------------------------------------------------
 // noise schedule: PredefinedNoiseSchedule / polynomial_schedule / clip_noise_schedule
@@ -1607,6 +1613,7 @@ void gaudi_destroy(gaudi_handle* h) {
                     &h->d_sflags, &h->d_sdist, &h->d_sadj, &h->d_saux, &h->d_stab, &h->d_as, &h->d_ncols, &h->d_soff, &h->d_sidx,
                     &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp};
   for (DevBuf* b : bufs) b->release();
+  pt_release(h);
   h->p_pred.release();
   h->p_dpred.release();
   h->p_z.release();
@@ -2621,5 +2628,6 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 }  // extern "C"
 
 #include "pred_host.inc"
+#include "pred_train_host.inc"
 #include "stability.inc"
 #include "nll_host.inc"

@@ -155,6 +155,7 @@ int gaudi_load_predictor(gaudi_handle* h, const gaudi_pred_config* cfg, int n, c
   if (!HP) return fail(h, GAUDI_E_INVALID, "no kernel instantiated for this hidden size");
   Tensors T;
   for (int i = 0; i < n; ++i) T.m[names[i]] = {tensors[i], numel[i]};
+  if (h->warn.rfind("predictor weights:", 0) == 0) h->warn.clear();  // a reload reports the weights it loads, not the last ones
   PredLayout lay{HP, F1, K, L};
   const std::string p = "egnn.";
   const int PK = HP * HP;
@@ -265,6 +266,10 @@ int gaudi_load_predictor(gaudi_handle* h, const gaudi_pred_config* cfg, int n, c
     pack(false, w, nullptr);
     HIPCHECK(h, h->pred_w4.reserve(sizeof(float) * w.size()));
     HIPCHECK(h, hipMemcpy(h->pred_w4.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
+  }
+  {
+    const int rc = pt_load(h, cfg, n, names, tensors, numel);
+    if (rc) return rc;
   }
   h->pcfg = *cfg;
   h->HPP = HP;

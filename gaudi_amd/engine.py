@@ -169,8 +169,20 @@ class Engine:
         n, c_names, c_ptrs, c_numel, keep = self._tensor_args(sd)
         self._check(self.lib.gaudi_load_predictor(self.h, C.byref(cfg), n, c_names, c_ptrs, c_numel),
                     "gaudi_load_predictor")
+        # a reload reports the weights now loaded: a predictor fallback of the previous weights no longer holds
+        reason = getattr(self, "_fallback_reason", None)
+        if reason and reason.startswith("predictor weights") and self._warning() != reason:
+            self._fallback_reason = None
         self._note_fallback()
         self.pred_args, self.K = dict(args), K
+        self.pred_names = list(sd.keys())
+        self.pred_shapes = [sd[k].shape for k in self.pred_names]
+
+    pred_sync = None  # set by a trainable CondPredictor: pushes parameters an optimizer changed before any predictor call
+
+    def _sync_pred(self):
+        if self.pred_sync is not None:
+            self.pred_sync()
 
     # ------------------------------------------------------------------ tables
     def gamma(self) -> np.ndarray:
@@ -200,6 +212,7 @@ class Engine:
         return out
 
     def predictor_fwd(self, z, t, node_mask, edge_mask) -> np.ndarray:
+        self._sync_pred()
         z = f32(z)
         B, N, D = z.shape
         nm, em = self._masks(node_mask, edge_mask, B, N)
@@ -210,6 +223,7 @@ class Engine:
         return out
 
     def predictor_grad(self, z, t, node_mask, edge_mask, dpred):
+        self._sync_pred()
         z = f32(z)
         B, N, D = z.shape
         nm, em = self._masks(node_mask, edge_mask, B, N)
@@ -222,6 +236,7 @@ class Engine:
         return pred, grad
 
     def step(self, s_idx, z_t, node_mask, edge_mask, eps_raw, target_w=None, scale=1.0) -> np.ndarray:
+        self._sync_pred()
         z = f32(z_t)
         B, N, D = z.shape
         nm, em = self._masks(node_mask, edge_mask, B, N)
@@ -246,6 +261,7 @@ class Engine:
     # ------------------------------------------------------------------ whole chain
     def sample(self, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None, std=1.0, target_w=None, scale=1.0,
                return_z0=False):
+        self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]
         nm, em = self._masks(nm, edge_mask, B, N)
@@ -271,6 +287,7 @@ class Engine:
 
     def predict_noised(self, x, onehot, t_int, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None):
         """sample_edm_t + predictor forward in one launch -> (z_t [B,N,3+F], pred [B,K])."""
+        self._sync_pred()
         x = f32(x)
         B, N = x.shape[0], x.shape[1]
         oh = f32(onehot).reshape(B, N, self.F)
@@ -287,6 +304,39 @@ class Engine:
                                                   fptr(em), int(seed), int(sample_offset), fptr(nz), fptr(zt),
                                                   fptr(pred)), "gaudi_predict_noised")
         return zt, pred
+
+    def predictor_loss_grad(self, x, onehot, t_int, node_mask, edge_mask, y, *, seed=0, sample_offset=0, noise=None):
+        """compute_loss + loss.backward() of the predictor (include/gaudi_hip.h: gaudi_predictor_loss_grad) ->
+        (loss, pred [B,K], {name: d loss / d tensor, or None where the tensor has no gradient path}) in the names and
+        shapes of the state dict given to load_predictor.  Inputs as predict_noised, plus the targets y [B,K]."""
+        self._sync_pred()
+        x = f32(x)
+        B, N = x.shape[0], x.shape[1]
+        oh = f32(onehot).reshape(B, N, self.F)
+        nm, em = self._masks(f32(node_mask).reshape(B, N), edge_mask, B, N)
+        ti = np.ascontiguousarray(np.broadcast_to(np.asarray(t_int).reshape(-1), (B,)), dtype=np.int32)
+        yy = f32(y).reshape(B, self.K)
+        nz = None
+        if noise is not None:
+            nz = f32(noise)
+            if nz.shape != (B, N, 3 + self.F):
+                raise GaudiError(f"noise must be [B,N,3+F] = {(B, N, 3 + self.F)}, got {nz.shape}")
+        n = C.c_int64(0)
+        self._check(self.lib.gaudi_predictor_grad_size(self.h, C.byref(n)), "gaudi_predictor_grad_size")
+        grad = np.zeros(int(n.value), np.float32)
+        has = np.zeros(len(self.pred_names), np.int32)
+        loss = np.zeros(1, np.float32)
+        pred = np.empty((B, self.K), np.float32)
+        self._check(self.lib.gaudi_predictor_loss_grad(self.h, B, N, fptr(x), fptr(oh), ti.ctypes.data_as(_lib.IP), fptr(nm),
+                                                       fptr(em), fptr(yy), int(seed), int(sample_offset), fptr(nz),
+                                                       fptr(loss), fptr(pred), fptr(grad), has.ctypes.data_as(_lib.IP)),
+                    "gaudi_predictor_loss_grad")
+        out, pos = {}, 0
+        for name, shape, g in zip(self.pred_names, self.pred_shapes, has):
+            size = int(np.prod(shape))
+            out[name] = grad[pos:pos + size].reshape(shape) if g else None
+            pos += size
+        return float(loss[0]), pred, out
 
     def edm_nll(self, x, onehot, t_int, node_mask, edge_mask, *, seed, sample_offset, noise=None, return_terms=False):
         """The EDM's negative log-likelihood of (x, onehot) in one launch (include/gaudi_hip.h: gaudi_edm_nll) -> nll [B], or
@@ -315,6 +365,7 @@ class Engine:
         reverse step between the two device phases (include/gaudi_hip.h: gaudi_sample_cb).  with_z=True: the target also
         depends on z outside the predictor -- ``target_grad(z_s [B,N,D], pred [B,K], t) -> (dT/dpred [B,K], dT/dz [B,N,D])``
         with dT/dz the DIRECT part, pred held fixed (gaudi_sample_cbz)."""
+        self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]
         nm, em = self._masks(nm, edge_mask, B, N)
@@ -375,6 +426,7 @@ class Engine:
 
     def sample_chain(self, node_mask, edge_mask, keep_frames, *, seed=0, sample_offset=0, noise=None, std=1.0):
         """-> chain [keep_frames, B, N, 3+F] (frame 0 = final [x | one_hot])."""
+        self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]
         nm, em = self._masks(nm, edge_mask, B, N)

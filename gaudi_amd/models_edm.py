@@ -587,6 +587,64 @@ class CondPredictor:
         self.engine = model.engine
         self.engine.load_predictor(self.args, state_dict)
         self.K = self.engine.K
+        self._state = state_dict
+
+    training = False
+    _params = None  # name -> torch.nn.Parameter, created on first use (parameters(), state_dict(), train())
+    _pushed = None  # the parameters' version counters when the device copy was last loaded
+
+    def _ensure_params(self):
+        if self._params is None:
+            if self._state is None:
+                raise GaudiError("a predictor attached with from_engine has no host copy of its weights to train")
+            import torch
+            from .engine import _strip
+            sd = _strip(self._state)
+            self._params = {k: torch.nn.Parameter(torch.from_numpy(v.copy())) for k, v in sd.items()}
+            self._pushed = self._versions()
+            self.engine.pred_sync = self._sync
+        return self._params
+
+    def _versions(self):
+        return tuple(p._version for p in self._params.values())
+
+    def _sync(self):
+        """Parameters changed in place (optimizer.step(), load_state_dict) reach the device before the next predictor call."""
+        if self._params is not None and self._versions() != self._pushed:
+            sd = {k: p.detach().numpy() for k, p in self._params.items()}
+            self._pushed = self._versions()
+            self.engine.load_predictor(self.args, sd)
+
+    def named_parameters(self):
+        """(name, torch.nn.Parameter) in the reference's state-dict names (EGNN_predictor.named_parameters)."""
+        return iter(self._ensure_params().items())
+
+    def parameters(self):
+        return iter(self._ensure_params().values())
+
+    def state_dict(self):
+        """A copy that get_cond_predictor_model (and the reference's EGNN_predictor.load_state_dict) reloads."""
+        import collections
+        return collections.OrderedDict((k, p.detach().clone()) for k, p in self._ensure_params().items())
+
+    def load_state_dict(self, state_dict):
+        import torch
+        from .engine import _strip
+        params = self._ensure_params()
+        sd = _strip(state_dict)
+        if set(sd) != set(params):
+            raise GaudiError(f"load_state_dict: names differ from the predictor's: {sorted(set(sd) ^ set(params))[:4]}")
+        with torch.no_grad():
+            for k, p in params.items():
+                p.copy_(torch.from_numpy(sd[k]))
+        self._sync()
+
+    def train(self, mode: bool = True):
+        """compute_loss then returns a loss whose backward() fills p.grad (gaudi_amd/cond_prediction.py); train(False) = eval()."""
+        if mode:
+            self._ensure_params()
+        self.training = bool(mode)
+        return self
 
     @classmethod
     def from_engine(cls, model: GaudiModel, args) -> "CondPredictor":
@@ -595,11 +653,13 @@ class CondPredictor:
         cp.args = checkpoint.args_dict(args)
         cp.engine = model.engine
         cp.K = model.engine.K
+        cp._state = None
         model.cond_predictor = cp
         return cp
 
     def eval(self):
-        return self
+        """Back to the forward-only path: compute_loss / val_epoch evaluate without the reverse pass."""
+        return self.train(False)
 
     _override = None  # set while a target closure is being traced (GaudiModel._trace_closure): the stand-in prediction
 

@@ -126,6 +126,26 @@ int gaudi_predict_noised(gaudi_handle* h, int B, int N, const float* x, const fl
                          const float* node_mask, const float* edge_mask, uint64_t seed, int64_t sample_offset,
                          const float* noise, float* zt_out /* [B,N,3+F] or NULL */, float* pred_out /* [B,K] or NULL */);
 
+/* The predictor's training step: cond_prediction/train_cond_predictor.py compute_loss (:64-81) followed by loss.backward().
+ * Inputs as gaudi_predict_noised, plus y [B,K] (the targets).  z_t and pred come from the same launch as gaudi_predict_noised
+ * (pred_out [B,K] or NULL receives the numbers it returns); loss_out [1] = l1_loss(pred, y) = mean |pred - y|.
+ * grad_out receives d loss / d w for every predictor tensor, in the order and the row-major shape of the names passed to
+ * gaudi_load_predictor, concatenated (gaudi_predictor_grad_size gives the float count).  has_grad_out [n names] = 1 where the
+ * tensor has a gradient path, 0 where it has none (the last layer's coord_mlp, whose coordinate output is never read, and any
+ * name the predictor does not use): those entries of grad_out are not written -- torch leaves .grad at None for them.
+ * The seed dpred = sign(pred - y) / (B K) (sign(0) = 0) runs back through a separate fp32 reverse pass over the unpadded
+ * weights (pred_train.h); the weight gradients are reduced on the fp32 matrix instruction in a fixed order without atomics,
+ * so two identical calls give bit-identical gradients.  Every kernel family is accepted on purpose (4-wave, V4G / V8G,
+ * GAUDI_EDGE_MATH=fp32, refused fp16-pair images): the forward is whatever gaudi_predict_noised runs, and the reverse pass
+ * does not depend on it.  N up to 128 (GAUDI_E_CAPACITY beyond); the batch is processed in slices of at most 1 GiB of
+ * scratch. */
+int gaudi_predictor_loss_grad(gaudi_handle* h, int B, int N, const float* x, const float* onehot, const int32_t* t_int,
+                              const float* node_mask, const float* edge_mask, const float* y /* [B,K] */, uint64_t seed,
+                              int64_t sample_offset, const float* noise /* [B,N,3+F] or NULL */, float* loss_out /* [1] */,
+                              float* pred_out /* [B,K] or NULL */, float* grad_out, int32_t* has_grad_out);
+/* Floats of gaudi_predictor_loss_grad's grad_out: the summed numel of the tensors passed to gaudi_load_predictor. */
+int gaudi_predictor_grad_size(gaudi_handle* h, int64_t* n_floats);
+
 /* The EDM's negative log-likelihood of data: EnVariationalDiffusion.forward in eval mode (en_diffusion.py:777-805, compute_loss
  * with t0_always = True).  x [B,N,3] (un-normalised, masked, mean-free), onehot [B,N,F], t_int [B] in 1..T (refused otherwise).
  * One launch of the EDM-only kernels evaluates the network twice per molecule: at z_t = alpha_t * xh + sigma_t * eps and
@@ -235,6 +255,13 @@ int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, i
 /* ---- Device-free host logic (no handle, no GPU): exposed so the CPU test suite can check it. ----
  * gamma [T+1] and (optionally) the per-step table [T][4] exactly as gaudi_load_edm builds them. */
 int gaudi_host_schedule(int T, float noise_power /* 0 = cosine */, float noise_precision, float* gamma_out, float* coef_out);
+/* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
+ * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
+ * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),
+ * has_grad_out[n] = the no-gradient-path rule, wt_out (or NULL) = the flat buffer with every matrix transposed.
+ * GAUDI_E_MISSING when a known name has the wrong size. */
+int gaudi_host_pred_train_layout(const gaudi_pred_config* cfg, int n, const char* const* names, const float* const* tensors,
+                                 const int64_t* numel, int32_t* off_out, int32_t* has_grad_out, float* wt_out);
 /* The network-free terms of gaudi_edm_nll, computed by the same function: terms_out [B][4] = kl_prior, neg_log_constants,
  * delta_log_px and the SNR weight SNR(gamma_s - gamma_t) - 1 of t_int[b] (1..T) for the schedule of gaudi_host_schedule and
  * normalize_factors (norm_x, norm_h). */

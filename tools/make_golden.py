@@ -1291,6 +1291,108 @@ def g25_nll():
     save("g25_nll", **out)
 
 
+def _proj_summary(g, seed):
+    """Compact record of a large gradient tensor: sum, sum of squares, 8 fixed random projections, 64 sampled entries
+    (tests/test_gpu_pred_train.py:_proj_summary recomputes the same from the device gradient)."""
+    g = np.asarray(g, np.float64).reshape(-1)
+    r = np.random.Generator(np.random.Philox(key=seed))
+    proj = r.standard_normal((8, g.size))
+    idx = r.integers(0, g.size, 64)
+    return np.concatenate([[g.sum(), (g * g).sum()], proj @ g, g[idx]]).astype(np.float64)
+
+
+def g26_pred_grad():
+    """compute_loss + loss.backward() of the predictor (cond_prediction/train_cond_predictor.py:64-81, 84-125) under injected
+    noise: the full gradient of every tensor (None -> listed in *_nograd), the loss, for tiny cata / hetro predictors with
+    attention and tanh on, one case with both off, t = 0, 500, T and mixed; two AdamW(amsgrad) steps of train_epoch on the
+    tiny cata case; and one default-width case (nf 196, 2 layers) stored as per-tensor summaries."""
+    from cond_prediction import train_cond_predictor as tcp
+    out = {}
+    cases = [  # name, dataset, nodes, predictor overrides, t tags
+        ("cata", "cata", [4, 11, 7, 1, 11], dict(TINY_P, attention=True, tanh=True), ("t0", "tmix")),
+        ("hetro", "hetro", [3, 9, 6, 10, 20], dict(TINY_P, attention=True, tanh=True), ("t500", "tT")),
+        ("plain", "cata", [5, 11, 8], dict(TINY_P, attention=False, tanh=False), ("tmix",)),
+        ("full", "cata", [11, 9, 11], dict(nf=196, n_layers=2), ("tmix",)),
+    ]
+    for ci, (name, ds, nodes, over, tags) in enumerate(cases):
+        F = synth.num_node_features(ds)
+        eargs = synth.edm_args(dataset=ds, **TINY)
+        esd = synth.synth_edm_state_dict(eargs, F, seed=2600 + ci)
+        a, model = build_ref_edm(ds, esd, **TINY)
+        psd = synth.synth_predictor_state_dict(synth.pred_args(dataset=ds, **over), F, 5, seed=2610 + ci, amplify_coord=True)
+        pa, pred = build_ref_pred(ds, psd, **over)
+        for prm in pred.parameters():
+            prm.requires_grad_(True)
+        nm, em, z = case_inputs(ds, nodes, None, seed=2620 + ci, guidance_pad=(ds != "cata"))
+        B, N, D = z.shape
+        rng = np.random.default_rng(2630 + ci)
+        x = (z[:, :, :3] * 3.0).astype(np.float32)
+        cls = rng.integers(0, F, (B, N))
+        h = (np.eye(F, dtype=np.float32)[cls] * nm).astype(np.float32)
+        out[f"{name}_x"], out[f"{name}_h"] = x, h
+        out[f"{name}_node_mask"], out[f"{name}_edge_mask"] = nm, em
+        tx, th, tnm, tem = (torch.from_numpy(v) for v in (x, h, nm, em))
+        T = a.diffusion_steps
+        names = list(pred.state_dict().keys())
+        for tag in tags:
+            t_int = dict(t0=np.zeros(B), t500=np.full(B, 500.0), tT=np.full(B, float(T)),
+                         tmix=rng.integers(0, T + 1, B).astype(np.float64))[tag]
+            eps = rng_noise(2640 + 10 * ci + len(tag), (B, N, D))
+            t = torch.from_numpy((t_int / T).astype(np.float32)).view(B, 1)
+            with InjectNoise([eps]), torch.no_grad():
+                p0 = pred(tcp.sample_edm_t(tx, th, model, t, tnm), tnm, tem.view(B, N * N), t).numpy()
+            sgn = np.where(rng.random(p0.shape) < 0.5, -1.0, 1.0)
+            y = (p0 + sgn * (0.5 + rng.random(p0.shape))).astype(np.float32)
+            randint0 = torch.randint
+            torch.randint = lambda low, high, size, device=None, **kw: torch.from_numpy(t_int.reshape(B, 1)).long()
+            try:
+                pred.zero_grad(set_to_none=True)
+                with InjectNoise([eps]):
+                    loss, _ = tcp.compute_loss(pred, tx, th, tnm, tem, torch.from_numpy(y), model, a)
+                loss.backward()
+            finally:
+                torch.randint = randint0
+            k = f"{name}_{tag}"
+            out[k + "_t_int"], out[k + "_eps"], out[k + "_y"] = t_int.astype(np.int32), eps, y
+            out[k + "_loss"] = np.float32(loss.item())
+            nograd = [n for n, prm in pred.named_parameters() if prm.grad is None]
+            out[k + "_nograd"] = np.array(json.dumps(nograd))
+            for n, prm in pred.named_parameters():
+                if prm.grad is None:
+                    continue
+                if name == "full":
+                    out[f"{k}_sum.{n}"] = _proj_summary(prm.grad.numpy(), 2650 + names.index(n))
+                else:
+                    out[f"{k}_g.{n}"] = prm.grad.numpy()
+        if name == "cata":  # two steps of train_epoch's loop: zero_grad, backward, AdamW(amsgrad) step
+            pred.load_state_dict({kk: torch.from_numpy(v.copy()) for kk, v in psd.items()})
+            opt = torch.optim.AdamW(pred.parameters(), lr=pa.lr, amsgrad=True, weight_decay=1e-12)
+            y = torch.from_numpy(rng.standard_normal((B, 5)).astype(np.float32))
+            losses = []
+            for step in range(2):
+                t_int = rng.integers(0, T + 1, B).astype(np.float64)
+                eps = rng_noise(2690 + step, (B, N, D))
+                randint0 = torch.randint
+                torch.randint = lambda low, high, size, device=None, **kw: torch.from_numpy(t_int.reshape(B, 1)).long()
+                try:
+                    with InjectNoise([eps]):
+                        loss, _ = tcp.compute_loss(pred, tx, th, tnm, tem, y, model, a)
+                finally:
+                    torch.randint = randint0
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+                losses.append(loss.item())
+                out[f"adam_{step}_t_int"], out[f"adam_{step}_eps"] = t_int.astype(np.int32), eps
+            out["adam_y"], out["adam_losses"], out["adam_lr"] = y.numpy(), np.array(losses, np.float32), np.float32(pa.lr)
+        out[f"{name}_cfg"] = np.array(json.dumps(dict(dataset=ds, over=over, eseed=2600 + ci, pseed=2610 + ci, T=T,
+                                                      tags=list(tags), names=names)))
+        print(f"g26 {name}: N {N} losses {[float(out[f'{name}_{tg}_loss']) for tg in tags]}")
+    save("g26_pred_grad", **{k: v for k, v in out.items() if not k.startswith(("hetro_", "plain_"))})
+    save("g26_pred_grad_hetro", **{k: v for k, v in out.items() if k.startswith("hetro_")})
+    save("g26_pred_grad_plain", **{k: v for k, v in out.items() if k.startswith("plain_")})
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1316,7 +1418,7 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad)
     which = sys.argv[1:] or list(fns)
     for w in which:
         fns[w]()
