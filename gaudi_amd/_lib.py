@@ -118,11 +118,19 @@ EXPORTS = {
     "gaudi_predictor_grad_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gaudi_host_pred_train_layout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64),
                                                IP, IP, FP]),
+    "gaudi_edm_loss_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, IP, FP, FP, C.c_uint64, C.c_int64, FP, C.c_int, FP,
+                                      FP, FP, FP, IP]),
+    "gaudi_edm_grad_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "gaudi_edm_set_train_weights": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64)]),
+    "gaudi_host_edm_train_layout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64),
+                                              IP, IP, FP]),
+    "gaudi_host_edm_seed_coef": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, FP, FP, FP]),
 }
 
 ABI_VERSION = 7  # include/gaudi_hip.h: GAUDI_ABI_VERSION
 _ROUND6_EXPORTS = ("gaudi_last_warning", "gaudi_abi_version", "gaudi_last_family_split", "gaudi_profile_clock", "gaudi_last_keep_h")  # an older A/B library (GAUDI_LIB) lacks them
-_NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_grad_size")  # ... and the NLL / training entry
+_NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_grad_size", "gaudi_edm_loss_grad",
+                "gaudi_edm_grad_size", "gaudi_edm_set_train_weights")  # ... and the NLL / training entry
 # points (same ABI version: no existing signature changed)
 
 _lib = None

@@ -120,6 +120,8 @@ struct gaudi_handle {
   long long fix_key = 0;      // global sample index whose Philox stream is shared
   int readout_n = 0;  // padded N the predictor readout divides by (0 = the call's N)
   struct PredTrainState* pt = nullptr;  // the predictor in torch layout for gaudi_predictor_loss_grad (pred_train_host.inc)
+  struct EdmTrainState* et = nullptr;   // the denoiser in torch layout for gaudi_edm_loss_grad (edm_train_host.inc)
+  bool edm_stale = false;  // gaudi_edm_set_train_weights changed the weights after the sampler images were packed
   // Plan hint (gaudi_set_plan_hint): the kernel family and the edge-GEMM arithmetic of a call follow from batch-wide maxima
   // (edge slots, a node's live edges).  A shard of a larger logical batch plans with the WHOLE batch's figures, so that a
   // molecule's rounding does not depend on where the batch was cut.  call_* = the same, set by gaudi_sample for its own
@@ -213,6 +215,12 @@ static int fail(gaudi_handle* h, int code, const std::string& msg) {
 
 // pred_train_host.inc
 static void pt_release(gaudi_handle* h);
+// edm_train_host.inc
+static void et_release(gaudi_handle* h);
+static int et_upload(gaudi_handle* h, const gaudi_edm_config* cfg, int n, const char* const* names, const float* const* tensors,
+                     const int64_t* numel);
+static const char* et_check(const gaudi_edm_config* cfg, int n, const char* const* names, const int64_t* numel);
+extern const char* const kEdmStale;
 static int pt_load(gaudi_handle* h, const gaudi_pred_config* cfg, int n, const char* const* names, const float* const* tensors,
                    const int64_t* numel);
 
@@ -1614,6 +1622,7 @@ void gaudi_destroy(gaudi_handle* h) {
                     &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp};
   for (DevBuf* b : bufs) b->release();
   pt_release(h);
+  et_release(h);
   h->p_pred.release();
   h->p_dpred.release();
   h->p_z.release();
@@ -1775,6 +1784,8 @@ int gaudi_load_edm(gaudi_handle* h, const gaudi_edm_config* cfg, int n, const ch
   const bool want_split = h->variant == 8 && h->split && EF == 2;
   pack(h->variant == 8 && EF == 2, w, want_split ? &ws : nullptr);
   if (!T.missing.empty()) return fail(h, GAUDI_E_MISSING, "EDM checkpoint tensor missing or mis-shaped: " + T.missing);
+  if (const char* bad = et_check(cfg, n, names, numel))  // the training copy's table, before anything is replaced
+    return fail(h, GAUDI_E_MISSING, std::string("EDM tensor mis-shaped: ") + bad);
   HIPCHECK(h, h->edm_w.reserve(sizeof(float) * w.size()));
   HIPCHECK(h, hipMemcpy(h->edm_w.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
   h->edm_w_bytes = sizeof(float) * w.size();
@@ -1797,6 +1808,13 @@ int gaudi_load_edm(gaudi_handle* h, const gaudi_edm_config* cfg, int n, const ch
   h->ecfg = *cfg;
   h->HPE = HP;
   h->has_edm = true;
+  h->edm_stale = false;
+  // the torch-layout copy of the training kernels (edm_train_host.inc): both copies now hold these weights
+  const int rc_train = et_upload(h, cfg, n, names, tensors, numel);
+  if (rc_train) {  // (an upload error: no half-loaded handle)
+    h->has_edm = false;
+    return rc_train;
+  }
   return GAUDI_OK;
 }
 
@@ -1818,6 +1836,7 @@ int gaudi_phi(gaudi_handle* h, int B, int N, const float* z, const float* t, con
               const float* edge_mask, float* eps_out) {
   if (!h || !z || !t || !node_mask || !edge_mask || !eps_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   HIPCHECK(h, hipSetDevice(h->device));
   KParams P{};
   int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, 0);
@@ -1888,6 +1907,7 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
                      float* z_out, float* x_out, float* onehot_out, int* nan_count, float* chain_out = nullptr,
                      int keep_frames = 0) {
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
   HIPCHECK(h, hipSetDevice(h->device));
   KParams P{};
@@ -2020,6 +2040,7 @@ int gaudi_step(gaudi_handle* h, int B, int N, int s_idx, const float* z_t, const
                const float* edge_mask, const float* eps_raw, const float* target_w, float scale, float* zs_out) {
   if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   const int T = h->ecfg.diffusion_steps;
   return run_chain(h, B, N, node_mask, edge_mask, z_t, false, s_idx, s_idx, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f,
                    target_w, scale, zs_out, nullptr, nullptr, nullptr);
@@ -2029,6 +2050,7 @@ int gaudi_decode(gaudi_handle* h, int B, int N, const float* z0, const float* no
                  const float* eps_raw, float* x_out, float* onehot_out) {
   if (!h || !z0 || !node_mask || !edge_mask || !eps_raw || !x_out || !onehot_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   const int T = h->ecfg.diffusion_steps;
   return run_chain(h, B, N, node_mask, edge_mask, z0, false, -1, 0, true, eps_raw, T + 1, 1, 0, 0, 1.0f, nullptr, 0.f,
                    nullptr, x_out, onehot_out, nullptr);
@@ -2074,6 +2096,7 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
                  float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
   if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
   if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
   HIPCHECK(h, hipSetDevice(h->device));
@@ -2202,6 +2225,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
                           gaudi_diag* diag) {
   if (!h || !node_mask || !edge_mask || !x_out || !onehot_out || (!target_grad && !target_grad_z)) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
 #ifdef GAUDI_STAMPS
   // the stamped diagnostic build times the fused step only: its 8-wave guide phase drops the direct dT/dz term (sampler_kernel.h)
@@ -2371,6 +2395,7 @@ int gaudi_sample_chain(gaudi_handle* h, int B, int N, const float* node_mask, co
                        int64_t sample_offset, const float* noise, float std, int keep_frames, float* chain_out) {
   if (!h || !node_mask || !edge_mask || !chain_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   const int T = h->ecfg.diffusion_steps, F = h->ecfg.in_node_nf, D = 3 + F;
   if (keep_frames < 1 || keep_frames > T) return fail(h, GAUDI_E_INVALID, "keep_frames must be in 1..T");
   std::vector<float> x((size_t)B * N * 3), oh((size_t)B * N * F);
@@ -2631,3 +2656,4 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 #include "pred_train_host.inc"
 #include "stability.inc"
 #include "nll_host.inc"
+#include "edm_train_host.inc"

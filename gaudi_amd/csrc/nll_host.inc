@@ -49,6 +49,7 @@ static int run_edm_nll(gaudi_handle* h, int B, int N, const float* x, const floa
                        const float* node_mask, const float* edge_mask, uint64_t seed, int64_t sample_offset, const float* noise,
                        float* nll_out, float* terms_out) {
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
   if (N > 255) return fail(h, GAUDI_E_CAPACITY, "N must be at most 255");  // (one node slot per thread in the MODE_NLL sums)
   HIPCHECK(h, hipSetDevice(h->device));

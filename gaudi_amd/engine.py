@@ -150,6 +150,9 @@ class Engine:
         self._check(self.lib.gaudi_load_edm(self.h, C.byref(cfg), n, c_names, c_ptrs, c_numel), "gaudi_load_edm")
         self._note_fallback()
         self.edm_args, self.F, self.T = dict(args), F, int(args["diffusion_steps"])
+        self.edm_names = list(sd.keys())
+        self.edm_shapes = [sd[k].shape for k in self.edm_names]
+        self._edm_train_sd = None  # weights given to edm_set_train_weights since this load (the sampler images lag behind)
         # EnVariationalDiffusion.check_issues_norm_values (en_diffusion.py:336-349): the reference refuses to BUILD a model whose
         # sigma_0 is not small against 1 / norm_value (8 standard deviations) -- e.g. 'cosine' with the default
         # normalize_factors [3, 4, 10]; a checkpoint it could never have produced is refused here as well
@@ -178,6 +181,17 @@ class Engine:
         self.pred_names = list(sd.keys())
         self.pred_shapes = [sd[k].shape for k in self.pred_names]
 
+    edm_sync = None  # set by a GaudiModel: pushes parameters an optimizer changed (edm_set_train_weights) before an EDM call
+
+    def _sync_edm(self, sampler: bool = True):
+        """Before an EDM call: let the model push changed parameters; before a sampler-kernel call (sampler=True) also
+        rebuild the sampler's images with load_edm when edm_set_train_weights has left them stale, once per change."""
+        if self.edm_sync is not None:
+            self.edm_sync()
+        if sampler and getattr(self, "_edm_train_sd", None) is not None:
+            sd, self._edm_train_sd = self._edm_train_sd, None
+            self.load_edm(self.edm_args, sd)
+
     pred_sync = None  # set by a trainable CondPredictor: pushes parameters an optimizer changed before any predictor call
 
     def _sync_pred(self):
@@ -203,6 +217,7 @@ class Engine:
         return nm, em
 
     def phi(self, z, t, node_mask, edge_mask) -> np.ndarray:
+        self._sync_edm()
         z = f32(z)
         B, N, D = z.shape
         nm, em = self._masks(node_mask, edge_mask, B, N)
@@ -236,6 +251,7 @@ class Engine:
         return pred, grad
 
     def step(self, s_idx, z_t, node_mask, edge_mask, eps_raw, target_w=None, scale=1.0) -> np.ndarray:
+        self._sync_edm()
         self._sync_pred()
         z = f32(z_t)
         B, N, D = z.shape
@@ -248,6 +264,7 @@ class Engine:
         return out
 
     def decode(self, z0, node_mask, edge_mask, eps_raw):
+        self._sync_edm()
         z = f32(z0)
         B, N, D = z.shape
         nm, em = self._masks(node_mask, edge_mask, B, N)
@@ -261,6 +278,7 @@ class Engine:
     # ------------------------------------------------------------------ whole chain
     def sample(self, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None, std=1.0, target_w=None, scale=1.0,
                return_z0=False):
+        self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]
@@ -343,6 +361,7 @@ class Engine:
         (nll [B], terms [B,6]) with return_terms: kl_prior, loss_t, neg_log_constants, loss_term_0, delta_log_px, error.
         x [B,N,3] un-normalised, masked, mean-free; onehot [B,N,F]; t_int [B] in 1..T; noise [2,B,N,3+F] raw draws or None
         (Philox draws 0 / 1 of (seed, sample_offset + b))."""
+        self._sync_edm()
         x = f32(x)
         B, N = x.shape[0], x.shape[1]
         oh = f32(onehot).reshape(B, N, self.F)
@@ -359,12 +378,69 @@ class Engine:
                                            int(seed), int(sample_offset), fptr(nz), fptr(nll), fptr(terms)), "gaudi_edm_nll")
         return (nll, terms) if return_terms else nll
 
+    def edm_set_train_weights(self, state_dict: dict):
+        """Replace the torch-layout weights the training kernels read (include/gaudi_hip.h: gaudi_edm_set_train_weights) with
+        state_dict, in the names, order and shapes given to load_edm.  No repack: the sampler's images go stale, and the next
+        sampler-kernel call through this Engine rebuilds them with load_edm first."""
+        sd = _strip(state_dict)
+        if list(sd.keys()) != self.edm_names:
+            raise GaudiError("edm_set_train_weights needs the state dict keys of load_edm, in the same order")
+        n, c_names, c_ptrs, c_numel, keep = self._tensor_args(sd)
+        self._check(self.lib.gaudi_edm_set_train_weights(self.h, n, c_names, c_ptrs, c_numel), "gaudi_edm_set_train_weights")
+        # a copy: _strip may alias the caller's arrays, and the sampler must reload exactly what the training copy holds
+        self._edm_train_sd = {k: v.copy() for k, v in sd.items()}
+
+    def edm_loss_grad(self, x, onehot, t_int, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None, loss_type="l2",
+                      weight=None, grad=True):
+        """The EDM's train-mode loss per molecule and sum_b weight_b d loss_b / d w (include/gaudi_hip.h: gaudi_edm_loss_grad)
+        -> (loss [B], net [B,N,3+F], {name: gradient, or None where the tensor has no gradient path}); with grad=False the
+        dict is empty (forward only).  x [B,N,3] un-normalised, masked, mean-free; onehot [B,N,F]; t_int [B] in 0..T;
+        noise [B,N,3+F] raw draws or None (Philox draw 0 of (seed, sample_offset + b)); loss_type 'l2' or 'vlb';
+        weight [B] or None (1 each)."""
+        self._sync_edm(sampler=False)
+        if loss_type not in ("l2", "vlb"):
+            raise GaudiError(f"diffusion_loss_type must be 'l2' or 'vlb', got {loss_type!r}")
+        x = f32(x)
+        B, N = x.shape[0], x.shape[1]
+        oh = f32(onehot).reshape(B, N, self.F)
+        nm, em = self._masks(f32(node_mask).reshape(B, N), edge_mask, B, N)
+        ti = np.ascontiguousarray(np.broadcast_to(np.asarray(t_int).reshape(-1), (B,)), dtype=np.int32)
+        D = 3 + self.F
+        nz = None
+        if noise is not None:
+            nz = f32(noise)
+            if nz.shape != (B, N, D):
+                raise GaudiError(f"noise must be [B,N,3+F] = {(B, N, D)}, got {nz.shape}")
+        w = None if weight is None else f32(np.broadcast_to(np.asarray(weight, np.float32).reshape(-1), (B,)))
+        loss = np.empty(B, np.float32)
+        net = np.empty((B, N, D), np.float32)
+        gbuf, has = None, None
+        if grad:
+            n = C.c_int64(0)
+            self._check(self.lib.gaudi_edm_grad_size(self.h, C.byref(n)), "gaudi_edm_grad_size")
+            gbuf = np.zeros(int(n.value), np.float32)
+            has = np.zeros(len(self.edm_names), np.int32)
+        self._check(self.lib.gaudi_edm_loss_grad(self.h, B, N, fptr(x), fptr(oh), ti.ctypes.data_as(_lib.IP), fptr(nm),
+                                                 fptr(em), int(seed), int(sample_offset), fptr(nz),
+                                                 0 if loss_type == "l2" else 1, fptr(w), fptr(loss), fptr(net), fptr(gbuf),
+                                                 None if has is None else has.ctypes.data_as(_lib.IP)),
+                    "gaudi_edm_loss_grad")
+        out = {}
+        if grad:
+            pos = 0
+            for name, shape, g in zip(self.edm_names, self.edm_shapes, has):
+                size = int(np.prod(shape))
+                out[name] = gbuf[pos:pos + size].reshape(shape) if g else None
+                pos += size
+        return loss, net, out
+
     def sample_callback(self, node_mask, edge_mask, target_grad, *, seed=0, sample_offset=0, noise=None, std=1.0,
                         scale=1.0, return_z0=False, with_z=False):
         """Guided chain for an arbitrary target: ``target_grad(pred [B,K], t) -> dT/dpred [B,K]`` is called once per
         reverse step between the two device phases (include/gaudi_hip.h: gaudi_sample_cb).  with_z=True: the target also
         depends on z outside the predictor -- ``target_grad(z_s [B,N,D], pred [B,K], t) -> (dT/dpred [B,K], dT/dz [B,N,D])``
         with dT/dz the DIRECT part, pred held fixed (gaudi_sample_cbz)."""
+        self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]
@@ -426,6 +502,7 @@ class Engine:
 
     def sample_chain(self, node_mask, edge_mask, keep_frames, *, seed=0, sample_offset=0, noise=None, std=1.0):
         """-> chain [keep_frames, B, N, 3+F] (frame 0 = final [x | one_hot])."""
+        self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)
         B, N = nm.shape[0], nm.shape[1]

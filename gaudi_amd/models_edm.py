@@ -297,6 +297,7 @@ class GaudiModel:
         self.sample_offset = 0
         self.injected_noise = None  # [T+2,B,N,3+F] raw draws (parity tests); None -> on-device Philox
         self.last_diag = None
+        self._state = state_dict
         import weakref
         GaudiModel._latest = weakref.ref(self)
 
@@ -384,14 +385,118 @@ class GaudiModel:
             return lt
         return pt
 
-    def eval(self):
-        return self
+    # ---- training (train_edm.py:52-94).  Unlike an nn.Module, a GaudiModel starts in eval mode: model(...) is the eval-mode
+    # NLL until train() is called.  The parameters are torch tensors on the host in the reference's names (gamma.gamma with
+    # requires_grad=False, then every dynamics.egnn tensor); changes made in place (optimizer.step(), load_state_dict) reach
+    # the training kernels through Engine.edm_set_train_weights before the next EDM call, and the sampler's images are
+    # rebuilt (Engine.load_edm) only before the next sampler-kernel call.
+    training = False
+    _state = None   # the state dict the model was built from (None: from_engine, nothing to train)
+    _params = None  # name -> torch.nn.Parameter, created on first use
+    _pushed = None  # the parameters' version counters when the device copy was last set
+
+    def _ensure_params(self):
+        if self._params is None:
+            if self._state is None:
+                raise GaudiError("training needs the host copy of the weights: a model built with from_engine has none")
+            import collections
+            import torch
+            from .engine import _strip
+            sd = _strip(self._state)
+            gamma = sd.get("gamma.gamma")
+            if gamma is None:
+                gamma = self.engine.gamma().astype(np.float32)
+            params = collections.OrderedDict()
+            params["gamma.gamma"] = torch.nn.Parameter(torch.from_numpy(np.array(gamma, np.float32)), requires_grad=False)
+            for k in self.engine.edm_names:
+                if k.startswith("dynamics."):
+                    params[k] = torch.nn.Parameter(torch.from_numpy(sd[k].copy()))
+            self._buffer = torch.from_numpy(np.asarray(sd.get("buffer", np.zeros(1, np.float32)), np.float32).copy())
+            self._params = params
+            self._pushed = self._versions()
+            self.engine.edm_sync = self._sync
+        return self._params
+
+    def _versions(self):
+        return tuple(p._version for p in self._params.values())
+
+    def _sync(self):
+        """Parameters changed in place reach the training kernels (no repack) before the next EDM call."""
+        if self._params is not None and self._versions() != self._pushed:
+            self._pushed = self._versions()
+            sd = {}
+            for k in self.engine.edm_names:
+                if k in self._params:
+                    sd[k] = self._params[k].detach().numpy()
+                elif k == "buffer":
+                    sd[k] = self._buffer.numpy()
+            self.engine.edm_set_train_weights(sd)
+
+    def named_parameters(self):
+        """(name, torch.nn.Parameter) in the reference's names and order (EnVariationalDiffusion.named_parameters)."""
+        return iter(self._ensure_params().items())
+
+    def parameters(self):
+        return iter(self._ensure_params().values())
+
+    def state_dict(self):
+        """A copy in the reference's keys (buffer, gamma.gamma, dynamics.*) that its strict load_state_dict and get_model
+        accept."""
+        import collections
+        params = self._ensure_params()
+        out = collections.OrderedDict(buffer=self._buffer.clone())
+        for k, p in params.items():
+            out[k] = p.detach().clone()
+        return out
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        import torch
+        from .engine import _strip
+        params = self._ensure_params()
+        sd = _strip(state_dict)
+        missing = set(params) - set(sd)
+        if missing or (strict and set(sd) - set(params) - {"buffer"}):
+            raise GaudiError(f"load_state_dict: keys differ from the model's: {sorted(set(sd) ^ set(params))[:4]}")
+        with torch.no_grad():
+            for k, p in params.items():
+                p.copy_(torch.from_numpy(sd[k]))
+        self._sync()
 
     def train(self, mode: bool = True):
-        """Training (the t0_always=False estimator and any backward pass through the weights) is not part of this port."""
-        if not mode:
-            return self
-        raise GaudiError("training is out of scope: GaudiModel evaluates the eval-mode NLL only (call model.eval())")
+        """model(...) then returns the train-mode loss per molecule (compute_loss with t0_always=False), whose backward()
+        fills every dynamics.* .grad; train(False) = eval()."""
+        if mode:
+            loss_type = self.args.get("diffusion_loss_type", "l2")
+            if loss_type not in ("l2", "vlb"):
+                raise GaudiError(f"diffusion_loss_type must be 'l2' or 'vlb', got {loss_type!r}")
+            self._ensure_params()
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        """Back to the eval-mode NLL (two network passes, no reverse pass)."""
+        return self.train(False)
+
+    def _train_forward(self, xn, hc, nm, em):
+        """en_diffusion.py:777-792 in train mode -> the per-molecule loss [B] through _EdmLoss."""
+        import torch
+        B = xn.shape[0]
+        params = self._ensure_params()
+        loss_type = self.args.get("diffusion_loss_type", "l2")
+        t_int = torch.randint(0, self.T + 1, size=(B, 1)).float()  # t0_always=False: t = 0 included (:657-659)
+        ti = t_int.numpy().reshape(B).astype(np.int32)
+        noise = self.injected_noise
+        noise = None if noise is None or np.shape(noise)[0] != 1 else np.asarray(noise)[0]  # [1,B,N,3+F]: ONE draw
+        seed, off = self.next_stream(B)
+
+        def call(weight=None):
+            return self.engine.edm_loss_grad(xn, hc, ti, nm, em, seed=seed, sample_offset=off, noise=noise,
+                                             loss_type=loss_type, weight=weight)
+
+        loss, _, grads = call()
+        names = list(params)
+        g = tuple(None if grads.get(k) is None else torch.from_numpy(grads[k]) for k in names)
+        return _edm_loss_apply(torch.from_numpy(loss), (names, g, call), *params.values())
 
     # ---- en_diffusion.py:777-805 (eval mode)
     def forward(self, x, h, node_mask=None, edge_mask=None, context=None):
@@ -415,6 +520,8 @@ class GaudiModel:
         hc = _to_numpy(h["categorical"]).astype(np.float32).reshape(B, N, self.in_node_nf)
         assert_correctly_masked(hc, nm)
         assert_mean_zero_with_mask(xn, nm)  # (compute_loss asserts it on z_t, en_diffusion.py:680)
+        if self.training:
+            return self._train_forward(xn, hc, nm, em)
         t_int = torch.randint(1, self.T + 1, size=(B, 1)).float()  # t0_always: lowest_t = 1 (:651-659)
         noise = self.injected_noise
         if noise is None or np.shape(noise)[0] != 2:
@@ -674,15 +781,100 @@ class CondPredictor:
                                                    _to_numpy(edge_mask).reshape(B, N, N)))
 
 
+_EDM_LOSS = None  # the torch.autograd.Function below, built on first use (torch is imported lazily here)
+
+
+def _edm_loss_apply(loss, ctx_data, *params):
+    global _EDM_LOSS
+    if _EDM_LOSS is None:
+        _EDM_LOSS = _make_edm_loss()
+    return _EDM_LOSS.apply(loss, ctx_data, *params)
+
+
+def _make_edm_loss():
+    import torch
+
+    class _EdmLoss(torch.autograd.Function):
+        """The per-molecule loss of gaudi_edm_loss_grad as a function of the parameters.  The forward call kept
+        G = sum_b g_b; an incoming gradient c that is the same for every molecule (loss.mean(0), loss.sum()) gives c G, any
+        other one re-runs the call with weight = grad_output (same t, noise stream or injected noise)."""
+
+        @staticmethod
+        def forward(ctx, loss, data, *ps):
+            ctx.data = data
+            return loss.clone()
+
+        @staticmethod
+        def backward(ctx, go):
+            names, grads, call = ctx.data
+            if bool(torch.all(go == go.reshape(-1)[0])):
+                c = go.reshape(-1)[0]
+                out = tuple(None if g is None else g * c for g in grads)
+            else:
+                rerun = call(weight=go.detach().numpy().astype(np.float32).reshape(-1))[2]
+                out = tuple(None if rerun.get(k) is None else torch.from_numpy(rerun[k]) for k in names)
+            return (None, None) + out
+
+    return _EdmLoss
+
+
+def init_edm_state_dict(args, in_node_nf: int) -> dict:
+    """Fresh weights of EGNN_dynamics drawn as the reference's modules draw them from torch's default generator, in
+    construction order (egnn_new.py:268-312 EGNN, 194-222 EquivariantBlock, 6-44 GCL, 96-121 EquivariantUpdate: its
+    bias-free last layer, xavier with gain 0.001, is built BEFORE coord_mlp's first two linears).  nn.Linear itself draws
+    them, so the numbers are torch's; gamma.gamma is the schedule table and buffer zero (en_diffusion.py:216-218)."""
+    import torch
+    a = checkpoint.args_dict(args)
+    H, L, S = int(a["nf"]), int(a["n_layers"]), int(a.get("inv_sublayers", 1))
+    A = 24 if a.get("sin_embedding") else 2
+    F1 = int(in_node_nf) + 1
+    sd = {"buffer": np.zeros(1, np.float32)}
+
+    def lin(name, i, o, layer=None):
+        m = layer if layer is not None else torch.nn.Linear(i, o)
+        sd[name + ".weight"] = m.weight.detach().numpy().copy()
+        if m.bias is not None:
+            sd[name + ".bias"] = m.bias.detach().numpy().copy()
+
+    p = "dynamics.egnn."
+    lin(p + "embedding", F1, H)
+    lin(p + "embedding_out", H, F1)
+    for l in range(L):
+        b = f"{p}e_block_{l}."
+        for s in range(S):
+            q = f"{b}gcl_{s}."
+            lin(q + "edge_mlp.0", 2 * H + A, H)
+            lin(q + "edge_mlp.2", H, H)
+            lin(q + "node_mlp.0", 2 * H, H)
+            lin(q + "node_mlp.2", H, H)
+            if a["attention"]:
+                lin(q + "att_mlp.0", H, 1)
+        last = torch.nn.Linear(H, 1, bias=False)
+        torch.nn.init.xavier_uniform_(last.weight, gain=0.001)
+        q = f"{b}gcl_equiv.coord_mlp."
+        lin(q + "0", 2 * H + A, H)
+        lin(q + "2", H, H)
+        lin(q + "4", H, 1, layer=last)
+    return sd
+
+
 def get_model(args, dataloader_train=None, only_norm=True, device: int = 0, state_dict=None):
     """models_edm.get_model (models_edm.py:61-104) -> (model, nodes_dist, prop_dist).
 
-    ``dataloader_train.dataset`` is only consulted for ``mean``/``std`` (property normalisation)."""
+    ``dataloader_train.dataset`` is only consulted for ``mean``/``std`` (property normalisation) and, without a checkpoint,
+    for ``num_node_features``.  Without args.restore or a state dict the model starts from fresh weights
+    (init_edm_state_dict), as the reference's does."""
     a = checkpoint.args_dict(args)
     if state_dict is None:
-        if not a.get("restore"):
-            raise GaudiError("get_model needs a checkpoint (args.restore / exp_dir) or an explicit state_dict")
-        state_dict = checkpoint.load_state_dict(a["exp_dir"])
+        if a.get("restore"):
+            state_dict = checkpoint.load_state_dict(a["exp_dir"])
+        else:
+            ds = getattr(dataloader_train, "dataset", None)
+            F = getattr(ds, "num_node_features", None)
+            if F is None:
+                from . import synth
+                F = synth.num_node_features(a.get("dataset", "cata"))
+            state_dict = init_edm_state_dict(a, int(F))
     model = GaudiModel(a, state_dict, device=device)
     prop_dist = None
     ds = getattr(dataloader_train, "dataset", None)

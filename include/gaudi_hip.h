@@ -146,6 +146,29 @@ int gaudi_predictor_loss_grad(gaudi_handle* h, int B, int N, const float* x, con
 /* Floats of gaudi_predictor_loss_grad's grad_out: the summed numel of the tensors passed to gaudi_load_predictor. */
 int gaudi_predictor_grad_size(gaudi_handle* h, int64_t* n_floats);
 
+/* EDM training: EnVariationalDiffusion in train mode (train_edm.py:36-50; en_diffusion.py:644-805 with t0_always = False)
+ * and the gradient of its per-molecule loss with respect to every dynamics.egnn tensor.  Inputs as gaudi_edm_nll, except
+ * t_int [B] in 0..T and noise = ONE draw [B,N,3+F] (or NULL: Philox draw 0 of (seed, sample_offset + b)).  loss_type 0 = l2,
+ * 1 = vlb.  loss_out [B] = the per-molecule loss (before compute_loss's .mean(0)); net_out [B,N,3+F] (or NULL) = phi(z_t, t).
+ * grad_out (or NULL: forward only) = sum_b weight_b d loss_b / d w (weight NULL: 1 each) in the layout of the names given to
+ * gaudi_load_edm (gaudi_edm_grad_size floats); has_grad_out [n names] = 1 for every dynamics.egnn tensor, 0 for the others
+ * (gamma.gamma, buffer), whose entries are not written.  The reverse pass is separate fp32 HIP over the torch-layout weights
+ * (edm_train.h) with a fixed-order reduction: two identical calls give bit-identical results.  N up to 128
+ * (GAUDI_E_CAPACITY beyond); the batch runs in slices of at most 1 GiB of scratch. */
+int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const float* onehot, const int32_t* t_int,
+                        const float* node_mask, const float* edge_mask, uint64_t seed, int64_t sample_offset,
+                        const float* noise /* [B,N,3+F] or NULL */, int loss_type, const float* weight /* [B] or NULL */,
+                        float* loss_out /* [B] */, float* net_out /* [B,N,3+F] or NULL */, float* grad_out /* or NULL */,
+                        int32_t* has_grad_out);
+/* Floats of gaudi_edm_loss_grad's grad_out: the summed numel of the tensors passed to gaudi_load_edm. */
+int gaudi_edm_grad_size(gaudi_handle* h, int64_t* n_floats);
+/* Replace only the torch-layout copy (and its transposes) that gaudi_edm_loss_grad reads; names, order and sizes must be
+ * those of gaudi_load_edm.  No repack: the sampler's weight images become stale, and every entry point that runs the
+ * sampler kernels (gaudi_phi, gaudi_step, gaudi_decode, gaudi_sample and its callback / chain forms, gaudi_edm_nll) fails with
+ * GAUDI_E_STATE, naming gaudi_load_edm, until gaudi_load_edm rebuilds both copies. */
+int gaudi_edm_set_train_weights(gaudi_handle* h, int n, const char* const* names, const float* const* tensors,
+                                const int64_t* numel);
+
 /* The EDM's negative log-likelihood of data: EnVariationalDiffusion.forward in eval mode (en_diffusion.py:777-805, compute_loss
  * with t0_always = True).  x [B,N,3] (un-normalised, masked, mean-free), onehot [B,N,F], t_int [B] in 1..T (refused otherwise).
  * One launch of the EDM-only kernels evaluates the network twice per molecule: at z_t = alpha_t * xh + sigma_t * eps and
@@ -262,6 +285,17 @@ int gaudi_host_schedule(int T, float noise_power /* 0 = cosine */, float noise_p
  * GAUDI_E_MISSING when a known name has the wrong size. */
 int gaudi_host_pred_train_layout(const gaudi_pred_config* cfg, int n, const char* const* names, const float* const* tensors,
                                  const int64_t* numel, int32_t* off_out, int32_t* has_grad_out, float* wt_out);
+/* The layout gaudi_edm_loss_grad reads the denoiser in (edm_train_host.inc: et_layout): off_out[4 + L (10 S + 5)] = float
+ * offset of each role (head: embedding w/b, embedding_out w/b; per block, per GCL: edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0
+ * w/b, node_mlp.0 w/b, node_mlp.2 w/b; then gcl_equiv.coord_mlp.0 w/b, .2 w/b, .4 w; -1: absent), has_grad_out[n], and
+ * wt_out (or NULL) = the flat buffer with every matrix transposed.  GAUDI_E_MISSING when a known name has the wrong size. */
+int gaudi_host_edm_train_layout(const gaudi_edm_config* cfg, int n, const char* const* names, const float* const* tensors,
+                                const int64_t* numel, int32_t* off_out, int32_t* has_grad_out, float* wt_out);
+/* The seed of gaudi_edm_loss_grad's reverse pass, by the function the call uses: d loss_b / d net = coef (net - eps), with
+ * coef_out [B][2] = (x columns, h columns) for loss_type (0 l2, 1 vlb), t_int [B] in 0..T, snr_w [B] = SNR(s - t) - 1 (read
+ * for vlb at t > 0 only), D = 3 + F, padded N, and weight [B] (or NULL: 1 each). */
+int gaudi_host_edm_seed_coef(int loss_type, int B, int T, int D, int N, const int32_t* t_int, const float* snr_w,
+                             const float* weight, float* coef_out);
 /* The network-free terms of gaudi_edm_nll, computed by the same function: terms_out [B][4] = kl_prior, neg_log_constants,
  * delta_log_px and the SNR weight SNR(gamma_s - gamma_t) - 1 of t_int[b] (1..T) for the schedule of gaudi_host_schedule and
  * normalize_factors (norm_x, norm_h). */

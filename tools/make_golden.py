@@ -1393,6 +1393,202 @@ def g26_pred_grad():
     save("g26_pred_grad_plain", **{k: v for k, v in out.items() if k.startswith("plain_")})
 
 
+def g27_edm_grad():
+    """EDM training, in float64: model.train(); loss = model(x, h, node_mask, edge_mask) (the per-molecule loss of compute_loss with
+    t0_always = False, en_diffusion.py:644-805, before train_edm.py's .mean(0)); loss.sum().backward() under a fixed t_int
+    (torch.randint patched) and InjectNoise([eps]).  Gradients are switched on for dynamics.* only (gamma.gamma keeps
+    requires_grad=False).  Per case: per-molecule losses, net, the full gradients (tiny widths) or _proj_summary records
+    (default widths), the no-grad list, and the parameter / state-dict key lists.  One file per group, as g26."""
+    groups = {
+        "g27_edm_grad": [  # name, dataset, nodes, max_nodes, over, weight seed, amplify, t_int rule
+            ("cata_mixed", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50), 2700, True, "mixed"),
+            ("cata_t0", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50), 2701, True, "zero"),
+            ("cata_vlb", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50, diffusion_loss_type="vlb"), 2702, True,
+             "mixed"),
+        ],
+        "g27_edm_grad_hetro": [
+            ("hetro_500_T", "hetro", [3, 9, 6, 20], None, dict(TINY), 2703, True, "500_T"),
+            ("plain_mean", "hetro", [5, 8, 10], None, dict(TINY, diffusion_steps=50, attention=False, tanh=False,
+                                                          inv_sublayers=2, aggregation_method="mean", norm_constant=0.5,
+                                                          coords_range=7.0), 2704, True, "mixed"),
+            ("cata_sin", "cata", [4, 11, 7, 2, 11], 11, dict(TINY, diffusion_steps=50, sin_embedding=True), 2705, True,
+             "mixed"),
+        ],
+        "g27_edm_grad_default": [
+            ("cata_default", "cata", [11, 11, 11], 11, {}, 2706, False, "mixed"),
+        ],
+    }
+    for fname, cases in groups.items():
+        out = {}
+        for ci, (name, ds, nodes, mx, over, wseed, amp, trule) in enumerate(cases):
+            F = synth.num_node_features(ds)
+            esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=wseed, amplify_coord=amp)
+            a, model = build_ref_edm(ds, esd, **over)
+            model.double()  # float64: the yardstick is the exact gradient, not one fp32 summation order
+            for k, prm in model.named_parameters():
+                prm.requires_grad_(k.startswith("dynamics."))
+            model.train()
+            nm, em, z = case_inputs(ds, nodes, mx, seed=wseed + 20, guidance_pad=mx is None)
+            B, N, D = z.shape
+            T = a.diffusion_steps
+            rng = np.random.default_rng(wseed + 30)
+            x = (z[:, :, :3] * 3.0).astype(np.float32)
+            h = (np.eye(F, dtype=np.float32)[rng.integers(0, F, (B, N))] * nm).astype(np.float32)
+            if trule == "zero":
+                t_int = np.zeros(B, np.int64)
+            elif trule == "500_T":
+                t_int = np.array([min(500, T), T] * B)[:B]
+            else:
+                t_int = rng.integers(0, T + 1, B)
+                t_int[0], t_int[-1] = 0, T
+            eps = rng_noise(wseed + 40, (B, N, D))
+            tx, th, tnm, tem = (torch.from_numpy(v).double() for v in (x, h, nm, em))
+            hd = {"categorical": th, "integer": torch.zeros(0, dtype=torch.float64)}
+            rec = []
+            phi0, randint0 = model.phi, torch.randint
+
+            def phi_rec(zz, tt, *rest):
+                o = phi0(zz, tt, *rest)
+                rec.append((zz.detach().clone(), tt.detach().clone(), o.detach().clone()))
+                return o
+
+            def randint_fixed(low, high, size, device=None, **kw):
+                assert (low, high, tuple(size)) == (0, T + 1, (B, 1)), (low, high, size)
+                return torch.from_numpy(t_int.reshape(B, 1)).long()
+
+            model.phi = phi_rec
+            torch.randint = randint_fixed
+            try:
+                with InjectNoise([eps], dtype=torch.float64):
+                    loss = model(tx, hd, tnm, tem.view(B, N * N))
+            finally:
+                torch.randint = randint0
+                del model.phi
+            loss.sum().backward()
+            assert len(rec) == 1
+            # the per-molecule loss as the fp32 reference computes it (log p(h | z_0) at t = 0 is a difference of nearly equal
+            # Phi values: the recorded loss is the fp32 one, the gradients the exact ones)
+            _, m32 = build_ref_edm(ds, esd, **over)
+            for k, prm in m32.named_parameters():
+                prm.requires_grad_(k.startswith("dynamics."))
+            m32.train()
+            rec32 = []
+            phi32 = m32.phi
+            m32.phi = lambda zz, tt, *rest: rec32.append(phi32(zz, tt, *rest)) or rec32[-1]
+            torch.randint = randint_fixed
+            try:
+                with InjectNoise([eps]):
+                    loss32 = m32(*(torch.from_numpy(v) for v in (x,)), {"categorical": torch.from_numpy(h),
+                                                                         "integer": torch.zeros(0)},
+                                 torch.from_numpy(nm), torch.from_numpy(em).view(B, N * N))
+            finally:
+                torch.randint = randint0
+                del m32.phi
+            if over.get("sin_embedding"):  # the fp32 reference's own spread from the exact values (the tests' bound)
+                loss32.sum().backward()
+                out[name + "_net32"] = rec32[0].detach().numpy()
+                for k, prm in m32.named_parameters():
+                    if prm.grad is not None:
+                        out[name + "_grad32:" + k] = prm.grad.numpy()
+            loss32 = loss32.detach()
+            zt, _, net = rec[0]
+            names = [k for k, _ in model.named_parameters()]
+            nograd = [k for k, prm in model.named_parameters() if prm.grad is None]
+            out[name + "_cfg"] = np.array(json.dumps(dict(dataset=ds, over=over, wseed=wseed, amp=amp, nodes=nodes, T=T)))
+            out[name + "_x"], out[name + "_h"], out[name + "_node_mask"], out[name + "_edge_mask"] = x, h, nm, em
+            out[name + "_t_int"] = t_int.astype(np.int32)
+            out[name + "_noise"] = eps
+            out[name + "_loss"] = loss32.numpy()
+            out[name + "_loss64"] = loss.detach().numpy()
+            out[name + "_zt"], out[name + "_net"] = zt.numpy().astype(np.float32), net.numpy()
+            out[name + "_params"] = np.array(json.dumps(names))
+            out[name + "_state_keys"] = np.array(json.dumps(list(model.state_dict().keys())))
+            out[name + "_nograd"] = np.array(json.dumps(nograd))
+            for pi, (k, prm) in enumerate(model.named_parameters()):
+                if prm.grad is None:
+                    continue
+                g = prm.grad.numpy()
+                if name == "cata_default":
+                    out[name + "_gsum:" + k] = _proj_summary(g, 2790 + pi)
+                else:
+                    out[name + "_grad:" + k] = g.astype(np.float32)
+            print(f"g27 {name}: loss {loss.detach().numpy()} t {t_int} nograd {nograd}")
+        save(fname, **out)
+
+
+def g27_edm_train():
+    """EDM training loop and initialisation (g27_edm_train): two iterations of train_edm.py:52-94 on the tiny cata case --
+    compute_loss in train mode, zero_grad, backward, edm/utils.py gradient_clipping with the Queue seeded with 3000
+    (train_edm.py:155-156), AdamW(lr, amsgrad=True, weight_decay=1e-12) (:152-154) -- with t_int and the noise fixed per
+    iteration: losses, grad norms and the trained dynamics.* weights.  And the reference's fresh state dict after
+    torch.manual_seed(0) (get_model without restore) for a tiny config with attention and one with two sub-layers."""
+    import train_edm as ref_train
+    from edm.utils import Queue as RQueue, gradient_clipping as rclip
+    out = {}
+    ds, nodes, over, wseed = "cata", [4, 11, 7, 2, 11], dict(TINY, diffusion_steps=50), 2710
+    F = synth.num_node_features(ds)
+    esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=wseed, amplify_coord=True)
+    a, model = build_ref_edm(ds, esd, **over)
+    for k, prm in model.named_parameters():
+        prm.requires_grad_(k.startswith("dynamics."))
+    nm, em, z = case_inputs(ds, nodes, 11, seed=wseed + 20)
+    B, N, D = z.shape
+    T = a.diffusion_steps
+    rng = np.random.default_rng(wseed + 30)
+    x = (z[:, :, :3] * 3.0).astype(np.float32)
+    h = (np.eye(F, dtype=np.float32)[rng.integers(0, F, (B, N))] * nm).astype(np.float32)
+    optim = torch.optim.AdamW(model.parameters(), lr=a.lr, amsgrad=True, weight_decay=1e-12)
+    q = RQueue(max_len=50)
+    q.add(3000)
+    losses, norms, ts, epss = [], [], [], []
+    randint0 = torch.randint
+    for it in range(2):
+        t_int = rng.integers(0, T + 1, B)
+        eps = rng_noise(wseed + 40 + it, (B, N, D))
+
+        def randint_fixed(low, high, size, device=None, **kw):
+            assert (low, high, tuple(size)) == (0, T + 1, (B, 1)), (low, high, size)
+            return torch.from_numpy(t_int.reshape(B, 1)).long()
+
+        model.train()
+        torch.randint = randint_fixed
+        try:
+            with InjectNoise([eps]):
+                loss = ref_train.compute_loss(model, torch.from_numpy(x), torch.from_numpy(h), torch.from_numpy(nm),
+                                              torch.from_numpy(em))
+        finally:
+            torch.randint = randint0
+        optim.zero_grad()
+        loss.backward()
+        gn = rclip(model, q)
+        optim.step()
+        losses.append(loss.item())
+        norms.append(float(gn))
+        ts.append(t_int.astype(np.int32))
+        epss.append(eps)
+    out["train_cfg"] = np.array(json.dumps(dict(dataset=ds, over=over, wseed=wseed, amp=True, nodes=nodes, T=T, lr=a.lr)))
+    out["train_x"], out["train_h"], out["train_node_mask"], out["train_edge_mask"] = x, h, nm, em
+    out["train_t_int"], out["train_noise"] = np.stack(ts), np.stack(epss)
+    out["train_loss"], out["train_grad_norm"] = np.array(losses), np.array(norms)
+    for k, v in model.state_dict().items():
+        if k.startswith("dynamics."):
+            out["train_w:" + k] = v.numpy()
+    for name, o in (("init_att", dict(TINY)), ("init_plain", dict(TINY, attention=False, inv_sublayers=2,
+                                                                         sin_embedding=True))):
+        ra = Args_EDM().parse_args([])
+        ra.device, ra.dp, ra.restore, ra.dataset = torch.device("cpu"), False, None, "cata"
+        for k, v in o.items():
+            setattr(ra, k, v)
+        torch.manual_seed(0)
+        m, _, _ = models_edm.get_model(ra, FakeLoader(1, 5), only_norm=True)
+        out[name + "_cfg"] = np.array(json.dumps(o))
+        out[name + "_keys"] = np.array(json.dumps(list(m.state_dict().keys())))
+        for k, v in m.state_dict().items():
+            out[name + ":" + k] = v.numpy()
+    print(f"g27_edm_train: losses {losses} grad norms {norms}")
+    save("g27_edm_train", **out)
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1418,7 +1614,7 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train)
     which = sys.argv[1:] or list(fns)
     for w in which:
         fns[w]()
