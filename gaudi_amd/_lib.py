@@ -125,6 +125,12 @@ EXPORTS = {
     "gaudi_host_edm_train_layout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64),
                                               IP, IP, FP]),
     "gaudi_host_edm_seed_coef": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, FP, FP, FP]),
+    "gaudi_sample_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, C.c_uint64, C.c_int64, FP, C.c_float, FP, C.c_float,
+                                    C.c_int, IP, FP, FP, FP, FP, FP, FP, C.POINTER(Diag)]),
+    "gaudi_step_pair": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, FP, FP, FP, FP, FP, C.c_float, FP]),
+    "gaudi_sample_cb_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, C.c_uint64, C.c_int64, FP, C.c_float, TARGET_CB,
+                                       TARGET_CBZ, C.c_void_p, C.c_float, C.c_int, IP, FP, FP, FP, FP, FP, FP, C.POINTER(Diag)]),
+    "gaudi_host_grid_coefficients": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_int, IP, FP, IP]),
 }
 
 ABI_VERSION = 7  # include/gaudi_hip.h: GAUDI_ABI_VERSION
@@ -132,6 +138,7 @@ _ROUND6_EXPORTS = ("gaudi_last_warning", "gaudi_abi_version", "gaudi_last_family
 _NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_grad_size", "gaudi_edm_loss_grad",
                 "gaudi_edm_grad_size", "gaudi_edm_set_train_weights")  # ... and the NLL / training entry
 # points (same ABI version: no existing signature changed)
+_GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")  # ... and the time-grid chains
 
 _lib = None
 
@@ -159,7 +166,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -179,3 +186,19 @@ def fptr(a: np.ndarray | None):
 
 def f32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def grid_coefficients(T: int, noise_power: float, noise_precision: float, grid):
+    """The step table of a time grid as the chains build it (include/gaudi_hip.h: gaudi_host_grid_coefficients; needs no
+    device) -> (coef [n-1,4] = alpha_t|s, sigma2_t|s / alpha_t|s / sigma_t, sigma, t of step g[k] -> g[k+1];
+    land [n-1] = the time index each step lands on)."""
+    lib = load_library()
+    g = np.ascontiguousarray(np.asarray(grid).reshape(-1), dtype=np.int32)
+    coef = np.zeros((max(len(g) - 1, 0), 4), np.float32)
+    land = np.zeros(max(len(g) - 1, 0), np.int32)
+    rc = lib.gaudi_host_grid_coefficients(int(T), float(noise_power), float(noise_precision), len(g), g.ctypes.data_as(IP),
+                                          coef.ctypes.data_as(FP), land.ctypes.data_as(IP))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_grid_coefficients failed ({rc}): the grid must be strictly descending integers "
+                         f"T >= g[0] > ... > g[n] = 0 with at least two entries")
+    return coef, land

@@ -84,7 +84,7 @@ struct gaudi_handle {
   // per-call workspaces
   DevBuf d_mask, d_order, d_edges, d_emask, d_npairs, d_seg, d_zin, d_zout, d_t, d_x, d_h, d_noise, d_nan, d_dpred,
       d_pred, d_tw, d_stash, d_chain, d_sx, d_stype, d_sn, d_sflags, d_sdist, d_sadj, d_saux, d_stab, d_as, d_ncols, d_soff,
-      d_sidx, d_gnode, d_rowmap, d_compmol, d_ncomp, d_clock;
+      d_sidx, d_gnode, d_rowmap, d_compmol, d_ncomp, d_clock, d_gcoef, d_gidx, d_zt;  // d_gcoef / d_gidx / d_zt: time-grid chains
   PinBuf p_pred, p_dpred;     // gaudi_sample_cb: pred [B,K] device -> host, dT/dpred [B,K] host -> device, once per step
   PinBuf p_z, p_dz;           // gaudi_sample_cbz: z_s [B,N,D] device -> host, scale * dT/dz host -> device
   DevBuf d_dz;
@@ -283,18 +283,49 @@ static inline float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-
 static inline float sigmoid_host(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // en_diffusion.py:433-457 (sigma_and_alpha_t_given_s), :365-373 (sigma), :843-849 (mu / sigma of p(z_s|z_t))
+// one row for the step from time index t_idx down to s_idx (any pair s_idx < t_idx, as the reference's functions take)
+static void coef_row(const std::vector<float>& g, int T, int s_idx, int t_idx, float* row) {
+  const float gs = g[s_idx], gt = g[t_idx];
+  const float sigma2 = -expm1f(softplus_f(gs) - softplus_f(gt));
+  const float alpha_ts = expf(0.5f * (logsigmoid_f(-gt) - logsigmoid_f(-gs)));
+  const float sigma_ts = sqrtf(sigma2);
+  const float sigma_s = sqrtf(sigmoid_host(gs)), sigma_t = sqrtf(sigmoid_host(gt));
+  row[0] = alpha_ts;
+  row[1] = sigma2 / alpha_ts / sigma_t;
+  row[2] = sigma_ts * sigma_s / sigma_t;
+  row[3] = (float)t_idx / (float)T;
+}
 static void make_coef(const std::vector<float>& g, int T, std::vector<float>& coef) {
   coef.resize((size_t)T * 4);
-  for (int s = 0; s < T; ++s) {
-    const float gs = g[s], gt = g[s + 1];
-    const float sigma2 = -expm1f(softplus_f(gs) - softplus_f(gt));
-    const float alpha_ts = expf(0.5f * (logsigmoid_f(-gt) - logsigmoid_f(-gs)));
-    const float sigma_ts = sqrtf(sigma2);
-    const float sigma_s = sqrtf(sigmoid_host(gs)), sigma_t = sqrtf(sigmoid_host(gt));
-    coef[4 * s + 0] = alpha_ts;
-    coef[4 * s + 1] = sigma2 / alpha_ts / sigma_t;
-    coef[4 * s + 2] = sigma_ts * sigma_s / sigma_t;
-    coef[4 * s + 3] = (float)(s + 1) / (float)T;
+  for (int s = 0; s < T; ++s) coef_row(g, T, s, s + 1, &coef[4 * s]);
+}
+
+// A chain on a time grid g[0] > g[1] > ... > g[n] = 0 (gaudi_sample_grid): the per-call step table.  Row r belongs to the step
+// that LANDS on idx[r], rows ascending in time like the unit-stride table (row s lands on s), so the kernels walk it downwards
+// exactly as they walk that one; the unit grid gives that table bit for bit.
+struct GridPlan {
+  int rows = 0;
+  int t0 = 0;  // g[0]: the time index the chain starts at
+  std::vector<float> coef;     // [rows][4]
+  std::vector<int32_t> idx;    // [rows]
+};
+static const char* grid_check(int T, int n_grid, const int32_t* grid) {
+  if (n_grid < 2 || !grid) return "a time grid needs at least two entries";
+  if (grid[0] > T) return "the time grid exceeds T";
+  if (grid[n_grid - 1] != 0) return "the time grid must end in 0";
+  for (int k = 0; k + 1 < n_grid; ++k)
+    if (grid[k + 1] >= grid[k]) return "the time grid must be strictly descending";
+  return nullptr;
+}
+static void make_grid_plan(const std::vector<float>& g, int T, int n_grid, const int32_t* grid, GridPlan& gp) {
+  gp.rows = n_grid - 1;
+  gp.t0 = grid[0];
+  gp.coef.resize((size_t)gp.rows * 4);
+  gp.idx.resize(gp.rows);
+  for (int r = 0; r < gp.rows; ++r) {
+    const int k = gp.rows - 1 - r;  // step k of the chain: g[k] -> g[k + 1]
+    coef_row(g, T, grid[k + 1], grid[k], &gp.coef[4 * r]);
+    gp.idx[r] = grid[k + 1];
   }
 }
 
@@ -1619,7 +1650,7 @@ void gaudi_destroy(gaudi_handle* h) {
                     &h->d_seg, &h->d_zin, &h->d_zout, &h->d_t, &h->d_x, &h->d_h, &h->d_noise, &h->d_nan, &h->d_dpred,
                     &h->d_pred, &h->d_tw, &h->d_stash, &h->d_chain, &h->d_sx, &h->d_stype, &h->d_sn,
                     &h->d_sflags, &h->d_sdist, &h->d_sadj, &h->d_saux, &h->d_stab, &h->d_as, &h->d_ncols, &h->d_soff, &h->d_sidx,
-                    &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp};
+                    &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp, &h->d_gcoef, &h->d_gidx, &h->d_zt};
   for (DevBuf* b : bufs) b->release();
   pt_release(h);
   et_release(h);
@@ -1905,7 +1936,9 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
                      bool do_init, int s_hi, int s_lo, bool do_decode, const float* noise, int draw_base, int n_draws,
                      uint64_t seed, int64_t sample_offset, float std0, const float* target_w, float scale,
                      float* z_out, float* x_out, float* onehot_out, int* nan_count, float* chain_out = nullptr,
-                     int keep_frames = 0) {
+                     int keep_frames = 0, const GridPlan* gp = nullptr, bool seeded = false, float* zt_out = nullptr) {
+  // gp: s_hi / s_lo are rows of its table.  seeded: z_in holds the un-normalised [x | onehot] of given molecules; the first
+  // launch noises them to time index gp->t0 with raw draw 0 (the forward-noising prologue of gaudi_predict_noised) -> zt_out
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
   if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
@@ -1917,8 +1950,33 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   if (rc) return rc;
   fill_edm(h, P);
   const int D = 3 + P.F, T = P.T;
-  if (s_hi >= T || s_lo < 0) return fail(h, GAUDI_E_INVALID, "step index out of range");
+  if (s_hi >= (gp ? gp->rows : T) || s_lo < 0) return fail(h, GAUDI_E_INVALID, "step index out of range");
   const size_t zb = sizeof(float) * B * N * D;
+  if (gp) {
+    HIPCHECK(h, h->d_gcoef.reserve(sizeof(float) * gp->coef.size()));
+    HIPCHECK(h, h->d_gidx.reserve(sizeof(int32_t) * gp->idx.size()));
+    HIPCHECK(h, hipMemcpyAsync(h->d_gcoef.p, gp->coef.data(), sizeof(float) * gp->coef.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(h->d_gidx.p, gp->idx.data(), sizeof(int32_t) * gp->idx.size(), hipMemcpyHostToDevice, h->stream));
+    P.coef = h->d_gcoef.as<float>();
+    P.step_idx = h->d_gidx.as<int>();
+  }
+  std::vector<float> as_start;
+  if (seeded) {
+    const float g = h->gamma[gp->t0];  // as gaudi_predict_noised: alpha (en_diffusion.py:375-377), sigma (:370-373)
+    as_start.resize((size_t)B * 2);
+    for (int b = 0; b < B; ++b) {
+      as_start[2 * b] = sqrtf(sigmoid_host(-g));
+      as_start[2 * b + 1] = sqrtf(sigmoid_host(g));
+    }
+    HIPCHECK(h, h->d_as.reserve(sizeof(float) * 2 * B));
+    HIPCHECK(h, hipMemcpyAsync(h->d_as.p, as_start.data(), sizeof(float) * 2 * B, hipMemcpyHostToDevice, h->stream));
+    P.alpha_sigma = h->d_as.as<float>();
+    if (zt_out) {
+      HIPCHECK(h, h->d_zt.reserve(zb));
+      HIPCHECK(h, hipMemsetAsync(h->d_zt.p, 0, zb, h->stream));
+      P.zt_out = h->d_zt.as<float>();
+    }
+  }
   HIPCHECK(h, h->d_zin.reserve(zb));
   HIPCHECK(h, h->d_zout.reserve(zb));
   HIPCHECK(h, h->d_x.reserve(sizeof(float) * B * N * 3));
@@ -1980,6 +2038,8 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
       P.z_out = zout;
       rc = launch(h, P, h->HPE, 0, 1);
       if (rc) return rc;
+      P.alpha_sigma = nullptr;  // (a seeded start: the first launch has noised the given molecules)
+      P.zt_out = nullptr;
       P.mode = MODE_GUIDE;
       P.do_init = 0;
       P.split = 0;
@@ -2016,6 +2076,8 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
     P.z_out = zout;
     rc = launch(h, P, h->HPE, hpp, any_steps ? (s - lo + 1) : 0);
     if (rc) return rc;
+    P.alpha_sigma = nullptr;  // (a seeded start: the first launch has noised the given molecules)
+    P.zt_out = nullptr;
     std::swap(zin, zout);
     first = false;
     s = lo - 1;
@@ -2023,6 +2085,7 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   }
   // after the swap, `zin` holds the latest z
   if (z_out) HIPCHECK(h, hipMemcpyAsync(z_out, zin, zb, hipMemcpyDeviceToHost, h->stream));
+  if (seeded && zt_out) HIPCHECK(h, hipMemcpyAsync(zt_out, h->d_zt.p, zb, hipMemcpyDeviceToHost, h->stream));
   if (do_decode) {
     HIPCHECK(h, hipMemcpyAsync(x_out, h->d_x.p, sizeof(float) * B * N * 3, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(h, hipMemcpyAsync(onehot_out, h->d_h.p, sizeof(float) * B * N * P.F, hipMemcpyDeviceToHost, h->stream));
@@ -2044,6 +2107,23 @@ int gaudi_step(gaudi_handle* h, int B, int N, int s_idx, const float* z_t, const
   const int T = h->ecfg.diffusion_steps;
   return run_chain(h, B, N, node_mask, edge_mask, z_t, false, s_idx, s_idx, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f,
                    target_w, scale, zs_out, nullptr, nullptr, nullptr);
+}
+
+int gaudi_step_pair(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
+                    const float* edge_mask, const float* eps_raw, const float* target_w, float scale, float* zs_out) {
+  if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
+  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
+  const int T = h->ecfg.diffusion_steps;
+  if (s_idx < 0 || t_idx <= s_idx || t_idx > T) return fail(h, GAUDI_E_INVALID, "a step needs 0 <= s_idx < t_idx <= T");
+  GridPlan gp;  // the one-row table of this pair; eps_raw stands for raw draw T - s_idx, the draw of the step that lands on s_idx
+  gp.rows = 1;
+  gp.t0 = t_idx;
+  gp.coef.resize(4);
+  coef_row(h->gamma, T, s_idx, t_idx, gp.coef.data());
+  gp.idx.assign(1, s_idx);
+  return run_chain(h, B, N, node_mask, edge_mask, z_t, false, 0, 0, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f, target_w, scale,
+                   zs_out, nullptr, nullptr, nullptr, nullptr, 0, &gp);
 }
 
 int gaudi_decode(gaudi_handle* h, int B, int N, const float* z0, const float* node_mask, const float* edge_mask,
@@ -2091,9 +2171,33 @@ static int resident_node_limit(gaudi_handle* h, int N, bool guided) {
   return 0;
 }
 
-int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                 int64_t sample_offset, const float* noise, float std, const float* target_w, float scale,
-                 float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
+// The arguments a time grid adds to a chain, checked (gaudi_sample_grid and its callback forms).  A seeded start refuses
+// fix_noise: that option shares the PRIOR draw between molecules, and given molecules have no prior draw.
+static int grid_args(gaudi_handle* h, int n_grid, const int32_t* grid, const float* x0, const float* onehot0, GridPlan& gp) {
+  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  const int T = h->ecfg.diffusion_steps;
+  if (const char* why = grid_check(T, n_grid, grid)) return fail(h, GAUDI_E_INVALID, why);
+  if ((x0 != nullptr) != (onehot0 != nullptr)) return fail(h, GAUDI_E_INVALID, "a start from given molecules needs both x0 and onehot0");
+  if (!x0 && grid[0] != T) return fail(h, GAUDI_E_INVALID, "a chain from the prior must start at time index T (grid[0] == T)");
+  if (x0 && h->fix_noise) return fail(h, GAUDI_E_INVALID, "fix_noise applies to chains from the prior, not to a start from given molecules");
+  make_grid_plan(h->gamma, T, n_grid, grid, gp);
+  return GAUDI_OK;
+}
+// [x | onehot] rows of the given molecules, as the forward-noising prologue reads them
+static std::vector<float> concat_xh(int B, int N, int F, const float* x, const float* onehot) {
+  const int D = 3 + F;
+  std::vector<float> xh((size_t)B * N * D);
+  for (size_t r = 0; r < (size_t)B * N; ++r) {
+    for (int d = 0; d < 3; ++d) xh[r * D + d] = x[r * 3 + d];
+    for (int k = 0; k < F; ++k) xh[r * D + 3 + k] = onehot[r * F + k];
+  }
+  return xh;
+}
+
+static int sample_impl(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                       int64_t sample_offset, const float* noise, float std, const float* target_w, float scale,
+                       float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag, const GridPlan* gp, const float* xh0,
+                       float* zt_out) {
   if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
   if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
@@ -2101,6 +2205,7 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
   if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
   HIPCHECK(h, hipSetDevice(h->device));
   const int T = h->ecfg.diffusion_steps, F = h->ecfg.in_node_nf, D = 3 + F;
+  const int s_top = gp ? gp->rows - 1 : T - 1;  // first row of the step table the chain walks down from
   struct CallHint {
     gaudi_handle* h;
     ~CallHint() {
@@ -2146,11 +2251,12 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
     h->last_split_resident = (int)small.size();
   }
   int nanc = 0;
-  std::vector<float> nz, gm, ge, gx, gh, gz;
+  std::vector<float> nz, gm, ge, gx, gh, gz, gs, gt;
   for (const Bucket& bk : buckets) {
     const int Bb = bk.idx ? (int)bk.idx->size() : B;
     const float *nmb = node_mask, *emb = edge_mask, *nsb = noise;
-    float *xo = x_out, *ho = onehot_out, *zo = z0_out;
+    float *xo = x_out, *ho = onehot_out, *zo = z0_out, *zto = xh0 ? zt_out : nullptr;
+    const float* xhb = xh0;
     if (bk.idx) {  // gather the bucket's molecules
       gm.resize((size_t)Bb * N);
       ge.resize((size_t)Bb * N * N);
@@ -2168,6 +2274,16 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
       if (z0_out) {
         gz.assign((size_t)Bb * N * D, 0.f);
         zo = gz.data();
+      }
+      if (xh0) {
+        gs.resize((size_t)Bb * N * D);
+        for (int k = 0; k < Bb; ++k)
+          std::memcpy(&gs[(size_t)k * N * D], xh0 + (size_t)(*bk.idx)[k] * N * D, sizeof(float) * (size_t)N * D);
+        xhb = gs.data();
+        if (zto) {
+          gt.assign((size_t)Bb * N * D, 0.f);
+          zto = gt.data();
+        }
       }
     }
     h->call_narrow = bk.narrow;
@@ -2197,9 +2313,11 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
       }
       h->call_molmap = bk.idx ? bk.idx->data() + b0 : nullptr;
       int nan_sub = 0;
-      int rc = run_chain(h, nb, N, nmb + (size_t)b0 * N, emb + (size_t)b0 * N * N, nullptr, true, T - 1, 0, true, nzp, 0, T + 2, seed,
+      int rc = run_chain(h, nb, N, nmb + (size_t)b0 * N, emb + (size_t)b0 * N * N, xhb ? xhb + (size_t)b0 * N * D : nullptr, xhb == nullptr,
+                         s_top, 0, true, nzp, 0, T + 2, seed,
                          bk.idx ? sample_offset : sample_offset + b0, std, target_w, scale, zo ? zo + (size_t)b0 * N * D : nullptr,
-                         xo + (size_t)b0 * N * 3, ho + (size_t)b0 * N * F, &nan_sub);
+                         xo + (size_t)b0 * N * 3, ho + (size_t)b0 * N * F, &nan_sub, nullptr, 0, gp, xhb != nullptr,
+                         zto ? zto + (size_t)b0 * N * D : nullptr);
       h->call_molmap = nullptr;
       if (rc) return rc;
       nanc += nan_sub;
@@ -2210,10 +2328,32 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
         std::memcpy(x_out + (size_t)b * N * 3, &gx[(size_t)k * N * 3], sizeof(float) * N * 3);
         std::memcpy(onehot_out + (size_t)b * N * F, &gh[(size_t)k * N * F], sizeof(float) * N * F);
         if (z0_out) std::memcpy(z0_out + (size_t)b * N * D, &gz[(size_t)k * N * D], sizeof(float) * N * D);
+        if (zto) std::memcpy(zt_out + (size_t)b * N * D, &gt[(size_t)k * N * D], sizeof(float) * N * D);
       }
   }
   finish_sample(B, N, node_mask, x_out, nanc, diag);
   return GAUDI_OK;
+}
+
+int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                 int64_t sample_offset, const float* noise, float std, const float* target_w, float scale,
+                 float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
+  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_w, scale, x_out, onehot_out, z0_out,
+                     diag, nullptr, nullptr, nullptr);
+}
+
+int gaudi_sample_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                      int64_t sample_offset, const float* noise, float std, const float* target_w, float scale, int n_grid,
+                      const int32_t* grid, const float* x0, const float* onehot0, float* x_out, float* onehot_out, float* z0_out,
+                      float* zt_out, gaudi_diag* diag) {
+  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
+  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
+  GridPlan gp;
+  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
+  std::vector<float> xh0;
+  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
+  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_w, scale, x_out, onehot_out, z0_out,
+                     diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
 }
 
 }  // extern "C"
@@ -2222,7 +2362,7 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
 static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
                           int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad,
                           gaudi_target_cbz target_grad_z, void* user, float scale, float* x_out, float* onehot_out, float* z0_out,
-                          gaudi_diag* diag) {
+                          gaudi_diag* diag, const GridPlan* gp = nullptr, const float* xh0 = nullptr, float* zt_out = nullptr) {
   if (!h || !node_mask || !edge_mask || !x_out || !onehot_out || (!target_grad && !target_grad_z)) return GAUDI_E_INVALID;
   if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
   if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
@@ -2272,6 +2412,33 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
   P.h_out = h->d_h.as<float>();
   P.nan_count = h->d_nan.as<int>();
   P.guided = 1;
+  const int s_top = gp ? gp->rows - 1 : T - 1;  // rows of the step table (a time grid: its own table, as in run_chain)
+  const float* coef_h = gp ? gp->coef.data() : h->coef.data();
+  if (gp) {
+    HIPCHECK(h, h->d_gcoef.reserve(sizeof(float) * gp->coef.size()));
+    HIPCHECK(h, h->d_gidx.reserve(sizeof(int32_t) * gp->idx.size()));
+    HIPCHECK(h, hipMemcpyAsync(h->d_gcoef.p, gp->coef.data(), sizeof(float) * gp->coef.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(h->d_gidx.p, gp->idx.data(), sizeof(int32_t) * gp->idx.size(), hipMemcpyHostToDevice, h->stream));
+    P.coef = h->d_gcoef.as<float>();
+    P.step_idx = h->d_gidx.as<int>();
+  }
+  std::vector<float> as_start;
+  if (xh0) {  // given molecules: the first launch noises them to time index gp->t0 with raw draw 0
+    const float g = h->gamma[gp->t0];
+    as_start.resize((size_t)B * 2);
+    for (int b = 0; b < B; ++b) {
+      as_start[2 * b] = sqrtf(sigmoid_host(-g));
+      as_start[2 * b + 1] = sqrtf(sigmoid_host(g));
+    }
+    HIPCHECK(h, h->d_as.reserve(sizeof(float) * 2 * B));
+    HIPCHECK(h, hipMemcpyAsync(h->d_as.p, as_start.data(), sizeof(float) * 2 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipMemcpyAsync(h->d_zin.p, xh0, zb, hipMemcpyHostToDevice, h->stream));
+    P.alpha_sigma = h->d_as.as<float>();
+    if (zt_out) {
+      HIPCHECK(h, h->d_zt.reserve(zb));
+      P.zt_out = h->d_zt.as<float>();
+    }
+  }
   P.scale = scale;
   std::vector<float> zero_w(16, 0.f);
   rc = fill_pred(h, P, zero_w.data(), B, N);
@@ -2290,18 +2457,21 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
   const bool dbg_cb = getenv("GAUDI_DEBUG_CB") != nullptr;
   double t_enq = 0, t_wait = 0, t_user = 0;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  for (int s = T - 1; s >= 0; --s) {
+  for (int s = s_top; s >= 0; --s) {
     const double t0 = dbg_cb ? now() : 0;
+    const float t_step = gp ? coef_h[4 * s + 3] : (float)(s + 1) / (float)T;  // (the same float either way: coef_row)
     // phase A: z_t -> z_s (before guidance) and pred = predictor(z_s, t); the activation stash stays on the device
     P.mode = MODE_SAMPLE;
     P.s_hi = P.s_lo = s;
-    P.do_init = s == T - 1;
+    P.do_init = s == s_top && !xh0;
     P.do_decode = 0;
     P.split = 1;
     P.z_in = zin;
     P.z_out = zout;
     rc = launch(h, P, h->HPE, gn ? 0 : h->HPP, 1);
     if (rc) return rc;
+    P.alpha_sigma = nullptr;
+    P.zt_out = nullptr;
     if (gn) {
       P.mode = MODE_GUIDE;
       P.do_init = 0;
@@ -2320,7 +2490,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
     if (target_grad_z) {
       float* dz = h->p_dz.as<float>();
       std::memset(dz, 0, zb);
-      target_grad_z(user, B, N, D, K, h->p_z.as<float>(), pred, (float)(s + 1) / (float)T, dT, dz);
+      target_grad_z(user, B, N, D, K, h->p_z.as<float>(), pred, t_step, dT, dz);
       // energy = scale * sum_b T (en_diffusion.py:899-903); the reference asserts that the x part of the gradient is zero on
       // masked nodes (remove_mean_with_mask, utils.py:33-44): the direct term is masked here
       for (int b = 0; b < B; ++b)
@@ -2331,7 +2501,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
       HIPCHECK(h, hipMemcpyAsync(h->d_dz.p, dz, zb, hipMemcpyHostToDevice, h->stream));
       P.dz_in = h->d_dz.as<float>();
     } else {
-      target_grad(user, B, K, pred, (float)(s + 1) / (float)T, dT);
+      target_grad(user, B, K, pred, t_step, dT);
     }
     const double t3 = dbg_cb ? now() : 0;
     HIPCHECK(h, hipMemcpyAsync(h->d_dpred.p, dT, pb, hipMemcpyHostToDevice, h->stream));
@@ -2351,7 +2521,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
   }
   if (dbg_cb)
     fprintf(stderr, "[callback] per step: enqueue %.1f us, wait for pred %.1f us, caller's function %.1f us (%d steps)\n",
-            1e6 * t_enq / T, 1e6 * t_wait / T, 1e6 * t_user / T, T);
+            1e6 * t_enq / (s_top + 1), 1e6 * t_wait / (s_top + 1), 1e6 * t_user / (s_top + 1), s_top + 1);
   // decode pass
   P.mode = MODE_SAMPLE;
   P.split = 0;
@@ -2364,6 +2534,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
   rc = launch(h, P, h->HPE, gn ? 0 : h->HPP, 0);
   if (rc) return rc;
   if (z0_out) HIPCHECK(h, hipMemcpyAsync(z0_out, zout, zb, hipMemcpyDeviceToHost, h->stream));
+  if (xh0 && zt_out) HIPCHECK(h, hipMemcpyAsync(zt_out, h->d_zt.p, zb, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(h, hipMemcpyAsync(x_out, h->d_x.p, sizeof(float) * B * N * 3, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(h, hipMemcpyAsync(onehot_out, h->d_h.p, sizeof(float) * B * N * P.F, hipMemcpyDeviceToHost, h->stream));
   int nanc = 0;
@@ -2389,6 +2560,21 @@ int gaudi_sample_cbz(gaudi_handle* h, int B, int N, const float* node_mask, cons
   if (!target_grad) return GAUDI_E_INVALID;
   return sample_cb_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, nullptr, target_grad, user, scale, x_out,
                         onehot_out, z0_out, diag);
+}
+
+int gaudi_sample_cb_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                         int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad,
+                         gaudi_target_cbz target_grad_z, void* user, float scale, int n_grid, const int32_t* grid, const float* x0,
+                         const float* onehot0, float* x_out, float* onehot_out, float* z0_out, float* zt_out, gaudi_diag* diag) {
+  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
+  if ((target_grad != nullptr) == (target_grad_z != nullptr)) return fail(h, GAUDI_E_INVALID, "exactly one of the two callbacks must be set");
+  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
+  GridPlan gp;
+  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
+  std::vector<float> xh0;
+  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
+  return sample_cb_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_grad, target_grad_z, user, scale, x_out,
+                        onehot_out, z0_out, diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
 }
 
 int gaudi_sample_chain(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
@@ -2447,6 +2633,18 @@ int gaudi_host_schedule(int T, float noise_power, float noise_precision, float* 
     std::vector<float> c;
     make_coef(g, T, c);
     std::memcpy(coef_out, c.data(), sizeof(float) * c.size());
+  }
+  return GAUDI_OK;
+}
+
+int gaudi_host_grid_coefficients(int T, float noise_power, float noise_precision, int n_grid, const int32_t* grid, float* coef_out,
+                                 int32_t* land_out) {
+  if (T < 1 || !coef_out || grid_check(T, n_grid, grid)) return GAUDI_E_INVALID;
+  GridPlan gp;
+  make_grid_plan(make_gamma(T, noise_power, noise_precision), T, n_grid, grid, gp);
+  for (int k = 0; k < gp.rows; ++k) {  // step order: row k = the step g[k] -> g[k + 1]
+    std::memcpy(coef_out + 4 * k, &gp.coef[4 * (size_t)(gp.rows - 1 - k)], sizeof(float) * 4);
+    if (land_out) land_out[k] = gp.idx[gp.rows - 1 - k];
   }
   return GAUDI_OK;
 }

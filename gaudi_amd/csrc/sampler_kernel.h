@@ -48,7 +48,10 @@ struct KParams {
   int fix_noise;            // en_diffusion.py:562-566: every molecule takes the raw draws of ONE sample ...
   long long fix_key;        // ... the Philox stream of this global sample index (or row 0 of the injected buffer)
   float std0;
-  const float* coef;        // [T][4] alpha_ts, eps_coef, sigma, t
+  const float* coef;        // [rows][4] alpha_ts, eps_coef, sigma, t: row s of the handle's unit-stride table, or of a per-call
+                            // table built for a time grid (gaudi_sample_grid); s_hi / s_lo count ROWS
+  const int* step_idx;      // [rows] time index a row's step lands on (noise draw T - index, sample_chain frame), or nullptr:
+                            // the unit-stride table, where row s lands on s
   float alpha0, sigma0, sigma_x, nv0, nv1;
   int* nan_count;
   EdmDev edm;
@@ -592,9 +595,12 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
       // one EDM evaluation per pass: reverse steps s_hi..s_lo, then (optionally) the decode pass
       for (int pass = 0; pass < n_pass; ++pass) {
         const bool is_step = mode == MODE_SAMPLE && pass < n_steps;
-        const int s = s_hi - pass;
+        int s = s_hi - pass;  // row of the step table ...
         f4 cf = splat(0.f);
-        if (is_step) cf = *(const f4*)(P.coef + 4 * s);
+        if (is_step) {
+          cf = *(const f4*)(P.coef + 4 * s);
+          if (P.step_idx != nullptr) s = P.step_idx[s];  // ... and the time index it lands on (launch-uniform)
+        }
         const float t_val = mode == MODE_PHI ? P.t_in[b] : cf[3];  // decode: t = 0
         if (is_step == false && mode == MODE_SAMPLE) store_z(sZ);  // z_0 is final: publish it
         const int split = P.split;

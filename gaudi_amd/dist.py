@@ -18,8 +18,13 @@ def shard_bounds(total: int, rank: int, world: int):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def sample_sharded(sample_fn, node_mask: np.ndarray, edge_mask: np.ndarray, rank: int, world: int, engine=None):
+def sample_sharded(sample_fn, node_mask: np.ndarray, edge_mask: np.ndarray, rank: int, world: int, engine=None, grid=None,
+                   start=None):
     """Run ``sample_fn(node_mask_shard, edge_mask_shard, sample_offset) -> (x, h)`` on this rank's block.
+
+    grid / start (a chain on a time grid, from given molecules: Engine.sample) are handed to sample_fn as keyword arguments
+    when given; ``start = (x, onehot)`` describes the WHOLE batch and a rank receives its slice by global sample index.  Noise
+    is keyed by time index and global sample index on any grid, so the gathered result equals the unsharded run.
 
     node_mask [B,N(,1)], edge_mask reshapeable to [B,N,N] describe the WHOLE logical batch (already padded
     to the batch-wide N, as sampling_edm.sample_guidance does, sampling_edm.py:177).  ``engine``: the
@@ -37,7 +42,12 @@ def sample_sharded(sample_fn, node_mask: np.ndarray, edge_mask: np.ndarray, rank
         prev = getattr(engine, "_plan_hint", (0, 0))  # a hint the caller had set is restored afterwards
         engine.set_plan_hint(*engine.plan_hint_for(nm, em))
     try:
-        x, h = sample_fn(nm[lo:hi], em[lo:hi], lo)
+        kw = {}
+        if grid is not None:
+            kw["grid"] = grid
+        if start is not None:
+            kw["start"] = (np.asarray(start[0], np.float32)[lo:hi], np.asarray(start[1], np.float32)[lo:hi])
+        x, h = sample_fn(nm[lo:hi], em[lo:hi], lo, **kw)
     finally:
         if engine is not None:
             engine.set_plan_hint(*prev)

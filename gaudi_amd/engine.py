@@ -250,7 +250,8 @@ class Engine:
                                                   fptr(pred), fptr(grad)), "gaudi_predictor_grad")
         return pred, grad
 
-    def step(self, s_idx, z_t, node_mask, edge_mask, eps_raw, target_w=None, scale=1.0) -> np.ndarray:
+    def step(self, s_idx, z_t, node_mask, edge_mask, eps_raw, target_w=None, scale=1.0, t_idx=None) -> np.ndarray:
+        """One teacher-forced reverse step z_t -> z_s from time index t_idx (default s_idx + 1) down to s_idx."""
         self._sync_edm()
         self._sync_pred()
         z = f32(z_t)
@@ -259,6 +260,10 @@ class Engine:
         eps = f32(eps_raw)
         tw = None if target_w is None else f32(target_w)
         out = np.empty_like(z)
+        if t_idx is not None:
+            self._check(self.lib.gaudi_step_pair(self.h, B, N, int(s_idx), int(t_idx), fptr(z), fptr(nm), fptr(em), fptr(eps),
+                                                 fptr(tw), float(scale), fptr(out)), "gaudi_step_pair")
+            return out
         self._check(self.lib.gaudi_step(self.h, B, N, int(s_idx), fptr(z), fptr(nm), fptr(em), fptr(eps), fptr(tw),
                                         float(scale), fptr(out)), "gaudi_step")
         return out
@@ -276,8 +281,27 @@ class Engine:
         return x, h
 
     # ------------------------------------------------------------------ whole chain
+    def _grid_args(self, grid, start, B, N, return_zt):
+        """-> (n_grid, grid int32, x0, onehot0, zt) for the *_grid entry points; malformed grids are refused by the library."""
+        g = np.ascontiguousarray(np.asarray(grid).reshape(-1), dtype=np.int32)
+        x0 = oh0 = zt = None
+        if start is not None:
+            x0, oh0 = start
+            x0 = None if x0 is None else f32(x0).reshape(B, N, 3)
+            oh0 = None if oh0 is None else f32(oh0).reshape(B, N, self.F)
+            if return_zt:
+                zt = np.zeros((B, N, 3 + self.F), np.float32)
+        elif return_zt:
+            raise GaudiError("return_zt needs a start from given molecules (start=(x, onehot))")
+        return len(g), g, x0, oh0, zt
+
     def sample(self, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None, std=1.0, target_w=None, scale=1.0,
-               return_z0=False):
+               return_z0=False, grid=None, start=None, return_zt=False):
+        """Whole chain -> (x, h, diag[, z0][, zt]).  grid: strictly descending time indices T >= g[0] > ... > g[n] = 0 (None:
+        all T steps); start = (x, onehot): noise these molecules to g[0] and run the chain from there instead of from the
+        prior (needs a grid; return_zt also returns that z_{g[0]}).  See include/gaudi_hip.h: gaudi_sample_grid."""
+        if grid is None and start is not None:
+            raise GaudiError("a start from given molecules needs the time grid to run (grid[0] = the time index to noise to)")
         self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)
@@ -295,13 +319,22 @@ class Engine:
         h = np.empty((B, N, self.F), np.float32)
         z0 = np.empty((B, N, D), np.float32) if return_z0 else None
         diag = Diag()
-        self._check(self.lib.gaudi_sample(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
-                                          float(std), fptr(tw), float(scale), fptr(x), fptr(h), fptr(z0),
-                                          C.byref(diag)), "gaudi_sample")
+        zt = None
+        if grid is None:
+            self._check(self.lib.gaudi_sample(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
+                                              float(std), fptr(tw), float(scale), fptr(x), fptr(h), fptr(z0),
+                                              C.byref(diag)), "gaudi_sample")
+        else:
+            ng, g, x0, oh0, zt = self._grid_args(grid, start, B, N, return_zt)
+            self._check(self.lib.gaudi_sample_grid(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
+                                                   float(std), fptr(tw), float(scale), ng, g.ctypes.data_as(_lib.IP), fptr(x0),
+                                                   fptr(oh0), fptr(x), fptr(h), fptr(z0), fptr(zt), C.byref(diag)),
+                        "gaudi_sample_grid")
         d = dict(max_masked_leak=diag.max_masked_leak, max_cog_rel=diag.max_cog_rel, max_cog_abs=diag.max_cog_abs,
                  nan_count=diag.nan_count, reprojected=diag.reprojected,
                  edge_math_fallback=getattr(self, "_fallback_reason", None), family_split_resident=self.family_split())
-        return (x, h, d, z0) if return_z0 else (x, h, d)
+        out = (x, h, d) + ((z0,) if return_z0 else ())
+        return out + (zt,) if return_zt else out
 
     def predict_noised(self, x, onehot, t_int, node_mask, edge_mask, *, seed=0, sample_offset=0, noise=None):
         """sample_edm_t + predictor forward in one launch -> (z_t [B,N,3+F], pred [B,K])."""
@@ -435,11 +468,14 @@ class Engine:
         return loss, net, out
 
     def sample_callback(self, node_mask, edge_mask, target_grad, *, seed=0, sample_offset=0, noise=None, std=1.0,
-                        scale=1.0, return_z0=False, with_z=False):
+                        scale=1.0, return_z0=False, with_z=False, grid=None, start=None, return_zt=False):
         """Guided chain for an arbitrary target: ``target_grad(pred [B,K], t) -> dT/dpred [B,K]`` is called once per
         reverse step between the two device phases (include/gaudi_hip.h: gaudi_sample_cb).  with_z=True: the target also
         depends on z outside the predictor -- ``target_grad(z_s [B,N,D], pred [B,K], t) -> (dT/dpred [B,K], dT/dz [B,N,D])``
-        with dT/dz the DIRECT part, pred held fixed (gaudi_sample_cbz)."""
+        with dT/dz the DIRECT part, pred held fixed (gaudi_sample_cbz).  grid / start / return_zt as in sample(): the callback
+        then receives t = g[k] / T of the step it belongs to (gaudi_sample_cb_grid)."""
+        if grid is None and start is not None:
+            raise GaudiError("a start from given molecules needs the time grid to run (grid[0] = the time index to noise to)")
         self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)
@@ -484,7 +520,17 @@ class Engine:
                 if not failure:
                     failure.append(exc)
 
-        if with_z:
+        zt = None
+        what = "gaudi_sample_cbz" if with_z else "gaudi_sample_cb"
+        if grid is not None:
+            ng, g, x0, oh0, zt = self._grid_args(grid, start, B, N, return_zt)
+            cb = TARGET_CBZ(_cbz) if with_z else TARGET_CB(_cb)
+            what = "gaudi_sample_cb_grid"
+            rc = self.lib.gaudi_sample_cb_grid(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
+                                               float(std), TARGET_CB() if with_z else cb, cb if with_z else TARGET_CBZ(), None,
+                                               float(scale), ng, g.ctypes.data_as(_lib.IP), fptr(x0), fptr(oh0), fptr(x), fptr(h),
+                                               fptr(z0), fptr(zt), C.byref(diag))
+        elif with_z:
             cb = TARGET_CBZ(_cbz)
             rc = self.lib.gaudi_sample_cbz(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
                                            float(std), cb, None, float(scale), fptr(x), fptr(h), fptr(z0), C.byref(diag))
@@ -494,14 +540,16 @@ class Engine:
                                           float(std), cb, None, float(scale), fptr(x), fptr(h), fptr(z0), C.byref(diag))
         if failure:
             raise failure[0]
-        self._check(rc, "gaudi_sample_cbz" if with_z else "gaudi_sample_cb")
+        self._check(rc, what)
         d = dict(max_masked_leak=diag.max_masked_leak, max_cog_rel=diag.max_cog_rel, max_cog_abs=diag.max_cog_abs,
                  nan_count=diag.nan_count, reprojected=diag.reprojected,
                  edge_math_fallback=getattr(self, "_fallback_reason", None), family_split_resident=self.family_split())
-        return (x, h, d, z0) if return_z0 else (x, h, d)
+        out = (x, h, d) + ((z0,) if return_z0 else ())
+        return out + (zt,) if return_zt else out
 
     def sample_chain(self, node_mask, edge_mask, keep_frames, *, seed=0, sample_offset=0, noise=None, std=1.0):
-        """-> chain [keep_frames, B, N, 3+F] (frame 0 = final [x | one_hot])."""
+        """-> chain [keep_frames, B, N, 3+F] (frame 0 = final [x | one_hot]).  Unit time grid only: the reference's frame rule
+        (frame (s * keep_frames) // T) is defined on it, so this call takes no grid."""
         self._sync_edm()
         self._sync_pred()
         nm = f32(node_mask)

@@ -49,16 +49,45 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
     return stability_dict, x[ok], one_hot[ok], node_mask[ok], edge_mask.view(bs, n, n)[ok].view(-1, 1)
 
 
-def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes):
+def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
-    properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting."""
+    properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
+    steps per molecule (None: all T)."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
     start_time = time()
-    x, one_hot, node_mask, edge_mask = sample_guidance(args, model, target_function, nodesxsample, scale=scale)
+    x, one_hot, node_mask, edge_mask = sample_guidance(args, model, target_function, nodesxsample, scale=scale,
+                                                       **({} if n_steps is None else dict(n_steps=n_steps)))
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
+    return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds)
+
+
+def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
+           prop_dist=None):
+    """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
+    (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
+    of the molecules that went in, so the caller sees what the refinement bought."""
+    model.eval()
+    cond_predictor.eval()
+    bs, n_nodes = _to_numpy(x).shape[0], _to_numpy(x).shape[1]
+    nm = _to_numpy(node_mask).astype(np.float32).reshape(bs, n_nodes, 1)
+    em = _to_numpy(edge_mask).astype(np.float32).reshape(-1, 1)
+    seed_vals = _to_numpy(get_target_function_values(_like_ref(_to_numpy(x).astype(np.float32)), _like_ref(_to_numpy(one_hot).astype(np.float32)),
+                                                     target_function, nm, em, model))
+    start_time = time()
+    xr, h = model.refine(x, one_hot, nm, em, t_start, target_function=target_function, scale=scale, n_steps=n_steps)
+    seconds = time() - start_time
+    print(f"Refined {bs} molecules in {seconds:.2f} seconds")
+    out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
+                    seconds)
+    out["seed_target_function_values"] = _like_ref(seed_vals)
+    return out
+
+
+def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds):
+    """The part of design after sampling (generation_guidance.py:96-184)."""
     _check(x, node_mask)
     stability_dict, _, _, _, _ = eval_stability(x, one_hot, node_mask, edge_mask, dataset=args.dataset,
                                                 engine=model.engine)

@@ -236,9 +236,10 @@ def affine_target_weights(fn, K: int, T: int, B: int = 3):
     return ref.numpy().astype(np.float32)
 
 
-def affine_gradient_holds(fn, w, T: int) -> bool:
+def affine_gradient_holds(fn, w, T: int, grid=None) -> bool:
     """The closure that affine_target_weights recognised, held to its weight vector at EVERY t the chain passes to it --
-    (s + 1) / T as float32, s = 0 .. T-1 (gaudi_hip.hip: sample_cb_impl) -- with rows of four magnitudes per call.  A closure
+    (s + 1) / T as float32, s = 0 .. T-1 (gaudi_hip.hip: sample_cb_impl), or g[k] / T for every step of a time grid g (the
+    last entry, 0, is where the chain lands: no step starts there) -- with rows of four magnitudes per call.  A closure
     whose python control flow depends on t (a guidance window) passes the three-point probe when the probe's points fall
     outside the window; this visits them all (T small torch evaluations; GaudiModel._run overlaps them with the device call)."""
     import torch
@@ -247,8 +248,9 @@ def affine_gradient_holds(fn, w, T: int) -> bool:
     gen = torch.Generator().manual_seed(4321)
     base = torch.randn(4, K, generator=gen) * torch.tensor([[1.0], [1e-2], [30.0], [1e3]])
     try:
-        for s in range(int(T)):
-            t = float(np.float32(s + 1) / np.float32(T))
+        t_indices = range(1, int(T) + 1) if grid is None else [int(g) for g in np.asarray(grid).reshape(-1)[:-1]]
+        for t_idx in t_indices:
+            t = float(np.float32(t_idx) / np.float32(T))
             if _affine_probe(fn, base.clone().requires_grad_(True), t, ref) is None:
                 return False
     except GaudiError:
@@ -556,7 +558,10 @@ class GaudiModel:
         self.sample_offset += int(n_samples)
         return int(self.seed), off
 
-    def _run(self, n_samples, node_mask, edge_mask, std, target, scale, fix_noise):
+    def _run(self, n_samples, node_mask, edge_mask, std, target, scale, fix_noise, grid=None, start=None):
+        """grid: the time grid the chain runs on (None: all T steps, today's entry points); start = (x, onehot): given
+        molecules the chain starts from, noised to grid[0], instead of the prior."""
+        gk = {} if grid is None else dict(grid=np.ascontiguousarray(np.asarray(grid).reshape(-1), dtype=np.int32), start=start)
         nm = _to_numpy(node_mask).astype(np.float32)
         B, N = nm.shape[0], nm.shape[1]
         if B != n_samples:
@@ -581,10 +586,10 @@ class GaudiModel:
                 nm3, em_flat = nm.reshape(B, N, 1), em.reshape(B * N * N, 1)
                 x, h, diag = self.engine.sample_callback(nm.reshape(B, N), em, lambda z, p, t: target.grad(z, p, t, nm3, em_flat),
                                                          seed=seed, sample_offset=off, noise=self.injected_noise, std=std,
-                                                         scale=scale, with_z=True)
+                                                         scale=scale, with_z=True, **gk)
             elif isinstance(target, PredTarget):
                 x, h, diag = self.engine.sample_callback(nm.reshape(B, N), em, target.grad, seed=seed, sample_offset=off,
-                                                         noise=self.injected_noise, std=std, scale=scale)
+                                                         noise=self.injected_noise, std=std, scale=scale, **gk)
             else:
                 tw = None if target is None else target.weights
                 fn = getattr(target, "_closure_fn", None)
@@ -594,24 +599,24 @@ class GaudiModel:
                     # holds it to that weight vector at every t of the chain (a closure with a guidance window).
                     # NOTE for callers: the closure is evaluated on a helper thread beside the engine call (it only ever sees
                     # stand-in predictions, never the engine) -- a closure with side effects on shared state must be wrapped in
-                    # PredTarget.  The verdict is cached per (closure, T, weights): repeated calls of design() with the same
-                    # closure pay for it once.
+                    # PredTarget.  The verdict is cached per (closure, T, weights, time grid): repeated calls of design() with the
+                    # same closure pay for it once; another grid visits other t and is checked on its own.
                     import threading
-                    key = (id(fn), int(self.T), tw.tobytes())
+                    key = (id(fn), int(self.T), tw.tobytes(), None if grid is None else gk["grid"].tobytes())
                     cache = self.__dict__.setdefault("_affine_verdicts", {})
                     if key in cache and cache[key][0] is fn:
                         holds[0] = cache[key][1]
                     else:
                         def _check_all_t():
                             try:
-                                holds[0] = affine_gradient_holds(fn, tw, self.T)
+                                holds[0] = affine_gradient_holds(fn, tw, self.T, gk.get("grid"))
                             except BaseException:
                                 holds[0] = False
                         checker = threading.Thread(target=_check_all_t, daemon=True)
                         checker.start()
                 try:
                     out = self.engine.sample(nm.reshape(B, N), em, seed=seed, sample_offset=off, noise=self.injected_noise, std=std,
-                                             target_w=tw, scale=scale, return_z0=fn is not None)
+                                             target_w=tw, scale=scale, return_z0=fn is not None, **gk)
                 finally:
                     if checker is not None:  # (joined whether or not the engine call raised)
                         checker.join()
@@ -624,12 +629,13 @@ class GaudiModel:
                     # runs through the general path, which differentiates the closure at every step
                     pt = PredTarget(target.cond_predictor, fn, name=target.name + " -> callback")
                     x, h, diag = self.engine.sample_callback(nm.reshape(B, N), em, pt.grad, seed=seed, sample_offset=off,
-                                                             noise=self.injected_noise, std=std, scale=scale)
+                                                             noise=self.injected_noise, std=std, scale=scale, **gk)
                     diag = dict(diag, affine_recheck_failed=1)
                 elif fn is not None:
                     # ... and at the predictions the chain actually ended on
                     import torch
-                    t_last = 1.0 / self.T
+                    # (the t of the last step: 1 / T on the unit grid, g[n-1] / T on a time grid)
+                    t_last = 1.0 / self.T if grid is None else float(np.float32(gk["grid"][-2]) / np.float32(self.T))
                     p0 = torch.from_numpy(self.engine.predictor_fwd(out[3], t_last, nm.reshape(B, N), em)).requires_grad_(True)
                     with torch.enable_grad():
                         (g0,) = torch.autograd.grad(fn(p0, t_last).sum(), p0, allow_unused=True)
@@ -643,11 +649,12 @@ class GaudiModel:
         F = h.shape[2]
         return _like_ref(x), {"categorical": _like_ref(h), "integer": _like_ref(np.zeros((B, N, 0), np.float32))}
 
-    def sample(self, n_samples, n_nodes, node_mask, edge_mask, context=None, fix_noise=False, std=1.0):
-        """EnVariationalDiffusion.sample (en_diffusion.py:958-1008)."""
+    def sample(self, n_samples, n_nodes, node_mask, edge_mask, context=None, fix_noise=False, std=1.0, grid=None):
+        """EnVariationalDiffusion.sample (en_diffusion.py:958-1008); grid: a time grid (sampling_edm.time_grid) to run the
+        chain on instead of all T steps."""
         if context is not None:
             raise GaudiError("context conditioning is not part of the GaUDI sampling path")
-        return self._run(n_samples, node_mask, edge_mask, std, None, 1.0, fix_noise)
+        return self._run(n_samples, node_mask, edge_mask, std, None, 1.0, fix_noise, grid=grid)
 
     def sample_chain(self, n_samples, n_nodes, node_mask, edge_mask, context, keep_frames=None, std=1.0):
         """EnVariationalDiffusion.sample_chain (en_diffusion.py:1118-1174) -> chain_flat [keep_frames*n_samples, N, 3+F]."""
@@ -662,9 +669,29 @@ class GaudiModel:
                                          seed=seed, sample_offset=off, noise=self.injected_noise, std=std)
         return _like_ref(chain.reshape(K * B, N, chain.shape[-1]))
 
-    def sample_guidance(self, n_samples, target_function, node_mask, edge_mask, scale=1, fix_noise=False, std=1.0):
-        """EnVariationalDiffusion.sample_guidance (en_diffusion.py:1010-1067)."""
-        return self._run(n_samples, node_mask, edge_mask, std, target_function, scale, fix_noise)
+    def sample_guidance(self, n_samples, target_function, node_mask, edge_mask, scale=1, fix_noise=False, std=1.0, grid=None):
+        """EnVariationalDiffusion.sample_guidance (en_diffusion.py:1010-1067); grid as in sample()."""
+        return self._run(n_samples, node_mask, edge_mask, std, target_function, scale, fix_noise, grid=grid)
+
+    def refine(self, x, h, node_mask, edge_mask, t_start, target_function=None, scale=1, n_steps=None):
+        """Start from given molecules instead of the prior: remove the masked mean of x, noise (x, h) to time index t_start
+        as sample_edm_t does (cond_prediction/train_cond_predictor.py:47-61; it has no std), then run the reverse process
+        -- guided when target_function is given -- from there down to 0 in n_steps steps (default: all t_start).  Costs
+        t_start / T of a full chain.  h: the one-hot features [B,N,F] or the reference's dict.  Returns what sample_guidance
+        returns."""
+        from .sampling_edm import time_grid
+        xn = _to_numpy(x).astype(np.float32)
+        B, N = xn.shape[0], xn.shape[1]
+        nm = _to_numpy(node_mask).astype(np.float32).reshape(B, N)
+        hc = _to_numpy(h["categorical"] if isinstance(h, dict) else h).astype(np.float32).reshape(B, N, self.in_node_nf)
+        # as the reference's training loops prepare a batch (train_cond_predictor.py:64-71): centre, then check the masking
+        xn = xn * nm[:, :, None]
+        xn = xn - (xn.sum(1, keepdims=True) / np.maximum(nm.sum(1), 1.0)[:, None, None]) * nm[:, :, None]
+        assert_correctly_masked(hc, nm)
+        assert_mean_zero_with_mask(xn, nm)
+        t_start = int(t_start)
+        grid = time_grid(self.T, t_start if n_steps is None else int(n_steps), t_start)
+        return self._run(B, nm.reshape(B, N, 1), edge_mask, 1.0, target_function, scale, False, grid=grid, start=(xn, hc))
 
 
 def assert_correctly_masked(variable, node_mask):

@@ -49,21 +49,42 @@ def _check(x, node_mask):
     assert rel < 1e-2, f"Mean is not zero, relative_error {rel}"
 
 
-def sample_pos_edm(args, model, nodesxsample, std=0.7):
-    """sampling_edm.py:128-169: unconditional molecules, padded to args.max_nodes."""
+def time_grid(T: int, n_steps: int, t_start=None) -> np.ndarray:
+    """The time grid of a chain of n_steps reverse steps: n_steps + 1 strictly descending time indices from t_start (default
+    T, the prior) down to 0, t_start * (n_steps - k) / n_steps rounded to the nearest integer (halves up).  time_grid(T, T) is the unit grid T, T-1, ..., 0 of
+    the reference's own loops."""
+    T, n_steps = int(T), int(n_steps)
+    t_start = T if t_start is None else int(t_start)
+    if not 1 <= t_start <= T:
+        raise GaudiError(f"t_start must be in 1..T = 1..{T}, got {t_start}")
+    if not 1 <= n_steps <= t_start:
+        raise GaudiError(f"n_steps must be in 1..t_start = 1..{t_start}, got {n_steps} (a finer grid would repeat a time index)")
+    # integer round-half-up of t_start * (n_steps - k) / n_steps: exact, no float rounding of the product
+    k = np.arange(n_steps + 1, dtype=np.int64)
+    return ((2 * t_start * (n_steps - k) + n_steps) // (2 * n_steps)).astype(np.int32)
+
+
+def _grid(model, n_steps):
+    return None if n_steps is None else time_grid(model.T, n_steps)
+
+
+def sample_pos_edm(args, model, nodesxsample, std=0.7, n_steps=None):
+    """sampling_edm.py:128-169: unconditional molecules, padded to args.max_nodes.  n_steps: reverse steps to spend per
+    molecule (None: all T)."""
     n = np.asarray(_to_numpy(nodesxsample)).astype(np.int64)
     max_nodes = int(args.max_nodes)
     assert int(n.max()) <= max_nodes
     nm, em, N = build_masks(n, max_nodes, args.dataset != "cata")
-    x, h = model.sample(len(n), N, nm, em, std=std)
+    x, h = model.sample(len(n), N, nm, em, std=std, **({} if n_steps is None else dict(grid=_grid(model, n_steps))))
     _check(x, nm)
     return x, h["categorical"], _like_ref(nm), _like_ref(em)
 
 
-def sample_guidance(args, model, target_function, nodesxsample, scale=1, std=1.0):
-    """sampling_edm.py:172-224: guided molecules, padded to the batch maximum."""
+def sample_guidance(args, model, target_function, nodesxsample, scale=1, std=1.0, n_steps=None):
+    """sampling_edm.py:172-224: guided molecules, padded to the batch maximum.  n_steps as in sample_pos_edm."""
     n = np.asarray(_to_numpy(nodesxsample)).astype(np.int64)
     nm, em, N = build_masks(n, int(n.max()), args.dataset != "cata")
-    x, h = model.sample_guidance(len(n), target_function, nm, em, scale, fix_noise=False, std=std)
+    x, h = model.sample_guidance(len(n), target_function, nm, em, scale, fix_noise=False, std=std,
+                                 **({} if n_steps is None else dict(grid=_grid(model, n_steps))))
     _check(x, nm)
     return x, h["categorical"], _like_ref(nm), _like_ref(em)

@@ -203,6 +203,46 @@ int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const fl
                  float scale, float* x_out /* [B,N,3] */, float* onehot_out /* [B,N,F] */,
                  float* z0_out /* [B,N,3+F] or NULL */, gaudi_diag* diag /* or NULL */);
 
+/* ---- Chains on a chosen time grid, from the prior or from given molecules. ----
+ * A grid is n_grid >= 2 strictly descending time indices g[0] > g[1] > ... > g[n_grid-1] = 0 with g[0] <= T.  Step k moves z
+ * from g[k] to g[k+1] with the reference's own formulas for that pair -- sample_p_zs_given_zt(s, t) and
+ * sample_p_zs_given_zt_guidance(s, t) take any s < t (en_diffusion.py:807-935); only the reference's loops fix t = s + 1 --
+ * and the networks (and a callback) see t = g[k] / T.  After the last step the usual decode p(x, h | z_0) runs.
+ *
+ * Start: x0 == onehot0 == NULL -> the prior z_T ~ N(0, std), legal only with g[0] == T.  Otherwise both are given
+ * (x0 [B,N,3] mean-free over live nodes, onehot0 [B,N,F], un-normalised as gaudi_predict_noised takes them) and the chain
+ * starts from  z_{g[0]} = alpha * normalize([x0 | onehot0]) + sigma * eps  (sample_edm_t, train_cond_predictor.py:47-61),
+ * computed by the first launch exactly as gaudi_predict_noised computes its z_t; zt_out [B,N,3+F] (or NULL) receives it.
+ * `std` scales the prior draw only.
+ *
+ * Noise is keyed by TIME INDEX, not by step count: draw 0 is the start (the prior draw, or eps of the forward noising), the
+ * step that lands on time index s takes draw T - s, the decode draw T + 1.  An injected buffer keeps the layout
+ * [T+2,B,N,3+F] and a coarse grid reads a subset of its rows; the Philox keys (global sample index, node, draw) are those of
+ * gaudi_sample.  So the unit grid T, T-1, ..., 0 reproduces gaudi_sample bit for bit, and a molecule's result does not
+ * depend on sharding or packing on any grid.
+ *
+ * GAUDI_E_INVALID (with gaudi_last_error) for: fewer than two entries, not strictly descending, last entry != 0, g[0] > T,
+ * a prior start with g[0] != T, only one of x0 / onehot0, a start from given molecules while fix_noise is set.
+ * gaudi_sample_chain takes no grid: its frame rule is defined on the unit grid only. */
+int gaudi_sample_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                      int64_t sample_offset, const float* noise, float std, const float* target_w /* [K] or NULL */, float scale,
+                      int n_grid, const int32_t* grid, const float* x0 /* or NULL */, const float* onehot0 /* or NULL */,
+                      float* x_out, float* onehot_out, float* z0_out /* or NULL */, float* zt_out /* or NULL */,
+                      gaudi_diag* diag /* or NULL */);
+
+/* One teacher-forced step z_t -> z_s for ANY pair 0 <= s_idx < t_idx <= T (gaudi_step is t_idx = s_idx + 1, bit for bit).
+ * eps_raw stands for raw draw T - s_idx. */
+int gaudi_step_pair(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
+                    const float* edge_mask, const float* eps_raw, const float* target_w /* [K] or NULL */, float scale,
+                    float* zs_out);
+
+/* The step table of a grid, as the chains above build it per call: coef_out [n_grid-1][4], row k = (alpha_t|s,
+ * sigma2_t|s / alpha_t|s / sigma_t, sigma, t) of step g[k] -> g[k+1]; land_out [n_grid-1] (or NULL) the time index each
+ * step lands on.  Same float operations as gaudi_host_schedule's [T][4] table: on the unit grid row k equals that table's
+ * row T-1-k bit for bit.  Needs no device.  GAUDI_E_INVALID for a malformed grid. */
+int gaudi_host_grid_coefficients(int T, float noise_power /* 0 = cosine */, float noise_precision, int n_grid,
+                                 const int32_t* grid, float* coef_out, int32_t* land_out);
+
 /* sample_guidance for an ARBITRARY differentiable target T(pred, t) (the reference accepts any closure over the
  * predictor, generation_guidance.py:187-205).  Each reverse step runs in two launches: (A) denoise + predictor forward,
  * (B) predictor reverse pass + guidance update; in between, target_grad receives pred [B,K] and t and must write
@@ -226,6 +266,14 @@ typedef void (*gaudi_target_cbz)(void* user, int B, int N, int D, int K, const f
 int gaudi_sample_cbz(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
                      int64_t sample_offset, const float* noise, float std, gaudi_target_cbz target_grad, void* user,
                      float scale, float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag);
+
+/* gaudi_sample_cb / gaudi_sample_cbz on a time grid (see gaudi_sample_grid for the grid, the start and the noise keying):
+ * exactly one of target_grad / target_grad_z is set; the callback receives t = g[k] / T. */
+int gaudi_sample_cb_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                         int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad,
+                         gaudi_target_cbz target_grad_z, void* user, float scale, int n_grid, const int32_t* grid,
+                         const float* x0, const float* onehot0, float* x_out, float* onehot_out, float* z0_out, float* zt_out,
+                         gaudi_diag* diag);
 
 /* EnVariationalDiffusion.sample_chain (en_diffusion.py:1118-1174): the unguided chain with `keep_frames`
  * intermediate states: chain_out [keep_frames,B,N,3+F], frame (s*keep_frames)//T = unnormalize_z(z_s) of the last

@@ -1589,6 +1589,171 @@ def g27_edm_train():
     save("g27_edm_train", **out)
 
 
+G28_PAIRS = [(1000, 998), (1000, 990), (1000, 950), (500, 498), (500, 490), (500, 450), (2, 0), (10, 0), (50, 0), (1000, 0)]
+
+
+def _spread(a32, a64):
+    return np.float64(np.abs(a32.astype(np.float64) - a64).max() / max(np.abs(a64).max(), 1e-30))
+
+
+def _g28_time_grid(t_start, n_steps):
+    """gaudi_amd.sampling_edm.time_grid, restated so the fixture does not depend on the code under test."""
+    return [int((2 * t_start * (n_steps - k) + n_steps) // (2 * n_steps)) for k in range(n_steps + 1)]
+
+
+def _g28_chain(model, T, grid, z, tnm, tem, noise, dt, tf=None, scale=0.0):
+    """The reference's sample / sample_guidance loop (en_diffusion.py:982-1067) over the pairs of a time grid instead of
+    t = s + 1: its own sample_p_zs_given_zt[_guidance](s, t), then sample_p_xh_given_z0 and the CoG re-projection.  noise
+    [T+2,B,N,D] is keyed by time index: the step that lands on s draws row T - s, the decode row T + 1."""
+    B = z.shape[0]
+    eps = [noise[T - s] for s in grid[1:]] + [noise[T + 1]]
+    with InjectNoise(eps, dt), torch.no_grad():
+        for t_i, s_i in zip(grid[:-1], grid[1:]):
+            st = (torch.full((B, 1), s_i) / T).to(dt)
+            tt = (torch.full((B, 1), t_i) / T).to(dt)
+            if tf is None:
+                z = model.sample_p_zs_given_zt(st, tt, z, tnm, tem, None)
+            else:
+                z = model.sample_p_zs_given_zt_guidance(st, tt, z, tnm, tem, tf, scale)
+        x, h = model.sample_p_xh_given_z0(z, tnm, tem, None)
+        if torch.sum(x, dim=1, keepdim=True).abs().max().item() > 5e-2:
+            x = x - x.sum(1, keepdim=True) / tnm.sum(1, keepdim=True) * tnm  # remove_mean_with_mask (utils.py:33-44)
+    return x.numpy(), h["categorical"].numpy().astype(np.float32)
+
+
+def g28_grid():
+    """Chains on a time grid (gaudi_sample_grid): the reference's step functions take ANY pair s < t (en_diffusion.py:807-935);
+    only its loops fix t = s + 1.  g28_grid_steps: the scalars of G28_PAIRS for both schedules, and teacher-forced unguided /
+    guided steps for those pairs (tiny cata and hetro widths, default widths).  g28_grid_chains: T = 50 chains on
+    time_grid(50, 10) and time_grid(50, 7) from the prior, and refinement chains from given molecules noised to t_start = 20
+    by sample_edm_t, in 20 and 5 steps.  Every output is computed by the fp32 reference and by the reference in float64;
+    *_spread is the max-norm distance of the two.  (Chain noise seeds 2875..: with 2870.. the reference's own spread of ONE
+    non-amplified guided chain on the uneven grid was 1.3e-4 -- a chain that close to a branch of its own says nothing about
+    a port; milder inputs instead of a wider bound.)"""
+    from cond_prediction.train_cond_predictor import sample_edm_t
+    out = {}
+    T = 1000
+    out["pairs"] = np.array(G28_PAIRS, np.int32)
+    for sched, over in (("polynomial_2", {}), ("cosine", dict(diffusion_noise_schedule="cosine", normalize_factors=[1, 2, 2]))):
+        sd = synth.synth_edm_state_dict(synth.edm_args(nf=8, n_layers=1), 1, seed=0)
+        a, model = build_ref_edm("cata", sd, nf=8, n_layers=1, diffusion_steps=T, **over)
+        rows = []
+        for t_i, s_i in G28_PAIRS:
+            st, tt = torch.full((1, 1), s_i) / T, torch.full((1, 1), t_i) / T
+            gs, gt = model.gamma(st), model.gamma(tt)
+            zt = torch.zeros(1, 1, 1)
+            s2, s_ts, a_ts = model.sigma_and_alpha_t_given_s(gt, gs, zt)
+            sig_s, sig_t = model.sigma(gs, zt), model.sigma(gt, zt)
+            rows.append([t_i, s_i, a_ts.item(), (s2 / a_ts / sig_t).item(), (s_ts * sig_s / sig_t).item(), tt.item()])
+        out[f"coef_{sched}"] = np.array(rows, dtype=np.float64)  # t, s, alpha_t|s, sigma2_t|s / alpha_t|s / sigma_t, sigma, t / T
+    cases = [("cata", "cata", [4, 11, 7, 11], TINY, TINY_P, True), ("hetro", "hetro", [3, 9, 6], TINY, TINY_P, True),
+             ("cata_full", "cata", [11, 8], dict(nf=192, n_layers=9), dict(nf=196, n_layers=12), False)]
+    for ci, (name, ds, nodes, eo, po, amp) in enumerate(cases):
+        F = synth.num_node_features(ds)
+        esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **eo), F, seed=2800 + ci, amplify_coord=amp)
+        a, model = build_ref_edm(ds, esd, **eo)
+        psd = synth.synth_predictor_state_dict(synth.pred_args(dataset=ds, **po), F, 5, seed=2810 + ci, amplify_coord=amp)
+        pa, pred = build_ref_pred(ds, psd, **po)
+        nm, em, z = case_inputs(ds, nodes, None, seed=2820 + ci, guidance_pad=True)
+        B, N, D = z.shape
+
+        def tf_gap(_in, _nm, _em, _t):
+            return -pred(_in, _nm, _em, _t)[:, 1]
+
+        out[f"{name}_z"], out[f"{name}_node_mask"], out[f"{name}_edge_mask"] = z, nm, em
+        out[f"{name}_cfg"] = np.array(json.dumps(dict(dataset=ds, eseed=2800 + ci, pseed=2810 + ci, T=T, amp=amp, eover=eo, pover=po)))
+        res = {}
+        for dt, tag in ((torch.float32, "fp32"), (torch.float64, "fp64")):
+            if dt == torch.float64:
+                model.double()
+                pred.double()
+            tnm, tem, tz = torch.from_numpy(nm).to(dt), torch.from_numpy(em).to(dt), torch.from_numpy(z).to(dt)
+            for t_i, s_i in G28_PAIRS:
+                eps = rng_noise(2830 + 10 * ci + s_i % 7, (B, N, D))
+                st, tt = (torch.full((B, 1), s_i) / T).to(dt), (torch.full((B, 1), t_i) / T).to(dt)
+                with InjectNoise([eps], dt), torch.no_grad():
+                    res[(tag, t_i, s_i, "unguided")] = model.sample_p_zs_given_zt(st, tt, tz, tnm, tem, None).numpy()
+                for scale in (0.6, 400.0):
+                    with InjectNoise([eps], dt), torch.no_grad():
+                        res[(tag, t_i, s_i, f"guided_scale{scale}")] = model.sample_p_zs_given_zt_guidance(
+                            st, tt, tz, tnm, tem, tf_gap, scale).numpy()
+                out[f"{name}_t{t_i}_s{s_i}_eps"] = eps
+        for (tag, t_i, s_i, kind), v in res.items():
+            if tag == "fp32":
+                out[f"{name}_t{t_i}_s{s_i}_zs_{kind}"] = v
+                out[f"{name}_t{t_i}_s{s_i}_zs_{kind}_spread"] = _spread(v, res[("fp64", t_i, s_i, kind)])
+        worst = max(float(v) for k, v in out.items() if k.startswith(name) and k.endswith("_spread"))
+        over_bar = [k for k, v in out.items() if k.startswith(name) and k.endswith("_spread") and float(v) >= 5e-5]
+        print(f"g28 steps {name}: worst fp32-vs-fp64 spread {worst:.2e}; at or above 5e-5: {over_bar}")
+    save("g28_grid_steps", **out)
+
+    out = {}
+    T = 50
+    for ci, (name, ds, nodes, amp) in enumerate([("cata_tiny", "cata", [6, 8, 8, 3], False), ("hetro_tiny", "hetro", [3, 5, 4], False),
+                                                 ("cata_tiny_amp", "cata", [6, 8, 8, 3], True)]):
+        F = synth.num_node_features(ds)
+        over = dict(diffusion_steps=T, **TINY)
+        esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=2850 + ci, amplify_coord=amp)
+        a, model = build_ref_edm(ds, esd, **over)
+        psd = synth.synth_predictor_state_dict(synth.pred_args(dataset=ds, **TINY_P), F, 5, seed=2860 + ci, amplify_coord=amp)
+        pa, pred = build_ref_pred(ds, psd, **TINY_P)
+
+        def tf_gap(_in, _nm, _em, _t):
+            return -pred(_in, _nm, _em, _t)[:, 1]
+
+        nm, em = masks(ds, nodes, None)
+        B, N = nm.shape[0], nm.shape[1]
+        D = 3 + F
+        noise = rng_noise(2875 + ci, (T + 2, B, N, D))
+        # given molecules for the refinement: masked, mean-free coordinates of a few Angstrom and a ring type per node
+        rng = np.random.default_rng(2880 + ci)
+        x0 = (rng.standard_normal((B, N, 3)) * 2.5).astype(np.float32) * nm
+        x0 = (x0 - x0.sum(1, keepdims=True) / np.maximum(nm.sum(1, keepdims=True), 1) * nm).astype(np.float32)
+        oh0 = np.zeros((B, N, F), np.float32)
+        np.put_along_axis(oh0, rng.integers(0, F, (B, N, 1)), 1.0, axis=2)
+        oh0 *= nm
+        out[f"{name}_noise"], out[f"{name}_node_mask"], out[f"{name}_edge_mask"] = noise, nm, em
+        out[f"{name}_x0"], out[f"{name}_onehot0"] = x0, oh0
+        out[f"{name}_cfg"] = np.array(json.dumps(dict(dataset=ds, T=T, eseed=2850 + ci, pseed=2860 + ci, nodes=nodes, amp=amp,
+                                                      std_unguided=0.7, std_guided=1.0, scale=0.6, t_start=20)))
+        res = {}
+        for dt, tag in ((torch.float32, "fp32"), (torch.float64, "fp64")):
+            if dt == torch.float64:
+                model.double()
+                pred.double()
+            tnm, tem = torch.from_numpy(nm).to(dt), torch.from_numpy(em).to(dt)
+            for n_steps in (10, 7):
+                grid = _g28_time_grid(T, n_steps)
+                out[f"{name}_grid{n_steps}"] = np.array(grid, np.int32)
+                for kind, std, tf, scale in (("unguided", 0.7, None, 0.0), ("guided", 1.0, tf_gap, 0.6)):
+                    with InjectNoise([noise[0]], dt):
+                        zT = model.sample_combined_position_feature_noise(B, N, tnm, std)
+                    res[(tag, f"prior{n_steps}_{kind}")] = _g28_chain(model, T, grid, zT, tnm, tem, noise, dt, tf, scale)
+            with InjectNoise([noise[0]], dt), torch.no_grad():
+                tt = (torch.full((B, 1), 20) / T).to(dt)
+                zt = sample_edm_t(torch.from_numpy(x0).to(dt), torch.from_numpy(oh0).to(dt), model, tt, tnm)
+            res[(tag, "zt20")] = (zt.numpy(),)
+            for n_steps in (20, 5):
+                grid = _g28_time_grid(20, n_steps)
+                out[f"{name}_refine_grid{n_steps}"] = np.array(grid, np.int32)
+                for kind, tf, scale in (("unguided", None, 0.0), ("guided", tf_gap, 0.6)):
+                    res[(tag, f"refine{n_steps}_{kind}")] = _g28_chain(model, T, grid, zt, tnm, tem, noise, dt, tf, scale)
+        for (tag, key), v in res.items():
+            if tag != "fp32":
+                continue
+            v64 = res[("fp64", key)]
+            if key == "zt20":
+                out[f"{name}_zt20"], out[f"{name}_zt20_spread"] = v[0], _spread(v[0], v64[0])
+                continue
+            out[f"{name}_{key}_x"], out[f"{name}_{key}_h"] = v
+            out[f"{name}_{key}_x_spread"] = _spread(v[0], v64[0])
+            out[f"{name}_{key}_h_equal_fp64"] = np.array(np.array_equal(v[1], v64[1]))
+        for k, v in out.items():
+            if k.startswith(name + "_") and k.endswith("_spread"):
+                print(f"g28 chains {k}: {float(v):.2e}")
+    save("g28_grid_chains", **out)
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1614,7 +1779,7 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid)
     which = sys.argv[1:] or list(fns)
     for w in which:
         fns[w]()
