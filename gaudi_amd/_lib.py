@@ -47,6 +47,15 @@ class StabilityAux(C.Structure):
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
+
+
+class TargetSpec(C.Structure):
+    """include/gaudi_hip.h: gaudi_target_spec."""
+    _fields_ = [("K", C.c_int32), ("w", FP), ("q", FP), ("c", FP), ("side", IP), ("scale", FP),
+                ("w_per_mol", C.c_int32), ("q_per_mol", C.c_int32), ("c_per_mol", C.c_int32), ("side_per_mol", C.c_int32),
+                ("scale_per_mol", C.c_int32), ("t_lo", C.c_int32), ("t_hi", C.c_int32)]
+
+
 # gaudi_target_cb(user, B, K, pred, t, dT_dpred_out)
 TARGET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, FP, C.c_float, FP)
 # gaudi_target_cbz(user, B, N, D, K, z_s, pred, t, dT_dpred_out, dT_dz_out)
@@ -131,6 +140,10 @@ EXPORTS = {
     "gaudi_sample_cb_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, C.c_uint64, C.c_int64, FP, C.c_float, TARGET_CB,
                                        TARGET_CBZ, C.c_void_p, C.c_float, C.c_int, IP, FP, FP, FP, FP, FP, FP, C.POINTER(Diag)]),
     "gaudi_host_grid_coefficients": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_int, IP, FP, IP]),
+    "gaudi_sample_target": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, C.c_uint64, C.c_int64, FP, C.c_float,
+                                      C.POINTER(TargetSpec), C.c_int, IP, FP, FP, FP, FP, FP, FP, FP, C.POINTER(Diag)]),
+    "gaudi_step_target": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, FP, FP, FP, FP, C.POINTER(TargetSpec), FP, FP]),
+    "gaudi_host_target_seed": (C.c_int, [C.POINTER(TargetSpec), C.c_int, C.c_int, FP, FP]),
 }
 
 ABI_VERSION = 7  # include/gaudi_hip.h: GAUDI_ABI_VERSION
@@ -139,6 +152,7 @@ _NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_g
                 "gaudi_edm_grad_size", "gaudi_edm_set_train_weights")  # ... and the NLL / training entry
 # points (same ABI version: no existing signature changed)
 _GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")  # ... and the time-grid chains
+_TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fused value targets
 
 _lib = None
 
@@ -166,7 +180,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory

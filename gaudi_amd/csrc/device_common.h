@@ -801,4 +801,23 @@ __device__ inline f4 philox_normal4(uint64_t seed, uint64_t sample, uint32_t dra
   return (f4){ra * ca, ra * sa, rb * cb, rb * sb};
 }
 
+// ---------------------------------------------------------------------------------------------
+// Value targets (gaudi_sample_target): T(p) = sum_k w[k] p[k] + q[k] a(p[k] - c[k], side[k])^2 with a(d, 0) = d,
+// a(d, +1) = max(d, 0) (upper bound), a(d, -1) = min(d, 0) (lower bound; a NaN d gives 0 on both hinges).
+// One molecule's parameters are a row of 4 K + 1 floats: w [K] | q [K] | c [K] | side [K] | scale.
+// Seed of the reverse pass, d(scale * T)/dp[k] = (w + (q + q) * a) * scale: every operation rounded on its own, in this order
+// (no contraction), so the kernels, gaudi_host_target_seed and a numpy float32 expression agree bit for bit.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int target_row_floats(int K) { return 4 * K + 1; }
+__host__ __device__ inline float target_seed(const float* row, int K, int k, float p) {
+#pragma clang fp contract(off)
+  const float w = row[k], q = row[K + k], c = row[2 * K + k], side = row[3 * K + k], scale = row[4 * K];
+  const float d = p - c;
+  const float a = side == 0.f ? d : (side > 0.f ? (d > 0.f ? d : 0.f) : (d < 0.f ? d : 0.f));
+  const float q2 = q + q;
+  const float qa = q2 * a;
+  const float g = w + qa;
+  return g * scale;
+}
+
 }  // namespace gaudi

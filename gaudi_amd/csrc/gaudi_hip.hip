@@ -85,6 +85,15 @@ struct gaudi_handle {
   DevBuf d_mask, d_order, d_edges, d_emask, d_npairs, d_seg, d_zin, d_zout, d_t, d_x, d_h, d_noise, d_nan, d_dpred,
       d_pred, d_tw, d_stash, d_chain, d_sx, d_stype, d_sn, d_sflags, d_sdist, d_sadj, d_saux, d_stab, d_as, d_ncols, d_soff,
       d_sidx, d_gnode, d_rowmap, d_compmol, d_ncomp, d_clock, d_gcoef, d_gidx, d_zt;  // d_gcoef / d_gidx / d_zt: time-grid chains
+  DevBuf d_vtpar, d_vttrace, d_vtdev;  // value targets: per-molecule parameter rows, the guidance trace, the VtDev that names them
+  // Value-target call in flight (gaudi_sample_target / gaudi_step_target set it around sample_impl / run_chain; nullptr otherwise):
+  // run_chain stages the parameter rows of ITS molecules (request index = b0 + k), the window flags and the trace, and keeps
+  // every molecule alone in its workgroup.
+  struct VtCall {
+    const gaudi_target_spec* spec = nullptr;
+    int K = 0, Btot = 0, b0 = 0;
+    float* trace = nullptr;  // host [rows][Btot][K + 2], zero-filled by the entry point, or nullptr
+  }* vt = nullptr;
   PinBuf p_pred, p_dpred;     // gaudi_sample_cb: pred [B,K] device -> host, dT/dpred [B,K] host -> device, once per step
   PinBuf p_z, p_dz;           // gaudi_sample_cbz: z_s [B,N,D] device -> host, scale * dT/dz host -> device
   DevBuf d_dz;
@@ -1039,15 +1048,17 @@ static size_t lds_bytes8(int hpe, int hpp, int N, int D, int S, int pubx, int sp
   return sizeof(float) * (lds_floats8_base(hpe, hpp, N, D, S, split, gn) + (hpp ? pubx : 0));
 }
 
-static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long steps) {
+static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp_, long long steps) {
   const bool v8 = h->run_variant == 8;
+  // a value-target launch (KParams::vt) runs the VT instantiation of its kernel; every other launch the one it always ran
+  const int hpp = hpp_, hpp_k = P.vt != nullptr && hpp_ ? (hpp_ | kVtKernel) : hpp_;
   const bool se = hpe && h->ecfg.sin_embedding;  // stage_graph keeps such a call on the 4-wave family
-  kernel_fn fn = v8   ? (h->run_pg && hpe && hpp ? pick_kernel8mp(hpe, hpp) : h->run_gn8 == 2 ? pick_kernel8gp(hpe, hpp) : h->run_gn8 ? pick_kernel8g(hpe, hpp) : pick_kernel8_mode(hpe, hpp, h->run_split, h->run_mr && hpp))
-                 : se ? pick_kernel_se(hpe, hpp, h->run_gn)
-                      : h->run_gn ? pick_kernel_g(hpe, hpp) : pick_kernel(hpe, hpp);
+  kernel_fn fn = v8   ? (h->run_pg && hpe && hpp ? pick_kernel8mp(hpe, hpp_k) : h->run_gn8 == 2 ? pick_kernel8gp(hpe, hpp_k) : h->run_gn8 ? pick_kernel8g(hpe, hpp_k) : pick_kernel8_mode(hpe, hpp_k, h->run_split, h->run_mr && hpp))
+                 : se ? pick_kernel_se(hpe, hpp_k, h->run_gn)
+                      : h->run_gn ? pick_kernel_g(hpe, hpp_k) : pick_kernel(hpe, hpp_k);
   // two column tiles per node GEMM on the resident full-ring kernel: its FR instantiation (same arithmetic, same results)
   if (v8 && !h->run_gn8 && h->run_split == 1 && !(h->run_mr && hpp) && P.N > 16 && !getenv("GAUDI_NO_FR"))
-    if (kernel_fn f2 = pick_kernel8s2(hpe, hpp)) fn = f2;
+    if (kernel_fn f2 = pick_kernel8s2(hpe, hpp_k)) fn = f2;
   if (!fn)
     return fail(h, GAUDI_E_INVALID,
                 "no kernel instantiated for padded hidden sizes (" + std::to_string(hpe) + "," + std::to_string(hpp) + ")" +
@@ -1650,7 +1661,7 @@ void gaudi_destroy(gaudi_handle* h) {
                     &h->d_seg, &h->d_zin, &h->d_zout, &h->d_t, &h->d_x, &h->d_h, &h->d_noise, &h->d_nan, &h->d_dpred,
                     &h->d_pred, &h->d_tw, &h->d_stash, &h->d_chain, &h->d_sx, &h->d_stype, &h->d_sn,
                     &h->d_sflags, &h->d_sdist, &h->d_sadj, &h->d_saux, &h->d_stab, &h->d_as, &h->d_ncols, &h->d_soff, &h->d_sidx,
-                    &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp, &h->d_gcoef, &h->d_gidx, &h->d_zt};
+                    &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp, &h->d_gcoef, &h->d_gidx, &h->d_zt, &h->d_vtpar, &h->d_vttrace, &h->d_vtdev};
   for (DevBuf* b : bufs) b->release();
   pt_release(h);
   et_release(h);
@@ -1931,6 +1942,48 @@ static void finish_sample(int B, int N, const float* node_mask, float* x_out, in
   }
 }
 
+// ---- value targets (gaudi_sample_target): one molecule's parameter row w | q | c | side | scale (device_common.h: target_seed)
+static void vt_pack_row(const gaudi_target_spec& sp, int K, int b, float* row) {
+  for (int k = 0; k < K; ++k) {
+    row[k] = sp.w ? sp.w[(sp.w_per_mol ? (size_t)b * K : 0) + k] : 0.f;
+    row[K + k] = sp.q ? sp.q[(sp.q_per_mol ? (size_t)b * K : 0) + k] : 0.f;
+    row[2 * K + k] = sp.c ? sp.c[(sp.c_per_mol ? (size_t)b * K : 0) + k] : 0.f;
+    row[3 * K + k] = sp.side ? (float)sp.side[(sp.side_per_mol ? (size_t)b * K : 0) + k] : 0.f;
+  }
+  row[4 * K] = sp.scale ? sp.scale[sp.scale_per_mol ? b : 0] : 1.f;
+}
+// refusals that need no device: K, sides, finiteness, the window against T (T <= 0: not checked)
+static const char* vt_check(const gaudi_target_spec* sp, int B, int K, int T) {
+  if (!sp) return "no target spec";
+#ifdef GAUDI_STAMPS
+  if (T > 0) return "value targets are not available in the GAUDI_STAMPS diagnostic build (it times the affine fused step only)";
+#endif
+  if (B <= 0) return "B must be positive";
+  if (sp->K != K) return "the target spec's K differs from the predictor's number of outputs";
+  if (K <= 0 || K > 16) return "a target spec takes 1 to 16 predictor outputs";
+  auto finite = [&](const float* a, int per_mol, size_t per) {
+    if (!a) return true;
+    const size_t n = per_mol ? (size_t)B * per : per;
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(a[i])) return false;
+    return true;
+  };
+  if (!finite(sp->w, sp->w_per_mol, K) || !finite(sp->q, sp->q_per_mol, K) || !finite(sp->c, sp->c_per_mol, K) ||
+      !finite(sp->scale, sp->scale_per_mol, 1))
+    return "a target parameter (w, q, c or scale) is not finite";
+  if (sp->side) {
+    const size_t n = sp->side_per_mol ? (size_t)B * K : (size_t)K;
+    for (size_t i = 0; i < n; ++i)
+      if (sp->side[i] < -1 || sp->side[i] > 1) return "side must be -1 (lower bound), 0 (value) or +1 (upper bound)";
+  }
+  const bool dflt = sp->t_lo == 0 && sp->t_hi == 0;
+  if (!dflt && T > 0) {
+    if (sp->t_lo < 1 || sp->t_hi > T) return "the guidance window must lie inside 1..T";
+    if (sp->t_lo > sp->t_hi) return "the guidance window is empty (t_lo > t_hi)";
+  }
+  return nullptr;
+}
+
 // shared by gaudi_step / gaudi_decode / gaudi_sample
 static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, const float* z_in,
                      bool do_init, int s_hi, int s_lo, bool do_decode, const float* noise, int draw_base, int n_draws,
@@ -1944,7 +1997,9 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
   HIPCHECK(h, hipSetDevice(h->device));
   KParams P{};
-  h->pack_now = chain_out == nullptr;  // sampling calls may pack small molecules into one workgroup (stage_graph8)
+  // sampling calls may pack small molecules into one workgroup (stage_graph8); a value target's seed and trace are per
+  // molecule while a shared workgroup has ONE readout: those calls keep one molecule per workgroup
+  h->pack_now = chain_out == nullptr && h->vt == nullptr;
   int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, target_w ? h->HPP : 0);
   h->pack_now = false;
   if (rc) return rc;
@@ -2022,6 +2077,38 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
     if (rc) return rc;
     hpp = h->HPP;
   }
+  std::vector<int32_t> vt_on;  // value target: which rows of the step table lie in the guidance window
+  const int vt_rows = gp ? gp->rows : T;
+  size_t vt_trace_bytes = 0;
+  if (h->vt && target_w) {
+    const gaudi_handle::VtCall& v = *h->vt;
+    if (P.rowmap != nullptr || P.NR != P.N || P.B != B) return fail(h, GAUDI_E_STATE, "a value-target launch must hold one molecule per workgroup");
+    const int K = v.K, RW = target_row_floats(K);
+    std::vector<float> par((size_t)B * RW);
+    for (int b = 0; b < B; ++b) vt_pack_row(*v.spec, K, v.b0 + b, &par[(size_t)b * RW]);
+    HIPCHECK(h, h->d_vtpar.reserve(sizeof(float) * par.size()));
+    HIPCHECK(h, hipMemcpyAsync(h->d_vtpar.p, par.data(), sizeof(float) * par.size(), hipMemcpyHostToDevice, h->stream));
+    VtDev vd{};
+    vd.par = h->d_vtpar.as<float>();
+    vd.B = B;
+    const int t_lo = v.spec->t_lo > 0 ? v.spec->t_lo : 1, t_hi = v.spec->t_hi > 0 ? v.spec->t_hi : T;
+    vt_on.resize(vt_rows);
+    for (int r = 0; r < vt_rows; ++r) {
+      const int t_from = gp ? (r == gp->rows - 1 ? gp->t0 : gp->idx[r + 1]) : r + 1;  // the step of row r starts at this time index
+      vt_on[r] = t_lo <= t_from && t_from <= t_hi;
+    }
+    if (v.trace) {
+      vt_trace_bytes = sizeof(float) * (size_t)(s_hi - s_lo + 1) * B * (K + 2);
+      HIPCHECK(h, h->d_vttrace.reserve(vt_trace_bytes));
+      HIPCHECK(h, hipMemsetAsync(h->d_vttrace.p, 0, vt_trace_bytes, h->stream));
+      vd.trace = h->d_vttrace.as<float>();
+      vd.top = s_hi;
+    }
+    HIPCHECK(h, h->d_vtdev.reserve(sizeof(VtDev)));
+    HIPCHECK(h, hipMemcpyAsync(h->d_vtdev.p, &vd, sizeof(VtDev), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(h, hipStreamSynchronize(h->stream));  // (par and vd are locals of this block)
+    P.vt = h->d_vtdev.as<VtDev>();
+  }
   float* zin = h->d_zin.as<float>();
   float* zout = h->d_zout.as<float>();
   if (h->run_two && target_w) {
@@ -2033,13 +2120,18 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
       P.s_hi = P.s_lo = s;
       P.do_init = (s == s_hi) && do_init;
       P.do_decode = 0;
-      P.split = 1;
+      const bool off_window = !vt_on.empty() && !vt_on[s];  // zero gradient: the denoiser-only kernel finishes the step itself
+      P.split = off_window ? 0 : 1;
       P.z_in = zin;
       P.z_out = zout;
       rc = launch(h, P, h->HPE, 0, 1);
       if (rc) return rc;
       P.alpha_sigma = nullptr;  // (a seeded start: the first launch has noised the given molecules)
       P.zt_out = nullptr;
+      if (off_window) {
+        std::swap(zin, zout);
+        continue;
+      }
       P.mode = MODE_GUIDE;
       P.do_init = 0;
       P.split = 0;
@@ -2067,7 +2159,15 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   int s = s_hi;
   const bool any_steps = s_hi >= s_lo;
   do {
-    const int lo = any_steps ? std::max(s_lo, s - h->steps_per_launch + 1) : s + 1;
+    int lo = any_steps ? std::max(s_lo, s - h->steps_per_launch + 1) : s + 1;
+    if (!vt_on.empty() && any_steps) {
+      // a guidance window is launch-uniform: the launch ends where the next step falls on the other side of it, and a launch
+      // outside the window takes the guided step with a zero gradient (guided = 2: no predictor pass)
+      int cut = s;
+      while (cut > lo && vt_on[cut - 1] == vt_on[s]) --cut;
+      lo = cut;
+      P.guided = vt_on[s] ? 1 : 2;
+    }
     P.s_hi = s;
     P.s_lo = lo;
     P.do_init = first && do_init;
@@ -2092,9 +2192,20 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   }
   if (chain_out)
     HIPCHECK(h, hipMemcpyAsync(chain_out, h->d_chain.p, zb * (size_t)keep_frames, hipMemcpyDeviceToHost, h->stream));
+  std::vector<float> vt_tr;
+  if (vt_trace_bytes) {
+    vt_tr.resize(vt_trace_bytes / sizeof(float));
+    HIPCHECK(h, hipMemcpyAsync(vt_tr.data(), h->d_vttrace.p, vt_trace_bytes, hipMemcpyDeviceToHost, h->stream));
+  }
   int nanc = 0;
   HIPCHECK(h, hipMemcpyAsync(&nanc, h->d_nan.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(h, hipStreamSynchronize(h->stream));
+  if (vt_trace_bytes) {  // this call's molecules are rows b0 .. b0 + B of the request's [steps][Btot][K + 2]
+    const gaudi_handle::VtCall& v = *h->vt;
+    const size_t row = (size_t)v.K + 2;
+    for (int st = 0; st <= s_hi - s_lo; ++st)
+      std::memcpy(v.trace + ((size_t)st * v.Btot + v.b0) * row, &vt_tr[(size_t)st * B * row], sizeof(float) * B * row);
+  }
   if (nan_count) *nan_count = nanc;
   return GAUDI_OK;
 }
@@ -2224,7 +2335,7 @@ static int sample_impl(gaudi_handle* h, int B, int N, const float* node_mask, co
   std::vector<int32_t> small, large;
   int lim = 0;
   if (h->variant == 8 && h->family_split && h->pack && h->gn8 && h->gn8_pack && !h->force_gn && !h->force_gn8 && !h->fix_noise &&
-      !h->plan_force_waves && (int64_t)B * N < (1 << 28)) {
+      !h->plan_force_waves && (int64_t)B * N < (1 << 28) && !h->vt) {  // (the first bucket runs PACKED: not for a value target)
     Meta8 M;
     std::string err;
     const int hpp = target_w ? h->HPP : 0;
@@ -2312,6 +2423,7 @@ static int sample_impl(gaudi_handle* h, int B, int N, const float* node_mask, co
         nzp = nz.data();
       }
       h->call_molmap = bk.idx ? bk.idx->data() + b0 : nullptr;
+      if (h->vt) h->vt->b0 = b0;
       int nan_sub = 0;
       int rc = run_chain(h, nb, N, nmb + (size_t)b0 * N, emb + (size_t)b0 * N * N, xhb ? xhb + (size_t)b0 * N * D : nullptr, xhb == nullptr,
                          s_top, 0, true, nzp, 0, T + 2, seed,
@@ -2354,6 +2466,81 @@ int gaudi_sample_grid(gaudi_handle* h, int B, int N, const float* node_mask, con
   if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
   return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_w, scale, x_out, onehot_out, z0_out,
                      diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
+}
+
+int gaudi_host_target_seed(const gaudi_target_spec* spec, int B, int K, const float* pred, float* out) {
+  if (!spec || !pred || !out || vt_check(spec, B, K, 0)) return GAUDI_E_INVALID;
+  std::vector<float> row(target_row_floats(K));
+  for (int b = 0; b < B; ++b) {
+    vt_pack_row(*spec, K, b, row.data());
+    for (int k = 0; k < K; ++k) out[(size_t)b * K + k] = target_seed(row.data(), K, k, pred[(size_t)b * K + k]);
+  }
+  return GAUDI_OK;
+}
+
+// clears the handle's value-target call when the entry point returns, whichever way
+struct VtScope {
+  gaudi_handle* h;
+  gaudi_handle::VtCall call;
+  VtScope(gaudi_handle* h_, const gaudi_target_spec* sp, int K, int B, float* trace) : h(h_) {
+    call.spec = sp;
+    call.K = K;
+    call.Btot = B;
+    call.trace = trace;
+    h->vt = &call;
+  }
+  ~VtScope() { h->vt = nullptr; }
+};
+
+int gaudi_sample_target(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                        int64_t sample_offset, const float* noise, float std, const gaudi_target_spec* spec, int n_grid,
+                        const int32_t* grid, const float* x0, const float* onehot0, float* x_out, float* onehot_out,
+                        float* z0_out, float* zt_out, float* trace_out, gaudi_diag* diag) {
+  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
+  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
+  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
+  const int T = h->ecfg.diffusion_steps, K = h->pcfg.out_nf;
+  if (const char* why = vt_check(spec, B, K, T)) return fail(h, GAUDI_E_INVALID, why);
+  std::vector<int32_t> unit;
+  if (!grid) {  // the unit grid T, T - 1, ..., 0: gaudi_sample's chain
+    unit.resize(T + 1);
+    for (int k = 0; k <= T; ++k) unit[k] = T - k;
+    grid = unit.data();
+    n_grid = T + 1;
+  }
+  GridPlan gp;
+  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
+  std::vector<float> xh0;
+  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
+  if (trace_out) std::memset(trace_out, 0, sizeof(float) * (size_t)gp.rows * B * (K + 2));
+  VtScope scope(h, spec, K, B, trace_out);
+  std::vector<float> zero_w(16, 0.f);  // (target_w != NULL marks the chain as guided; the kernels read the parameter rows instead)
+  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, zero_w.data(), 1.0f, x_out, onehot_out, z0_out,
+                     diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
+}
+
+int gaudi_step_target(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
+                      const float* edge_mask, const float* eps_raw, const gaudi_target_spec* spec, float* zs_out,
+                      float* trace_out) {
+  if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
+  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
+  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
+  if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
+  const int T = h->ecfg.diffusion_steps, K = h->pcfg.out_nf;
+  if (s_idx < 0 || t_idx <= s_idx || t_idx > T) return fail(h, GAUDI_E_INVALID, "a step needs 0 <= s_idx < t_idx <= T");
+  if (const char* why = vt_check(spec, B, K, T)) return fail(h, GAUDI_E_INVALID, why);
+  GridPlan gp;
+  gp.rows = 1;
+  gp.t0 = t_idx;
+  gp.coef.resize(4);
+  coef_row(h->gamma, T, s_idx, t_idx, gp.coef.data());
+  gp.idx.assign(1, s_idx);
+  if (trace_out) std::memset(trace_out, 0, sizeof(float) * (size_t)B * (K + 2));
+  VtScope scope(h, spec, K, B, trace_out);
+  std::vector<float> zero_w(16, 0.f);
+  return run_chain(h, B, N, node_mask, edge_mask, z_t, false, 0, 0, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f, zero_w.data(), 1.0f,
+                   zs_out, nullptr, nullptr, nullptr, nullptr, 0, &gp);
 }
 
 }  // extern "C"

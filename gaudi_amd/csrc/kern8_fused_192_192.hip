@@ -5,6 +5,8 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8_fused_192_192(int hpe, int hpp) {
-  if (hpe == 192 && hpp == 192) return gaudi::sampler_kernel8<192, 192>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 192 && hpp == 192) return vt ? gaudi::sampler_kernel8<192, 192, true> : gaudi::sampler_kernel8<192, 192>;
   return nullptr;
 }

@@ -5,6 +5,8 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8_pred_256(int hpe, int hpp) {
-  if (hpe == 0 && hpp == 256) return gaudi::sampler_kernel8<0, 256>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 0 && hpp == 256) return vt ? gaudi::sampler_kernel8<0, 256, true> : gaudi::sampler_kernel8<0, 256>;
   return nullptr;
 }

@@ -6,8 +6,10 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8gp_tiny(int hpe, int hpp) {
-  if (hpe == 32 && hpp == 48) return gaudi::sampler_kernel8gp<32, 48>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 32 && hpp == 48) return vt ? gaudi::sampler_kernel8gp<32, 48, true> : gaudi::sampler_kernel8gp<32, 48>;
   if (hpe == 32 && hpp == 0) return gaudi::sampler_kernel8gp<32, 0>;
-  if (hpe == 0 && hpp == 48) return gaudi::sampler_kernel8gp<0, 48>;
+  if (hpe == 0 && hpp == 48) return vt ? gaudi::sampler_kernel8gp<0, 48, true> : gaudi::sampler_kernel8gp<0, 48>;
   return nullptr;
 }

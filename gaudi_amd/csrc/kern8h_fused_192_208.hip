@@ -5,6 +5,8 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8h_fused_192_208(int hpe, int hpp) {
-  if (hpe == 192 && hpp == 208) return gaudi::sampler_kernel8h<192, 208>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 192 && hpp == 208) return vt ? gaudi::sampler_kernel8h<192, 208, true> : gaudi::sampler_kernel8h<192, 208>;
   return nullptr;
 }

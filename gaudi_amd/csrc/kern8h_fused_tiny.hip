@@ -5,9 +5,11 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8h_fused_tiny(int hpe, int hpp) {
-  if (hpe == 32 && hpp == 48) return gaudi::sampler_kernel8h<32, 48>;
-  if (hpe == 32 && hpp == 32) return gaudi::sampler_kernel8h<32, 32>;
-  if (hpe == 48 && hpp == 48) return gaudi::sampler_kernel8h<48, 48>;
-  if (hpe == 64 && hpp == 64) return gaudi::sampler_kernel8h<64, 64>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 32 && hpp == 48) return vt ? gaudi::sampler_kernel8h<32, 48, true> : gaudi::sampler_kernel8h<32, 48>;
+  if (hpe == 32 && hpp == 32) return vt ? gaudi::sampler_kernel8h<32, 32, true> : gaudi::sampler_kernel8h<32, 32>;
+  if (hpe == 48 && hpp == 48) return vt ? gaudi::sampler_kernel8h<48, 48, true> : gaudi::sampler_kernel8h<48, 48>;
+  if (hpe == 64 && hpp == 64) return vt ? gaudi::sampler_kernel8h<64, 64, true> : gaudi::sampler_kernel8h<64, 64>;
   return nullptr;
 }

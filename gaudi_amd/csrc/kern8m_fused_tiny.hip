@@ -7,17 +7,19 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8m_fused_tiny(int hpe, int hpp, int mode) {
-  if (hpe == 32 && hpp == 48 && mode == 0) return gaudi::sampler_kernel8m<0, 32, 48>;
-  if (hpe == 32 && hpp == 32 && mode == 0) return gaudi::sampler_kernel8m<0, 32, 32>;
-  if (hpe == 48 && hpp == 48 && mode == 0) return gaudi::sampler_kernel8m<0, 48, 48>;
-  if (hpe == 64 && hpp == 64 && mode == 0) return gaudi::sampler_kernel8m<0, 64, 64>;
-  if (hpe == 32 && hpp == 48 && mode == 1) return gaudi::sampler_kernel8m<1, 32, 48>;
-  if (hpe == 32 && hpp == 32 && mode == 1) return gaudi::sampler_kernel8m<1, 32, 32>;
-  if (hpe == 48 && hpp == 48 && mode == 1) return gaudi::sampler_kernel8m<1, 48, 48>;
-  if (hpe == 64 && hpp == 64 && mode == 1) return gaudi::sampler_kernel8m<1, 64, 64>;
-  if (hpe == 32 && hpp == 48 && mode == 2) return gaudi::sampler_kernel8m<2, 32, 48>;
-  if (hpe == 32 && hpp == 32 && mode == 2) return gaudi::sampler_kernel8m<2, 32, 32>;
-  if (hpe == 48 && hpp == 48 && mode == 2) return gaudi::sampler_kernel8m<2, 48, 48>;
-  if (hpe == 64 && hpp == 64 && mode == 2) return gaudi::sampler_kernel8m<2, 64, 64>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 32 && hpp == 48 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 32, 48, true> : gaudi::sampler_kernel8m<0, 32, 48>;
+  if (hpe == 32 && hpp == 32 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 32, 32, true> : gaudi::sampler_kernel8m<0, 32, 32>;
+  if (hpe == 48 && hpp == 48 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 48, 48, true> : gaudi::sampler_kernel8m<0, 48, 48>;
+  if (hpe == 64 && hpp == 64 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 64, 64, true> : gaudi::sampler_kernel8m<0, 64, 64>;
+  if (hpe == 32 && hpp == 48 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 32, 48, true> : gaudi::sampler_kernel8m<1, 32, 48>;
+  if (hpe == 32 && hpp == 32 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 32, 32, true> : gaudi::sampler_kernel8m<1, 32, 32>;
+  if (hpe == 48 && hpp == 48 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 48, 48, true> : gaudi::sampler_kernel8m<1, 48, 48>;
+  if (hpe == 64 && hpp == 64 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 64, 64, true> : gaudi::sampler_kernel8m<1, 64, 64>;
+  if (hpe == 32 && hpp == 48 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 32, 48, true> : gaudi::sampler_kernel8m<2, 32, 48>;
+  if (hpe == 32 && hpp == 32 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 32, 32, true> : gaudi::sampler_kernel8m<2, 32, 32>;
+  if (hpe == 48 && hpp == 48 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 48, 48, true> : gaudi::sampler_kernel8m<2, 48, 48>;
+  if (hpe == 64 && hpp == 64 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 64, 64, true> : gaudi::sampler_kernel8m<2, 64, 64>;
   return nullptr;
 }

@@ -7,14 +7,16 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8m_pred_small(int hpe, int hpp, int mode) {
-  if (hpe == 0 && hpp == 32 && mode == 0) return gaudi::sampler_kernel8m<0, 0, 32>;
-  if (hpe == 0 && hpp == 48 && mode == 0) return gaudi::sampler_kernel8m<0, 0, 48>;
-  if (hpe == 0 && hpp == 64 && mode == 0) return gaudi::sampler_kernel8m<0, 0, 64>;
-  if (hpe == 0 && hpp == 32 && mode == 1) return gaudi::sampler_kernel8m<1, 0, 32>;
-  if (hpe == 0 && hpp == 48 && mode == 1) return gaudi::sampler_kernel8m<1, 0, 48>;
-  if (hpe == 0 && hpp == 64 && mode == 1) return gaudi::sampler_kernel8m<1, 0, 64>;
-  if (hpe == 0 && hpp == 32 && mode == 2) return gaudi::sampler_kernel8m<2, 0, 32>;
-  if (hpe == 0 && hpp == 48 && mode == 2) return gaudi::sampler_kernel8m<2, 0, 48>;
-  if (hpe == 0 && hpp == 64 && mode == 2) return gaudi::sampler_kernel8m<2, 0, 64>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 0 && hpp == 32 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 0, 32, true> : gaudi::sampler_kernel8m<0, 0, 32>;
+  if (hpe == 0 && hpp == 48 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 0, 48, true> : gaudi::sampler_kernel8m<0, 0, 48>;
+  if (hpe == 0 && hpp == 64 && mode == 0) return vt ? gaudi::sampler_kernel8m<0, 0, 64, true> : gaudi::sampler_kernel8m<0, 0, 64>;
+  if (hpe == 0 && hpp == 32 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 0, 32, true> : gaudi::sampler_kernel8m<1, 0, 32>;
+  if (hpe == 0 && hpp == 48 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 0, 48, true> : gaudi::sampler_kernel8m<1, 0, 48>;
+  if (hpe == 0 && hpp == 64 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 0, 64, true> : gaudi::sampler_kernel8m<1, 0, 64>;
+  if (hpe == 0 && hpp == 32 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 0, 32, true> : gaudi::sampler_kernel8m<2, 0, 32>;
+  if (hpe == 0 && hpp == 48 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 0, 48, true> : gaudi::sampler_kernel8m<2, 0, 48>;
+  if (hpe == 0 && hpp == 64 && mode == 2) return vt ? gaudi::sampler_kernel8m<2, 0, 64, true> : gaudi::sampler_kernel8m<2, 0, 64>;
   return nullptr;
 }

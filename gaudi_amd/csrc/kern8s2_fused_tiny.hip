@@ -5,7 +5,9 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern8s2_fused_tiny(int hpe, int hpp) {
-  if (hpe == 32 && hpp == 48) return gaudi::sampler_kernel8s2<32, 48>;
-  if (hpe == 64 && hpp == 64) return gaudi::sampler_kernel8s2<64, 64>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 32 && hpp == 48) return vt ? gaudi::sampler_kernel8s2<32, 48, true> : gaudi::sampler_kernel8s2<32, 48>;
+  if (hpe == 64 && hpp == 64) return vt ? gaudi::sampler_kernel8s2<64, 64, true> : gaudi::sampler_kernel8s2<64, 64>;
   return nullptr;
 }

@@ -5,6 +5,8 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern_fused_128_128(int hpe, int hpp) {
-  if (hpe == 128 && hpp == 128) return gaudi::sampler_kernel<128, 128>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 128 && hpp == 128) return vt ? gaudi::sampler_kernel<128, 128, true> : gaudi::sampler_kernel<128, 128>;
   return nullptr;
 }

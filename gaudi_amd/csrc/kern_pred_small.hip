@@ -5,9 +5,11 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kern_pred_small(int hpe, int hpp) {
-  if (hpe == 0 && hpp == 32) return gaudi::sampler_kernel<0, 32>;
-  if (hpe == 0 && hpp == 48) return gaudi::sampler_kernel<0, 48>;
-  if (hpe == 0 && hpp == 64) return gaudi::sampler_kernel<0, 64>;
-  if (hpe == 0 && hpp == 128) return gaudi::sampler_kernel<0, 128>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 0 && hpp == 32) return vt ? gaudi::sampler_kernel<0, 32, true> : gaudi::sampler_kernel<0, 32>;
+  if (hpe == 0 && hpp == 48) return vt ? gaudi::sampler_kernel<0, 48, true> : gaudi::sampler_kernel<0, 48>;
+  if (hpe == 0 && hpp == 64) return vt ? gaudi::sampler_kernel<0, 64, true> : gaudi::sampler_kernel<0, 64>;
+  if (hpe == 0 && hpp == 128) return vt ? gaudi::sampler_kernel<0, 128, true> : gaudi::sampler_kernel<0, 128>;
   return nullptr;
 }

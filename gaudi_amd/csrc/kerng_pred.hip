@@ -4,7 +4,9 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kerng_pred(int hpe, int hpp) {
-  if (hpe == 0 && hpp == 48) return gaudi::sampler_kernel_g<0, 48>;
-  if (hpe == 0 && hpp == 208) return gaudi::sampler_kernel_g<0, 208>;
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
+  if (hpe == 0 && hpp == 48) return vt ? gaudi::sampler_kernel_g<0, 48, true> : gaudi::sampler_kernel_g<0, 48>;
+  if (hpe == 0 && hpp == 208) return vt ? gaudi::sampler_kernel_g<0, 208, true> : gaudi::sampler_kernel_g<0, 208>;
   return nullptr;
 }

@@ -5,8 +5,10 @@
 typedef void (*kernel_fn)(const gaudi::KParams);
 
 kernel_fn gaudi_kernse_fused(int hpe, int hpp, int gn) {
+  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
+  hpp &= ~gaudi::kVtKernel;
   if (gn) return nullptr;
-  if (hpe == 32 && hpp == 48) return gaudi::sampler_kernel_se<32, 48>;
-  if (hpe == 192 && hpp == 208) return gaudi::sampler_kernel_se<192, 208>;
+  if (hpe == 32 && hpp == 48) return vt ? gaudi::sampler_kernel_se<32, 48, true> : gaudi::sampler_kernel_se<32, 48>;
+  if (hpe == 192 && hpp == 208) return vt ? gaudi::sampler_kernel_se<192, 208, true> : gaudi::sampler_kernel_se<192, 208>;
   return nullptr;
 }

@@ -642,7 +642,9 @@ template <int HP, bool GN = false>
 __device__ __forceinline__ void guidance_update(const PredDev& W, const MolGraph& mg, float* net, float* sZ, float* sGrad, float* sTmp,
                                 float* sMean, float t_val, float sigma, const float* target_w, float scale,
                                 float* pred_out, float readout_div, float* stash, int tid STAMP_DECL, int phase = 0,
-                                const float* dpred_ext = nullptr, float* gnode = nullptr, const float* dz_ext = nullptr) {
+                                const float* dpred_ext = nullptr, float* gnode = nullptr, const float* dz_ext = nullptr,
+                                const float* vt = nullptr, float* trn = nullptr) {
+  // vt / trn (or nullptr): a value target's parameter row (device_common.h: target_seed) and the norm | clip slots of its trace row
   (void)sTmp;
   const int N = mg.N, D = mg.D;
   PredSmem<HP, GN> sm;
@@ -651,7 +653,8 @@ __device__ __forceinline__ void guidance_update(const PredDev& W, const MolGraph
   if (tid < W.K) {
     if (pred_out && phase != 2) pred_out[tid] = sm.pred[tid];
     // energy = scale * sum_b T(pred_b)  ->  d(energy)/dpred = scale * dT/dpred
-    sm.pred[16 + tid] = (phase == 2 ? dpred_ext[tid] : target_w[tid]) * scale;
+    if (vt != nullptr && phase == 0) sm.pred[16 + tid] = target_seed(vt, W.K, tid, sm.pred[tid]);
+    else sm.pred[16 + tid] = (phase == 2 ? dpred_ext[tid] : target_w[tid]) * scale;
   }
   __syncthreads();
   if (phase == 1) return;
@@ -665,7 +668,13 @@ __device__ __forceinline__ void guidance_update(const PredDev& W, const MolGraph
     float s = 0.f;
     for (int e = tid; e < N * D; e += 64) s += sGrad[e] * sGrad[e];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (tid == 0) sMean[4] = fminf(10.0f / (sqrtf(s) + 1e-6f), 1.0f);
+    if (tid == 0) {
+      sMean[4] = fminf(10.0f / (sqrtf(s) + 1e-6f), 1.0f);
+      if (trn != nullptr) {
+        trn[0] = sqrtf(s);
+        trn[1] = sMean[4];
+      }
+    }
   }
   __syncthreads();
   const float coef = sMean[4];

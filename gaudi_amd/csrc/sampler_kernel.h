@@ -19,7 +19,9 @@ struct KParams {
   int mode, B, N, F, EW;   // B workgroups (molecules, or groups of them), N node slots per workgroup
   int NR;                   // rows per molecule in the global [molecules][NR][.] arrays (= N unless the launch runs wide groups:
                             // gaudi_hip.hip, stage_graph8 -- a group of several molecules then has MORE node slots than a molecule)
-  int do_init, do_decode, guided;
+  int do_init, do_decode, guided;  // guided: 1 = guided steps; 2 = guided steps OUTSIDE a value target's guidance window: the guided
+                                   // step with a zero gradient (eps_t.nan_to_num and the NaN scrub stay, no predictor pass; the
+                                   // host cuts the chain into launches at the window's ends, so this is launch-uniform)
   int s_hi, s_lo, T;
   // graph metadata (device)
   const float* node_mask;   // [B][N]
@@ -84,7 +86,25 @@ struct KParams {
   unsigned long long* clock_out;
   int hk_off;                  // 8-wave split kernels: float offset (from the start of LDS) of the kept split copy of h, 0 = none
                                // (w8_nodes_f16.h: node_ctx_keep; placed by the host behind the whole plan when 160 KiB leave the room)
+  // Value targets (gaudi_sample_target / gaudi_step_target): read by the VT instantiations of the kernels only (sampler_kernel_v),
+  // which the host launches exactly when this is set.  Such launches are never packed and never wide: one molecule per
+  // workgroup, B = molecules.
+  const struct VtDev* vt;
 };
+// flag in the hpp argument of the translation units' lookup functions (gaudi_kern*_*(hpe, hpp ...)): the VT instantiation
+constexpr int kVtKernel = 1 << 16;
+struct VtDev {                 // (in device memory)
+  const float* par;            // [B][4 K + 1] per-molecule target parameters (device_common.h: target_seed)
+  float* trace;                // [steps][B][K + 2] predictions at (z_s, t) | gradient 2-norm before the clip | clip coefficient, or nullptr
+  int top;                     // row of the step table the first trace row belongs to (trace row = top - row)
+  int B;                       // molecules of the launch
+};
+// this molecule's parameter row / its trace row of the step of table row `srow` (nullptr: not traced)
+__device__ __forceinline__ const float* vt_row(const VtDev* vt, int b, int K) { return vt->par + (size_t)b * target_row_floats(K); }
+__device__ __forceinline__ float* vt_trace_row(const VtDev* vt, int b, int K, int srow) {
+  float* const t = vt->trace;
+  return t != nullptr ? t + ((size_t)(vt->top - srow) * vt->B + b) * (K + 2) : nullptr;
+}
 constexpr int kMaxComp = 4;
 
 __host__ __device__ inline int common_floats(int N, int D, int EW) {
@@ -141,9 +161,12 @@ struct V4T {
   __device__ __forceinline__ static void guide(const PredDev& W, const Graph& mg, float* net, float* sZ, float* sGrad, float* sTmp,
                                                float* sMean, float t_val, float sigma, const float* target_w, float scale,
                                                float* pred_out, float readout_div, float* stash, int tid STAMP_DECL, int phase,
-                                               const float* dpred_ext, float* gnode, const float* dz_ext) {
-    gaudi::guidance_update<HP, GN>(W, mg, net, sZ, sGrad, sTmp, sMean, t_val, sigma, target_w, scale, pred_out, readout_div, stash,
-                                   tid STAMP_ARGS, phase, dpred_ext, gnode, dz_ext);
+                                               const float* dpred_ext, float* gnode, const float* dz_ext, const VtDev* vt,
+                                               int b, int srow) {
+    float* const tr = vt != nullptr ? vt_trace_row(vt, b, W.K, srow) : nullptr;
+    gaudi::guidance_update<HP, GN>(W, mg, net, sZ, sGrad, sTmp, sMean, t_val, sigma, target_w, scale, tr != nullptr ? tr : pred_out,
+                                   readout_div, stash, tid STAMP_ARGS, phase, dpred_ext, gnode, dz_ext,
+                                   vt != nullptr ? vt_row(vt, b, W.K) : nullptr, tr != nullptr ? tr + W.K : nullptr);
   }
   template <int HP>
   __device__ __forceinline__ static void pred_entry(const PredDev& W, const Graph& mg, float* net, float* sZ, float* sGrad,
@@ -229,6 +252,44 @@ __device__ __forceinline__ EdmDev uni(const EdmDev& w) {
 __device__ __forceinline__ PredDev uni(const PredDev& w) {
   return PredDev{uni(w.w), uni(w.w_bytes), uni(w.F), uni(w.K), uni(w.L), uni(w.attention), uni(w.use_tanh), uni(w.coords_range_layer), uni(w.ktail), uni(w.ws),
                  uni(w.ws_bytes), uni(w.hinv)};
+}
+__device__ __forceinline__ float* lds_base() {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  return smem;
+}
+// ---- value targets on the 8-wave kernels: three small out-of-line phases (sizes, global pointers and LDS OFFSETS in, as above)
+// seed of the reverse pass from this molecule's parameter row (w8_pred.h: guidance_seed is the affine form); a traced step
+// leaves the predictions in its trace row.  pred_off: float offset of PredSmem::pred ([16] pred | [16] dpred).
+__device__ __attribute__((noinline)) void vt_seed8(const VtDev* vt_, int b_, int srow_, int K_, int pred_off_) {
+  const VtDev* const vt = uni(vt_);
+  const int b = uni(b_), K = uni(K_), tid = threadIdx.x;
+  float* const pred = lds_base() + uni(pred_off_);
+  if (tid < K) {
+    float* const tr = vt_trace_row(vt, b, K, uni(srow_));
+    if (tr != nullptr) tr[tid] = pred[tid];
+    pred[16 + tid] = target_seed(vt_row(vt, b, K), K, tid, pred[tid]);
+  }
+  __syncthreads();
+}
+// 2-norm of the gradient before the clip -> trace: the sum guidance_apply takes for an unpacked molecule (lane l of wave 0 adds
+// the elements e = l, l + 64, ... in ascending order, then the same butterfly), so the norm is the one the clip is made from
+__device__ __attribute__((noinline)) void vt_norm8(const VtDev* vt_, int b_, int srow_, int K_, int ND_, int grad_off_) {
+  const VtDev* const vt = uni(vt_);
+  const int K = uni(K_), ND = uni(ND_), tid = threadIdx.x;
+  float* const tr = vt_trace_row(vt, uni(b_), K, uni(srow_));
+  if (tr == nullptr || tid >= 64) return;
+  const float* const g = lds_base() + uni(grad_off_);
+  float s = 0.f;
+  for (int e = tid; e < ND; e += 64) s += g[e] * g[e];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if (tid == 0) tr[K] = sqrtf(s);
+}
+// ... and the clip coefficient guidance_apply left in sMean[3] (component 0)
+__device__ __attribute__((noinline)) void vt_clip8(const VtDev* vt_, int b_, int srow_, int K_, int mean_off_) {
+  const VtDev* const vt = uni(vt_);
+  const int K = uni(K_);
+  float* const tr = vt_trace_row(vt, uni(b_), K, uni(srow_));
+  if (tr != nullptr && threadIdx.x == 0) tr[K + 1] = (lds_base() + uni(mean_off_))[3];
 }
 #ifndef GAUDI_STAMPS
 // GN: the node buffers of the phase live in the workgroup's slice of the global scratch (gnode_), everything else in LDS
@@ -338,8 +399,10 @@ struct V8T {
   __device__ __forceinline__ static void guide(const PredDev& W, const Graph& mg, float* net, float* sZ, float* sGrad, float* sTmp,
                                                float* sMean, float t_val, float sigma, const float* target_w, float scale,
                                                float* pred_out, float readout_div, float* stash, int tid STAMP_DECL, int phase,
-                                               const float* dpred_ext, float* gnode, const float* dz_ext) {
+                                               const float* dpred_ext, float* gnode, const float* dz_ext, const VtDev* vt,
+                                               int b, int srow) {
 #ifdef GAUDI_STAMPS
+    (void)vt; (void)b; (void)srow;  // (the stamped diagnostic build times the affine fused step only)
     (void)dz_ext;  // (the stamped diagnostic build times the fused step only)
     w8::guidance_update<HP, SP, MR, GN, PG>(W, mg, net, sZ, sGrad, sTmp, sMean, t_val, sigma, target_w, scale, pred_out, readout_div, stash,
                                             mg.pubx, mg.pub_ch, tid STAMP_ARGS, phase, dpred_ext, (GN || PG) ? uni(gnode) : nullptr);
@@ -348,14 +411,19 @@ struct V8T {
     w8::PredSmem<HP, SP, GN, PG> sm;
     sm.carve(net, mg.N, mg.S, mg.pubx, gnode);
     if (phase != 2) pred_fwd8_call<HP, SP, MR, GN, kFL, PG>(W, gargs(mg), t_val, stash, readout_div, gnode);
-    w8::guidance_seed(W, sm, target_w, scale, pred_out, tid, phase, dpred_ext);
+    // (a value target takes out-of-line helpers around the unchanged affine code; vt is a compile-time nullptr in every
+    // instantiation but the VT ones, so these branches exist in those alone)
+    if (vt != nullptr) vt_seed8(vt, b, srow, W.K, (int)(sm.pred - lds_base()));
+    else w8::guidance_seed(W, sm, target_w, scale, pred_out, tid, phase, dpred_ext);
     if (phase == 1) return;
     pred_bwd8_call<HP, SP, MR, GN, kFL, PG>(W, gargs(mg), stash, readout_div, phase == 2 ? 1 : 0, gnode);
     if (dz_ext != nullptr) {  // + the target's direct dependence on z (callback launches are never packed: slot n = node n)
       for (int e = tid; e < mg.N * mg.D; e += kThreads) sGrad[e] += dz_ext[e];
       __syncthreads();
     }
+    if (vt != nullptr) vt_norm8(vt, b, srow, W.K, mg.N * mg.D, (int)(sGrad - lds_base()));  // (before the clip scales the gradient)
     w8::guidance_apply(mg, sZ, sGrad, sMean, sigma, tid);
+    if (vt != nullptr) vt_clip8(vt, b, srow, W.K, (int)(sMean - lds_base()));
 #endif
   }
   template <int HP>
@@ -374,7 +442,9 @@ __host__ __device__ inline int common_floats_base(int N, int D) { return 3 * ali
 
 // V4 -> 256 threads (one wave per SIMD, up to 512 registers); V8 -> 512 threads = two waves per SIMD: the register
 // allocator is held to 256 VGPR + AGPR per lane.  P stays a by-value kernel argument (SGPR-resident).
-template <class V, int HPE, int HPP>
+// VT: the instantiation value-target launches run (KParams::vt set).  Every other launch runs VT = false, in which vt is a
+// compile-time nullptr and `guided` is tested as before: those kernels compile to the code they had without the feature.
+template <class V, int HPE, int HPP, bool VT = false>
 __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P) {
   constexpr int kThreads = V::kThreads;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -627,7 +697,8 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
             STAMP(ST_UPDATE);
           }
           if constexpr (HPP > 0) {
-            if (guided) {
+            // (outside a value target's guidance window the gradient is zero: z_s - sigma * 0 = z_s, no predictor pass)
+            if (VT ? guided == 1 : guided != 0) {
               // guidance (en_diffusion.py:899-920): predictor at (z_s, t), clip, project, apply
               const float t_step = cf[3], sigma_step = cf[2];
               V::template guide<HPP>(P.pred, mg, net, sZ, sEps /* grad */, sNz /* scratch */, sMean, t_step, sigma_step,
@@ -635,7 +706,8 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
                                    P.readout_div, P.stash + (size_t)b * P.stash_stride, tid STAMP_ARGS, split,
                                    split == 2 ? P.dpred_in + (size_t)b * P.pred.K : nullptr,
                                    V::kGlobalNodes ? P.gnode + (size_t)blockIdx.x * P.gnode_stride : nullptr,
-                                   split == 2 && P.dz_in != nullptr ? P.dz_in + (size_t)b * N * D : nullptr);
+                                   split == 2 && P.dz_in != nullptr ? P.dz_in + (size_t)b * N * D : nullptr,
+                                   VT ? P.vt : (const VtDev*)nullptr, b, s_hi - pass);
             }
           }
           if (split == 1) break;  // phase A ends before the projection: phase B resumes from this z_s
@@ -737,7 +809,8 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
                              P.readout_div, P.stash + (size_t)b * P.stash_stride, tid STAMP_ARGS, gsplit,
                              gsplit == 2 ? P.dpred_in + (size_t)b * P.pred.K : nullptr,
                              V::kGlobalNodes ? P.gnode + (size_t)blockIdx.x * P.gnode_stride : nullptr,
-                             gsplit == 2 && P.dz_in != nullptr ? P.dz_in + (size_t)b * N * D : nullptr);
+                             gsplit == 2 && P.dz_in != nullptr ? P.dz_in + (size_t)b * N * D : nullptr,
+                             VT ? P.vt : (const VtDev*)nullptr, b, P.s_hi);
       if (gsplit == 1) return;
       col_means(sZ);
       __syncthreads();
@@ -770,34 +843,34 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
 }
 
 typedef void (*sampler_fn)(const KParams);
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel = &sampler_kernel_v<V4, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel_g = &sampler_kernel_v<V4G, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel_se = &sampler_kernel_v<V4S, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel_gse = &sampler_kernel_v<V4GS, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8 = &sampler_kernel_v<V8, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8s = &sampler_kernel_v<V8S, HPE, HPP>;
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8s2 = &sampler_kernel_v<V8T<1, false, false, true>, HPE, HPP>;  // (FR: kern8s2_*.hip)
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8h = &sampler_kernel_v<V8H, HPE, HPP>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel = &sampler_kernel_v<V4, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel_g = &sampler_kernel_v<V4G, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel_se = &sampler_kernel_v<V4S, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel_gse = &sampler_kernel_v<V4GS, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8 = &sampler_kernel_v<V8, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8s = &sampler_kernel_v<V8S, HPE, HPP, VT>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8s2 = &sampler_kernel_v<V8T<1, false, false, true>, HPE, HPP, VT>;  // (FR: kern8s2_*.hip)
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8h = &sampler_kernel_v<V8H, HPE, HPP, VT>;
 // ... whose predictor runs several rounds of edge tiles (kern8m_*.hip): SP = 0 / 1 / 2 as above
-template <int SP, int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8m = &sampler_kernel_v<V8T<SP, true>, HPE, HPP>;
+template <int SP, int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8m = &sampler_kernel_v<V8T<SP, true>, HPE, HPP, VT>;
 // ... and with the node buffers in global memory (kern8g_*.hip: molecules beyond the LDS limit; split edge GEMMs, full ring,
 // several rounds of edge tiles in the predictor)
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8g = &sampler_kernel_v<V8T<1, true, 1>, HPE, HPP>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8g = &sampler_kernel_v<V8T<1, true, 1>, HPE, HPP, VT>;
 // ... wide groups on the FULL ring: several rounds of edge tiles, the predictor's fifth node buffer in the global scratch (kern8mp_*.hip)
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8mp = &sampler_kernel_v<V8T<1, true, 0, false, true>, HPE, HPP>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8mp = &sampler_kernel_v<V8T<1, true, 0, false, true>, HPE, HPP, VT>;
 // ... of which P and Q stay in LDS (kern8gp_*.hip: taken where that plan fits)
-template <int HPE, int HPP>
-inline constexpr sampler_fn sampler_kernel8gp = &sampler_kernel_v<V8T<1, true, 2>, HPE, HPP>;
+template <int HPE, int HPP, bool VT = false>
+inline constexpr sampler_fn sampler_kernel8gp = &sampler_kernel_v<V8T<1, true, 2>, HPE, HPP, VT>;
 
 }  // namespace gaudi

@@ -19,12 +19,16 @@ def shard_bounds(total: int, rank: int, world: int):
 
 
 def sample_sharded(sample_fn, node_mask: np.ndarray, edge_mask: np.ndarray, rank: int, world: int, engine=None, grid=None,
-                   start=None):
+                   start=None, per_sample=None):
     """Run ``sample_fn(node_mask_shard, edge_mask_shard, sample_offset) -> (x, h)`` on this rank's block.
 
     grid / start (a chain on a time grid, from given molecules: Engine.sample) are handed to sample_fn as keyword arguments
     when given; ``start = (x, onehot)`` describes the WHOLE batch and a rank receives its slice by global sample index.  Noise
     is keyed by time index and global sample index on any grid, so the gathered result equals the unsharded run.
+
+    per_sample: dict of arrays whose first axis is the WHOLE batch (per-molecule guidance parameters: a value target's
+    [B,K] weights / centres / ... and [B] scales, Engine.sample_target); a rank receives ``per_sample={name: a[lo:hi]}``,
+    its slice by global sample index, as a keyword argument.
 
     node_mask [B,N(,1)], edge_mask reshapeable to [B,N,N] describe the WHOLE logical batch (already padded
     to the batch-wide N, as sampling_edm.sample_guidance does, sampling_edm.py:177).  ``engine``: the
@@ -47,6 +51,11 @@ def sample_sharded(sample_fn, node_mask: np.ndarray, edge_mask: np.ndarray, rank
             kw["grid"] = grid
         if start is not None:
             kw["start"] = (np.asarray(start[0], np.float32)[lo:hi], np.asarray(start[1], np.float32)[lo:hi])
+        if per_sample is not None:
+            for name, a in per_sample.items():
+                if np.ndim(a) < 1 or np.shape(a)[0] != B:
+                    raise ValueError(f"per_sample[{name!r}] must have the whole batch ({B}) as its first axis, got shape {np.shape(a)}")
+            kw["per_sample"] = {name: np.asarray(a)[lo:hi] for name, a in per_sample.items()}
         x, h = sample_fn(nm[lo:hi], em[lo:hi], lo, **kw)
     finally:
         if engine is not None:

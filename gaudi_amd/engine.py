@@ -34,6 +34,82 @@ def _noise_power(schedule: str) -> float:
     return power
 
 
+def target_spec(spec, B: int, K: int):
+    """A value-target spec (dict with any of w, q, c, side, scale, window; include/gaudi_hip.h: gaudi_target_spec) as the C
+    struct -> (struct, arrays it points into: keep them alive for the call).  w / q / c / side: [K] shared or [B,K] per
+    molecule; scale: a float or [B]; window = (t_lo, t_hi) time indices, None = every step.  Shapes are checked here, values
+    (sides, finiteness, the window against T) by the library."""
+    if not isinstance(spec, dict):
+        if callable(getattr(spec, "spec", None)):  # a models_edm.ValueTarget
+            spec = spec.spec()
+        else:
+            raise GaudiError("a target spec is a dict with any of w, q, c, side, scale, window (or a ValueTarget), "
+                             f"got {type(spec).__name__}")
+    unknown = set(spec) - {"w", "q", "c", "side", "scale", "window"}
+    if unknown:
+        raise GaudiError(f"unknown target spec entries {sorted(unknown)}")
+    cs = _lib.TargetSpec()
+    keep = []
+
+    def arr(name, dtype):
+        a = spec.get(name)
+        if a is None:
+            return None, 0
+        a = np.ascontiguousarray(np.asarray(a), dtype=dtype)
+        if a.shape == (K,):
+            per = 0
+        elif a.shape == (B, K):
+            per = 1
+        else:
+            raise GaudiError(f"target spec '{name}' must be [K] = {(K,)} or [B,K] = {(B, K)}, got {a.shape}")
+        keep.append(a)
+        return a, per
+
+    cs.K = K
+    for name in ("w", "q", "c"):
+        a, per = arr(name, np.float32)
+        setattr(cs, name, None if a is None else a.ctypes.data_as(_lib.FP))
+        setattr(cs, name + "_per_mol", per)
+    sd = spec.get("side")
+    if sd is not None and not np.all(np.asarray(sd) == np.round(np.asarray(sd, np.float64))):
+        raise GaudiError("target spec 'side' must hold -1 (lower bound), 0 (value) or +1 (upper bound)")
+    a, per = arr("side", np.int32)
+    cs.side = None if a is None else a.ctypes.data_as(_lib.IP)
+    cs.side_per_mol = per
+    sc = spec.get("scale")
+    if sc is not None:
+        per = np.ndim(sc) > 0  # a number is shared; an array holds one scale per molecule and must have B entries
+        sc = np.asarray(sc, np.float32)
+        if sc.shape != ((B,) if per else ()):
+            raise GaudiError(f"target spec 'scale' must be a number or [B] = {(B,)}, got {sc.shape}")
+        sc = np.ascontiguousarray(sc.reshape(-1))
+        keep.append(sc)
+        cs.scale = sc.ctypes.data_as(_lib.FP)
+        cs.scale_per_mol = 1 if per else 0
+    win = spec.get("window")
+    if win is not None:
+        cs.t_lo, cs.t_hi = int(win[0]), int(win[1])
+        if cs.t_lo == 0 and cs.t_hi == 0:
+            raise GaudiError("the guidance window must lie inside 1..T")
+    return cs, keep
+
+
+def host_target_seed(spec, pred) -> np.ndarray:
+    """d(scale_b T_b)/dpred [B,K] of a value-target spec at pred [B,K], by the function the kernels use (no device;
+    include/gaudi_hip.h: gaudi_host_target_seed)."""
+    p = f32(pred)
+    if p.ndim != 2:
+        raise GaudiError(f"pred must be [B,K], got {p.shape}")
+    B, K = p.shape
+    cs, keep = target_spec(spec, B, K)
+    out = np.empty_like(p)
+    rc = _lib.load_library().gaudi_host_target_seed(C.byref(cs), B, K, fptr(p), fptr(out))
+    del keep
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_target_seed failed ({rc}): side must be -1 / 0 / +1 and every parameter finite")
+    return out
+
+
 class Engine:
     def __init__(self, device: int = 0):
         self.lib = _lib.load_library()
@@ -546,6 +622,69 @@ class Engine:
                  edge_math_fallback=getattr(self, "_fallback_reason", None), family_split_resident=self.family_split())
         out = (x, h, d) + ((z0,) if return_z0 else ())
         return out + (zt,) if return_zt else out
+
+    # ------------------------------------------------------------------ fused value targets
+    def sample_target(self, node_mask, edge_mask, spec, *, seed=0, sample_offset=0, noise=None, std=1.0, grid=None, start=None,
+                      return_z0=False, return_zt=False, trace=False):
+        """Guided chain for the fused value-target family (include/gaudi_hip.h: gaudi_sample_target) -> (x, h, diag[, z0][, zt]
+        [, trace]).  spec: dict with any of w, q, c, side ([K] shared or [B,K] per molecule), scale (float or [B]) and
+        window = (t_lo, t_hi) in time indices (see target_spec).  trace=True also returns [steps, B, K+2]: the predictions at
+        every guided step, the gradient's 2-norm before the clip and the clip coefficient (zero rows outside the window).
+        grid / start / return_zt as in sample()."""
+        if grid is None and start is not None:
+            raise GaudiError("a start from given molecules needs the time grid to run (grid[0] = the time index to noise to)")
+        self._sync_edm()
+        self._sync_pred()
+        nm = f32(node_mask)
+        B, N = nm.shape[0], nm.shape[1]
+        nm, em = self._masks(nm, edge_mask, B, N)
+        D = 3 + self.F
+        nz = None
+        if noise is not None:
+            nz = f32(noise)
+            want = (self.T + 2, 1 if self.fix_noise else B, N, D)
+            if nz.shape != want:
+                raise GaudiError(f"noise must be [T+2,{'1' if self.fix_noise else 'B'},N,3+F] = {want}, got {nz.shape}")
+        cs, keep = target_spec(spec, B, self.K)
+        x = np.empty((B, N, 3), np.float32)
+        h = np.empty((B, N, self.F), np.float32)
+        z0 = np.empty((B, N, D), np.float32) if return_z0 else None
+        diag = Diag()
+        ng, g, x0, oh0, zt = 0, None, None, None, None
+        if grid is not None:
+            ng, g, x0, oh0, zt = self._grid_args(grid, start, B, N, return_zt)
+        elif return_zt:
+            raise GaudiError("return_zt needs a start from given molecules (start=(x, onehot))")
+        steps = self.T if grid is None else ng - 1
+        tr = np.zeros((max(steps, 0), B, self.K + 2), np.float32) if trace else None
+        self._check(self.lib.gaudi_sample_target(self.h, B, N, fptr(nm), fptr(em), int(seed), int(sample_offset), fptr(nz),
+                                                 float(std), C.byref(cs), ng, None if g is None else g.ctypes.data_as(_lib.IP),
+                                                 fptr(x0), fptr(oh0), fptr(x), fptr(h), fptr(z0), fptr(zt), fptr(tr),
+                                                 C.byref(diag)), "gaudi_sample_target")
+        del keep
+        d = dict(max_masked_leak=diag.max_masked_leak, max_cog_rel=diag.max_cog_rel, max_cog_abs=diag.max_cog_abs,
+                 nan_count=diag.nan_count, reprojected=diag.reprojected,
+                 edge_math_fallback=getattr(self, "_fallback_reason", None), family_split_resident=self.family_split())
+        out = (x, h, d) + ((z0,) if return_z0 else ()) + ((zt,) if return_zt else ())
+        return out + (tr,) if trace else out
+
+    def step_target(self, s_idx, z_t, node_mask, edge_mask, eps_raw, spec, *, t_idx=None, trace=False):
+        """One teacher-forced guided step z_t -> z_s (time index t_idx, default s_idx + 1, down to s_idx) for a value-target
+        spec (gaudi_step_target) -> z_s, or (z_s, trace row [B, K+2]) with trace=True."""
+        self._sync_edm()
+        self._sync_pred()
+        z = f32(z_t)
+        B, N, D = z.shape
+        nm, em = self._masks(node_mask, edge_mask, B, N)
+        eps = f32(eps_raw)
+        cs, keep = target_spec(spec, B, self.K)
+        out = np.empty_like(z)
+        tr = np.zeros((B, self.K + 2), np.float32) if trace else None
+        self._check(self.lib.gaudi_step_target(self.h, B, N, int(s_idx), int(s_idx) + 1 if t_idx is None else int(t_idx), fptr(z),
+                                               fptr(nm), fptr(em), fptr(eps), C.byref(cs), fptr(out), fptr(tr)),
+                    "gaudi_step_target")
+        del keep
+        return (out, tr) if trace else out
 
     def sample_chain(self, node_mask, edge_mask, keep_frames, *, seed=0, sample_offset=0, noise=None, std=1.0):
         """-> chain [keep_frames, B, N, 3+F] (frame 0 = final [x | one_hot]).  Unit time grid only: the reference's frame rule

@@ -64,6 +64,71 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds)
 
 
+def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
+                 n_steps=None):
+    """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
+    j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
+    (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
+
+    targets_or_scales: a list whose entries are numbers (guidance scales of ``target``, a ValueTarget with shared arrays) or
+    ValueTargets with shared ([K]) arrays (each with its own centres / curvatures / scale; ``scale`` multiplies them all).
+    The guidance window is one per call: settings whose windows differ are refused.  Returns one design()-shaped dict per setting, evaluated
+    as design() does; ``seconds`` is the ONE call's time, ``molecules_per_second`` the whole call's rate."""
+    from .models_edm import ValueTarget
+    model.eval()
+    cond_predictor.eval()
+    settings = []
+    for s in targets_or_scales:
+        if isinstance(s, ValueTarget):
+            settings.append((s, 1.0))
+        else:
+            if not isinstance(target, ValueTarget):
+                raise ValueError("a sweep over scales needs target= (a ValueTarget with shared arrays)")
+            settings.append((target, float(s)))
+    if not settings:
+        raise ValueError("design_sweep needs at least one setting")
+    if any(t.window != settings[0][0].window for t, _ in settings):
+        raise ValueError("design_sweep runs one call, and a call has one guidance window: the settings' windows differ")
+    bs, K = int(args.batch_size), int(cond_predictor.engine.K)
+
+    def rows(name, fill, dtype):
+        out = []
+        for t, _ in settings:
+            a = getattr(t, name)
+            a = np.full(K, fill, dtype) if a is None else np.asarray(a, dtype)
+            if a.shape != (K,):
+                raise ValueError(f"design_sweep takes ValueTargets with shared [K] arrays, got {name} of shape {a.shape}")
+            out.append(np.broadcast_to(a, (bs, K)))
+        return np.concatenate(out, 0)
+
+    scales = []
+    for t, mult in settings:
+        sc = np.float32(1.0) if t.scale is None else np.asarray(t.scale, np.float32)
+        if np.ndim(sc):
+            raise ValueError("design_sweep takes ValueTargets with a scalar scale")
+        # (the strength design(..., scale=scale * mult) would give this setting: its own scale times the call's, ValueTarget.spec)
+        scales.append(np.full(bs, np.float32(sc) * np.float32(float(scale) * mult), np.float32))
+    mixed = ValueTarget(cond_predictor, rows("weights", 0, np.float32), rows("curvature", 0, np.float32),
+                        rows("center", 0, np.float32), rows("side", 0, np.int32), np.concatenate(scales),
+                        settings[0][0].window, name="sweep")
+    nodesxsample = np.array([n_nodes] * (bs * len(settings)), dtype=np.int64)
+    start_time = time()
+    x, one_hot, node_mask, edge_mask = sample_guidance(args, model, mixed, nodesxsample, scale=1.0,
+                                                       **({} if n_steps is None else dict(n_steps=n_steps)))
+    seconds = time() - start_time
+    print(f"Generated {x.shape[0]} molecules ({len(settings)} settings) in {seconds:.2f} seconds")
+    N = x.shape[1]
+    em = edge_mask.reshape(len(nodesxsample), N * N)
+    out = []
+    for j, (t, mult) in enumerate(settings):
+        lo, hi = j * bs, (j + 1) * bs
+        d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
+                      em[lo:hi].reshape(-1, 1), seconds)
+        d["molecules_per_second"] = x.shape[0] / seconds
+        out.append(d)
+    return out
+
+
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
            prop_dist=None):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there

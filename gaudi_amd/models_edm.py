@@ -94,6 +94,66 @@ class LinearTarget:
         return _like_ref((pred @ self.weights + self.const).astype(np.float32))
 
 
+class ValueTarget:
+    """Declarative value-seeking target of the predictor outputs, per molecule b:
+        T_b(p) = sum_k w[b,k] p[k] + sum_k q[b,k] a(p[k] - c[b,k], side[b,k])^2
+    with a(d, 0) = d (aim at the value c), a(d, +1) = max(d, 0) (c is an upper bound), a(d, -1) = min(d, 0) (c is a lower
+    bound).  weights / curvature / center / side are [K] (shared) or [B,K] (one row per molecule of the call), scale a float
+    or [B] (the call's own ``scale`` argument multiplies it), window = (t_lo, t_hi): only steps starting at time indices
+    t_lo..t_hi are guided.  Runs fused on the device (gaudi_sample_target): no per-step callback.  Calling it with the
+    reference's closure signature evaluates T on the GPU predictor's output (design() / get_target_function_values)."""
+
+    def __init__(self, cond_predictor, weights=None, curvature=None, center=None, side=None, scale=None, window=None,
+                 name="value"):
+        self.cond_predictor = cond_predictor
+
+        def arr(a, dtype=np.float32):
+            return None if a is None else np.asarray(_to_numpy(a), dtype)
+
+        self.weights, self.curvature, self.center = arr(weights), arr(curvature), arr(center)
+        self.side = arr(side, np.int32)
+        self.scale = None if scale is None else np.asarray(_to_numpy(scale), np.float32)
+        self.window = None if window is None else (int(window[0]), int(window[1]))
+        self.name = name
+
+    @classmethod
+    def from_physical(cls, cond_predictor, prop_dist: PropertyNorm, weights=None, curvature=None, center=None, side=None,
+                      scale=None, window=None, name="value"):
+        """The same target given in physical units of the properties: the predictor works on normalised properties
+        p = (P - mean) / std (PropertyNorm), so  c -> (c - mean) / std,  q -> q std^2,  w -> w std  (the constant w . mean
+        does not change the gradient and is dropped)."""
+        mean, std = prop_dist.mean.astype(np.float32), prop_dist.std.astype(np.float32)
+        conv = lambda a, f: None if a is None else f(np.asarray(_to_numpy(a), np.float32)).astype(np.float32)
+        return cls(cond_predictor, conv(weights, lambda w: w * std), conv(curvature, lambda q: q * std * std),
+                   conv(center, lambda c: (c - mean) / std), side, scale, window, name)
+
+    def spec(self, scale=1.0) -> dict:
+        """The engine's spec dict; ``scale`` (the sampling call's argument) multiplies the target's own."""
+        sc = np.float32(scale) if self.scale is None else (self.scale * np.float32(scale)).astype(np.float32)
+        return dict(w=self.weights, q=self.curvature, c=self.center, side=self.side, scale=sc, window=self.window)
+
+    def value(self, pred: np.ndarray) -> np.ndarray:
+        """T_b(pred_b) [B] in float32 (no scale: the reference's closures return the unscaled target)."""
+        p = np.asarray(pred, np.float32)
+        zero = np.zeros(p.shape[1], np.float32)
+        w = zero if self.weights is None else self.weights
+        q = zero if self.curvature is None else self.curvature
+        c = zero if self.center is None else self.center
+        sd = zero if self.side is None else self.side
+        d = p - c
+        a = np.where(sd == 0, d, np.where(sd > 0, np.where(d > 0, d, 0), np.where(d < 0, d, 0))).astype(np.float32)
+        return ((w * p).sum(1, dtype=np.float32) + (q * a * a).sum(1, dtype=np.float32)).astype(np.float32)
+
+    def grad(self, pred: np.ndarray, t: float = 0.0) -> np.ndarray:
+        """dT/dpred [B,K] times the target's own scale, by the function the kernels use (engine.host_target_seed)."""
+        from .engine import host_target_seed
+        return host_target_seed(self.spec(), pred)
+
+    def __call__(self, _input, _node_mask, _edge_mask, _t):
+        pred = _to_numpy(self.cond_predictor(_input, _node_mask, _edge_mask, _t))
+        return _like_ref(self.value(pred))
+
+
 class ZTarget:
     """A target closure over (z, node_mask, edge_mask, t) that depends on z BOTH through the predictor and directly -- the
     reference differentiates any function of z_s (en_diffusion.py:899-903).  Per reverse step the host evaluates the closure on
@@ -299,6 +359,8 @@ class GaudiModel:
         self.sample_offset = 0
         self.injected_noise = None  # [T+2,B,N,3+F] raw draws (parity tests); None -> on-device Philox
         self.last_diag = None
+        self.trace_guidance = False  # True: a ValueTarget chain also records its guidance trace ...
+        self.last_trace = None       # ... here: [steps, B, K+2] (Engine.sample_target)
         self._state = state_dict
         import weakref
         GaudiModel._latest = weakref.ref(self)
@@ -317,6 +379,7 @@ class GaudiModel:
         m.norm_values = list(checkpoint.normalize_factors(m.args))
         m.norm_biases = (None, 0.0, 0.0)
         m.seed, m.sample_offset, m.injected_noise, m.last_diag = None, 0, None, None
+        m.trace_guidance, m.last_trace = False, None
         return m
 
     @classmethod
@@ -569,7 +632,7 @@ class GaudiModel:
         em = _to_numpy(edge_mask).astype(np.float32).reshape(B, N, N)
         tw = None
         if target is not None:
-            if not isinstance(target, (LinearTarget, PredTarget, ZTarget)):
+            if not isinstance(target, (LinearTarget, PredTarget, ZTarget, ValueTarget)):
                 if not callable(target):
                     raise GaudiError("target_function must be callable")
                 # the reference's own form: a closure over (z, node_mask, edge_mask, t) that calls cond_predictor
@@ -582,7 +645,14 @@ class GaudiModel:
         # fix_noise (en_diffusion.py:562-566,972-978): one raw draw per call, broadcast over the batch
         self.engine.set_fix_noise(bool(fix_noise), off)
         try:
-            if isinstance(target, ZTarget):
+            self.last_trace = None
+            if isinstance(target, ValueTarget):
+                out = self.engine.sample_target(nm.reshape(B, N), em, target.spec(scale), seed=seed, sample_offset=off,
+                                                noise=self.injected_noise, std=std, trace=bool(self.trace_guidance), **gk)
+                x, h, diag = out[0], out[1], out[2]
+                if self.trace_guidance:
+                    self.last_trace = out[-1]  # [steps, B, K+2]: predictions | gradient norm before the clip | clip coefficient
+            elif isinstance(target, ZTarget):
                 nm3, em_flat = nm.reshape(B, N, 1), em.reshape(B * N * N, 1)
                 x, h, diag = self.engine.sample_callback(nm.reshape(B, N), em, lambda z, p, t: target.grad(z, p, t, nm3, em_flat),
                                                          seed=seed, sample_offset=off, noise=self.injected_noise, std=std,

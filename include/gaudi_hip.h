@@ -230,6 +230,48 @@ int gaudi_sample_grid(gaudi_handle* h, int B, int N, const float* node_mask, con
                       float* x_out, float* onehot_out, float* z0_out /* or NULL */, float* zt_out /* or NULL */,
                       gaudi_diag* diag /* or NULL */);
 
+/* ---- Value-seeking targets, per-molecule guidance, a guidance window and a guidance trace, fused. ----
+ * One target per molecule b over the predictor outputs p[k], k < K:
+ *   T_b(p) = sum_k w[b,k] p[k] + sum_k q[b,k] a(p[k] - c[b,k], side[b,k])^2
+ *   a(d, 0) = d  (aim at the value c);  a(d, +1) = d if d > 0 else 0  (upper bound c);  a(d, -1) = d if d < 0 else 0  (lower bound c)
+ * and the energy of sample_p_zs_given_zt_guidance (en_diffusion.py:899-903) is scale[b] * T_b.  The kernels seed the predictor's
+ * reverse pass with  d(scale T)/dp[k] = (w + (q + q) * a) * scale  in fp32, every operation rounded on its own, in that order
+ * (gaudi_host_target_seed is the same function on the host).  Each array is shared ([K]; scale: one float) or per molecule
+ * ([B,K]; scale [B]) as its *_per_mol flag says; a NULL array means 0 (w, q, c, side) or 1 (scale).
+ * Window: the step that STARTS at time index t is guided iff t_lo <= t <= t_hi (both 0: every step, 1..T).  Outside it the step
+ * is the guided step with a zero gradient -- eps_t.nan_to_num and the final NaN scrub stay -- and the predictor is not run. */
+typedef struct {
+  int32_t K;                 /* must equal the predictor's number of outputs (<= 16) */
+  const float* w;            /* linear weights        [K] or [B,K], or NULL */
+  const float* q;            /* curvatures            [K] or [B,K], or NULL */
+  const float* c;            /* centres / bounds      [K] or [B,K], or NULL */
+  const int32_t* side;       /* -1 / 0 / +1           [K] or [B,K], or NULL */
+  const float* scale;        /* guidance strength     [1] or [B],   or NULL */
+  int32_t w_per_mol, q_per_mol, c_per_mol, side_per_mol, scale_per_mol;
+  int32_t t_lo, t_hi;        /* guidance window in time indices; 0, 0 = 1..T */
+} gaudi_target_spec;
+
+/* gaudi_sample_grid with the spec in place of (target_w, scale).  grid == NULL: the unit grid T, T-1, ..., 0 (n_grid ignored).
+ * trace_out (or NULL) [n_grid-1][B][K+2]: for every step in chain order and every molecule, the K predictions at (z_s, t), the
+ * 2-norm of the gradient before the clip, and the clip coefficient min(1, 10 / (norm + 1e-6)) (en_diffusion.py:905-909); rows of
+ * steps outside the window are zero.  Noise keys, sample_offset, fix_noise, grids and seeded starts as in gaudi_sample_grid.
+ * Every molecule runs alone in its workgroup (no packed or wide groups: a shared workgroup has one readout and one seed), so
+ * molecule i's result depends on molecule i's parameters only, bit for bit, and equals gaudi_sample_cb with the same
+ * dT/dpred bit for bit.  GAUDI_E_INVALID (with gaudi_last_error) for: K mismatch, a side outside {-1, 0, 1}, a window outside
+ * 1..T or empty, a non-finite parameter, and what gaudi_sample_grid refuses. */
+int gaudi_sample_target(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
+                        int64_t sample_offset, const float* noise, float std, const gaudi_target_spec* spec, int n_grid,
+                        const int32_t* grid /* or NULL */, const float* x0 /* or NULL */, const float* onehot0 /* or NULL */,
+                        float* x_out, float* onehot_out, float* z0_out /* or NULL */, float* zt_out /* or NULL */,
+                        float* trace_out /* or NULL */, gaudi_diag* diag /* or NULL */);
+/* gaudi_step_pair with the spec; trace_out (or NULL) [B][K+2] = the step's trace row. */
+int gaudi_step_target(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
+                      const float* edge_mask, const float* eps_raw, const gaudi_target_spec* spec, float* zs_out,
+                      float* trace_out /* or NULL */);
+/* The seed the kernels compute, on the host (no device): out [B,K] = d(scale_b T_b)/dp at pred [B,K].  GAUDI_E_INVALID for a
+ * spec whose K differs, a side outside {-1, 0, 1} or a non-finite parameter. */
+int gaudi_host_target_seed(const gaudi_target_spec* spec, int B, int K, const float* pred, float* out);
+
 /* One teacher-forced step z_t -> z_s for ANY pair 0 <= s_idx < t_idx <= T (gaudi_step is t_idx = s_idx + 1, bit for bit).
  * eps_raw stands for raw draw T - s_idx. */
 int gaudi_step_pair(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,

@@ -1754,6 +1754,86 @@ def g28_grid():
     save("g28_grid_chains", **out)
 
 
+def _g29_params(seed, B, K, scale_lo, scale_hi):
+    """Per-molecule value-target parameters (models_edm.ValueTarget): every side occurs, scales spread over [lo, hi]."""
+    rng = np.random.default_rng(seed)
+    w = (0.5 * rng.standard_normal((B, K))).astype(np.float32)
+    q = rng.uniform(0.2, 1.5, (B, K)).astype(np.float32)
+    c = (0.5 * rng.standard_normal((B, K))).astype(np.float32)
+    side = rng.integers(-1, 2, (B, K)).astype(np.int32)
+    side[:, :3] = np.array([0, 1, -1], np.int32)  # (each form in every molecule, whatever the draw)
+    scale = np.exp(rng.uniform(np.log(scale_lo), np.log(scale_hi), B)).astype(np.float32)
+    return dict(w=w, q=q, c=c, side=side, scale=scale)
+
+
+def _g29_closure(pred, par):
+    """The value-target family as a closure the reference differentiates: per-molecule tensors, the per-molecule scale folded
+    in (the reference call runs with scale = 1)."""
+    w, q, c, scale = (torch.from_numpy(par[k]) for k in ("w", "q", "c", "scale"))
+    side = torch.from_numpy(par["side"])
+
+    def tf(_in, _nm, _em, _t):
+        p = pred(_in, _nm, _em, _t)
+        d = p - c
+        a = torch.where(side == 0, d, torch.where(side > 0, d.clamp(min=0), d.clamp(max=0)))
+        return scale * ((w * p).sum(1) + (q * a * a).sum(1))
+
+    return tf
+
+
+def g29_value_target():
+    """Value-seeking targets with per-molecule parameters (aim at a value, upper and lower bounds, per-molecule strength):
+    teacher-forced steps through the reference's sample_p_zs_given_zt_guidance at the tiny and the default widths, and T = 50
+    chains through its sample_guidance at the tiny cata / hetero widths of g7, injected noise."""
+    out = {}
+    K, T = 5, 1000
+    for tag, ds, nodes, over, over_p, eseed, pseed in (("tiny", "hetro", [3, 5, 4], TINY, TINY_P, 2900, 2910),
+                                                       ("default", "cata", [11, 7], {}, {}, 2901, 2911)):
+        F = synth.num_node_features(ds)
+        esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=eseed, amplify_coord=True)
+        a, model = build_ref_edm(ds, esd, **over)
+        psd = synth.synth_predictor_state_dict(synth.pred_args(dataset=ds, **over_p), F, K, seed=pseed, amplify_coord=True)
+        pa, pred = build_ref_pred(ds, psd, **over_p)
+        nm, em, z = case_inputs(ds, nodes, None, seed=2920, guidance_pad=True)
+        B, N, D = z.shape
+        tnm, tem = torch.from_numpy(nm), torch.from_numpy(em)
+        out[f"{tag}_z"], out[f"{tag}_node_mask"], out[f"{tag}_edge_mask"] = z, nm, em
+        steps = (0, 500, 999) if tag == "tiny" else (500,)
+        for strength, (lo, hi) in (("weak", (0.2, 1.0)), ("strong", (100.0, 600.0))):  # strong: the clip branch
+            par = _g29_params(2930 + (strength == "strong"), B, K, lo, hi)
+            for k, v in par.items():
+                out[f"{tag}_{strength}_{k}"] = v
+            tf = _g29_closure(pred, par)
+            for s in steps:
+                eps = rng_noise(2940 + s % 7, (B, N, D))
+                st = torch.full((B, 1), s) / T
+                tt = (torch.full((B, 1), s) + 1) / T
+                out[f"{tag}_s{s}_eps"] = eps
+                with InjectNoise([eps]), torch.no_grad():
+                    zg = model.sample_p_zs_given_zt_guidance(st, tt, torch.from_numpy(z), tnm, tem, tf, 1.0).numpy()
+                out[f"{tag}_{strength}_s{s}_zs"] = zg
+        out[f"{tag}_cfg"] = np.array(json.dumps(dict(dataset=ds, eseed=eseed, pseed=pseed, T=T, nodes=nodes, steps=list(steps), amp=True)))
+    Tc = 50
+    for ci, (name, ds, nodes) in enumerate([("cata_chain", "cata", [6, 8, 8, 3]), ("hetro_chain", "hetro", [3, 5, 4])]):
+        F = synth.num_node_features(ds)
+        over = dict(diffusion_steps=Tc, **TINY)
+        esd = synth.synth_edm_state_dict(synth.edm_args(dataset=ds, **over), F, seed=2950 + ci, amplify_coord=False)
+        a, model = build_ref_edm(ds, esd, **over)
+        psd = synth.synth_predictor_state_dict(synth.pred_args(dataset=ds, **TINY_P), F, K, seed=2960 + ci, amplify_coord=False)
+        pa, pred = build_ref_pred(ds, psd, **TINY_P)
+        par = _g29_params(2970 + ci, len(nodes), K, 0.2, 1.0)
+        Nn = max(nodes) * (2 if ds != "cata" else 1)
+        noise = rng_noise(2980 + ci, (Tc + 2, len(nodes), Nn, 3 + F))
+        with InjectNoise(list(noise)):
+            x, h, nm, em = ref_sampling.sample_guidance(a, model, _g29_closure(pred, par), torch.tensor(nodes), scale=1.0, std=1.0)
+        for k, v in par.items():
+            out[f"{name}_{k}"] = v
+        out[f"{name}_noise"], out[f"{name}_x"], out[f"{name}_h"] = noise, x.numpy(), h.numpy().astype(np.float32)
+        out[f"{name}_node_mask"], out[f"{name}_edge_mask"] = nm.numpy(), em.numpy()
+        out[f"{name}_cfg"] = np.array(json.dumps(dict(dataset=ds, T=Tc, eseed=2950 + ci, pseed=2960 + ci, nodes=nodes, amp=False)))
+    save("g29_value_target", **out)
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1779,7 +1859,7 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target)
     which = sys.argv[1:] or list(fns)
     for w in which:
         fns[w]()
