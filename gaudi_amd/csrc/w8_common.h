@@ -56,8 +56,31 @@ __device__ __forceinline__ float seg_scan1(float x, const RunMask& m) {
   x = fmaf(row_shr<8>(x), m.m8, x);
   return x;
 }
+// The four scans of a tile's float4, interleaved, each step ONE instruction: the multiply-add reads its shifted operand through
+// the DPP modifier itself (x += shr(x) * m, fused as in seg_scan1: the same values).  hipcc does not combine the row shift into
+// the multiply-add here -- it emits a DPP move and a v_fmac per step, 32 instructions per float4 instead of 16 -- so the sequence
+// is written out.  Hazards the compiler cannot see inside the block: a DPP read needs two wait states behind the vector write of
+// its source (met inside: the four scans alternate, three instructions lie between a write and its read) and five behind a vector
+// write of EXEC -- the leading s_nop covers whatever precedes the block.
+#ifndef GAUDI_SCAN_FUSED_DPP
+#define GAUDI_SCAN_FUSED_DPP 1
+#endif
 __device__ __forceinline__ f4 seg_scan(f4 v, const RunMask& m) {
+#if GAUDI_SCAN_FUSED_DPP
+  float a = v[0], b = v[1], c = v[2], d = v[3];
+#define GAUDI_SCAN_STEP(SH, M)                                                                        \
+  "v_fmac_f32_dpp %0, %0, %" #M " row_shr:" #SH " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_fmac_f32_dpp %1, %1, %" #M " row_shr:" #SH " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_fmac_f32_dpp %2, %2, %" #M " row_shr:" #SH " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+  "v_fmac_f32_dpp %3, %3, %" #M " row_shr:" #SH " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+  asm volatile("s_nop 4\n\t" GAUDI_SCAN_STEP(1, 4) GAUDI_SCAN_STEP(2, 5) GAUDI_SCAN_STEP(4, 6) GAUDI_SCAN_STEP(8, 7)
+               : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
+               : "v"(m.m1), "v"(m.m2), "v"(m.m4), "v"(m.m8));
+#undef GAUDI_SCAN_STEP
+  return (f4){a, b, c, d};
+#else
   return (f4){seg_scan1(v[0], m), seg_scan1(v[1], m), seg_scan1(v[2], m), seg_scan1(v[3], m)};
+#endif
 }
 
 // edge word of a slot: i | j << 8 | run_start << 16 (column inside the tile) | run_end << 20 | part << 21

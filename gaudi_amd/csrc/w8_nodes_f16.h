@@ -21,7 +21,8 @@
 // NODE and per GEMM input on the device (the row's max exponent -> 2^14: split_rows_h), undone in the epilogue.  NaN
 // propagates as in fp32; an infinite activation gives NaN where fp32 gives +-inf (hi = inf, x - hi = NaN) -- the sampler
 // scrubs both the same way (models.py:138-141).  The host refuses the form (-> fp32 node GEMMs, with a warning: gaudi_last_warning)
-// for weight sets with infinities or a matrix whose largest entry lies more than 2^12 below the network's (gaudi_hip.hip: NodeScale).
+// for weight sets with infinities or a matrix whose largest entry lies more than 2^17 (edge-level matrices; node-level: 2^25) below
+// the network's (gaudi_hip.hip: NodeScale).
 //
 // Bytes.  hi and lo are 2 + 2 bytes: a matrix image is exactly the fp32 matrix's size -- units of 1 KiB ordered
 // [K chunk of 32][output tile][piece], lane L = (row L & 15, inputs 8 (L >> 4) .. +7 of the chunk).  An odd tile count (208 =
@@ -76,9 +77,6 @@ struct NodeStampH {
 
 __device__ __forceinline__ f4 mfma_h(const u4 a, const u4 b, const f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ u4 ldu4h(const WBuf& wh, int off_floats, int lane) {
-  return __builtin_bit_cast(u4, ldw4n(wh, off_floats, lane));
 }
 
 // ---- geometry shared with the host packer (gaudi_hip.hip: pack_matrix_f16)
@@ -228,23 +226,28 @@ struct NodePFH {
   NodeSetH<NodeGeoH<HP>::NTW> s[NodeGeoH<HP>::D];  // chunks 0 .. D-1 of the next node GEMM, loaded ahead of the call
 };
 
-// the lane offsets of the wave's tiles: a tile the wave does not have is "loaded" with an out-of-range lane (returns 0, fetches
-// nothing) -- every wave runs the same loads, none sits behind a branch
+// the byte offsets of the lane's 16 bytes inside a chunk, per tile of the wave -- tile t's two units start at t * 2 KiB, the lane's
+// share at lane * 16 -- as the loads' VECTOR offset: the wave's tile never enters the scalar offset, which is then the chunk's alone
+// and shared by the loads of a chunk, and the second piece (+1 KiB) rides in the instruction's immediate.  (With the tile in the
+// scalar offset every 1 KiB unit had one of its own: two scalar additions per load in the K loops.)  A tile the wave does not
+// have is "loaded" with an out-of-range offset (returns 0, fetches nothing) -- every wave runs the same loads, none sits behind a
+// branch.  kOOBBytes + 1 KiB neither wraps nor comes back into range: descriptors are smaller than 2 GiB.
+constexpr int kOOBBytes = (int)0x80000000u;
 template <int HP>
 struct TileLanesH {
-  int l[NodeGeoH<HP>::NTW];
+  int vo[NodeGeoH<HP>::NTW];
   __device__ __forceinline__ TileLanesH(int wave, int lane, bool on = true) {
 #pragma unroll
-    for (int u = 0; u < NodeGeoH<HP>::NTW; ++u) l[u] = (on && wave + kWaves * u < NodeGeoH<HP>::T) ? lane : kOOBLane;
+    for (int u = 0; u < NodeGeoH<HP>::NTW; ++u)
+      vo[u] = (on && wave + kWaves * u < NodeGeoH<HP>::T) ? lane * 16 + (wave + kWaves * u) * 2048 : kOOBBytes;
   }
 };
 template <int HP>
-__device__ __forceinline__ void nh_load(NodeSetH<NodeGeoH<HP>::NTW>& s, const WBuf& wh, int chunk_off, int wave, const TileLanesH<HP>& tl) {
+__device__ __forceinline__ void nh_load(NodeSetH<NodeGeoH<HP>::NTW>& s, const WBuf& wh, int chunk_off, const TileLanesH<HP>& tl) {
 #pragma unroll
   for (int u = 0; u < NodeGeoH<HP>::NTW; ++u) {
-    const int t = wave + kWaves * u < NodeGeoH<HP>::T ? wave + kWaves * u : 0;
-    s.p[u][0] = ldu4h(wh, chunk_off + (t * 2 + 0) * 256, tl.l[u]);
-    s.p[u][1] = ldu4h(wh, chunk_off + (t * 2 + 1) * 256, tl.l[u]);
+    s.p[u][0] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(wh.r, tl.vo[u], chunk_off * 4, GAUDI_NODE_LOAD_AUX));
+    s.p[u][1] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(wh.r, tl.vo[u] + 1024, chunk_off * 4, GAUDI_NODE_LOAD_AUX));
   }
 }
 // How many chunks travel ahead of a call: kAheadAll = as many as the depth (where the next GEMM follows directly), kAheadOne =
@@ -257,7 +260,7 @@ __device__ __forceinline__ void node_prefetch_h(NodePFH<HP>& pf, const WBuf& wh,
   const TileLanesH<HP> tl(wave, lane);
   static_for<nd>([&](auto d_tag) {
     constexpr int d = decltype(d_tag)::value;
-    nh_load<HP>(pf.s[d], wh, 2 * W + d * nh_chunk_floats(HP), wave, tl);
+    nh_load<HP>(pf.s[d], wh, 2 * W + d * nh_chunk_floats(HP), tl);
   });
 }
 
@@ -301,7 +304,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
   // chunks that did not travel ahead of the call
   static_for<D>([&](auto d_tag) {
     constexpr int d = decltype(d_tag)::value;
-    if constexpr (d >= kIn) nh_load<HP>(pf.s[d], wh, 2 * Wa + d * nh_chunk_floats(HP), wave, tl);
+    if constexpr (d >= kIn) nh_load<HP>(pf.s[d], wh, 2 * Wa + d * nh_chunk_floats(HP), tl);
   });
   // tail weights (odd tile counts): k-step q of the wave's tiles; steps past the first are loaded only when they hold weights
   float ta[NTW][4], tb[NTW][4];
@@ -311,7 +314,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
       const int t = wave + kWaves * u < T ? wave + kWaves * u : 0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int ln = (q == 0 || !cx.ktail) ? tl.l[u] : kOOBLane;
+        const int ln = ((q == 0 || !cx.ktail) && wave + kWaves * u < T) ? lane : kOOBLane;
         ta[u][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wh.r, ln * 4, (2 * Wa + nh_tail_off(HP) + t * 256 + q * 64) * 4, 0));
         if constexpr (TWO)
           tb[u][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wh.r, ln * 4, (2 * Wb + nh_tail_off(HP) + t * 256 + q * 64) * 4, 0));
@@ -411,9 +414,9 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!(kAblateH & 4)) {
-        if constexpr (i + D < nc) nh_load<HP>(pf.s[d], wh, 2 * Wcur + (i + D) * nh_chunk_floats(HP), wave, tl);
-        else if constexpr (!last_src) nh_load<HP>(pf.s[d], wh, 2 * Wb + d * nh_chunk_floats(HP), wave, tl);
-        else if constexpr (d < kOut - kLate) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), wave, tl_next);
+        if constexpr (i + D < nc) nh_load<HP>(pf.s[d], wh, 2 * Wcur + (i + D) * nh_chunk_floats(HP), tl);
+        else if constexpr (!last_src) nh_load<HP>(pf.s[d], wh, 2 * Wb + d * nh_chunk_floats(HP), tl);
+        else if constexpr (d < kOut - kLate) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       }
       __builtin_amdgcn_sched_barrier(0);
       bcur = bnext;
@@ -424,7 +427,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
     constexpr int d = decltype(d_tag)::value;
     if constexpr (d >= kOut - kLate && d < kOut) {
       __builtin_amdgcn_sched_barrier(0);
-      if (!(kAblateH & 4)) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), wave, tl_next);
+      if (!(kAblateH & 4)) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       __builtin_amdgcn_sched_barrier(0);
     }
   };

@@ -176,33 +176,46 @@ __device__ __forceinline__ bool trip_group(const RingS<HP, MODE>& r, int W, int 
   asm volatile("" : "+s"(units));
   return !(nxt && nextW < 0);
 }
+// units U .. UT-1 of a wave's run: one descriptor, one vector offset (the lane's 16 bytes), one scalar offset (the run's first unit)
+// and one LDS base; unit U at immediate offset U * kBytes, which the instruction adds to BOTH addresses
+template <int U, int UT, int kBytes>
+__device__ __forceinline__ void dma_units(const WBuf& wb, int soff_bytes, int lane, float* l, int count) {
+  if constexpr (U < UT) {
+    if (U < count)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wb.r, (__attribute__((address_space(3))) void*)l, 16, lane * 16, soff_bytes, U * kBytes, 0);
+    dma_units<U + 1, UT, kBytes>(wb, soff_bytes, lane, l, count);
+  }
+}
 // LDS-DMA: unit un of the group goes straight to slot + un KiB (wave-uniform LDS base + 16 B per lane)
 template <int HP, int MODE>
-__device__ __forceinline__ bool rings_dma(const RingS<HP, MODE>& r, float* slot, int W, int nextW, int tr, int wave, int lane) {
+__device__ __forceinline__ bool rings_dma(const RingS<HP, MODE>& r, const WBuf& wb, float* slot, int W, int nextW, int tr, int wave, int lane) {
   using G = SplitGeo<HP, MODE>;
   int off, units;
   if (!trip_group(r, W, nextW, tr, off, units)) return false;
-#pragma unroll
-  for (int u = 0; u < G::UT; ++u) {
-    const int un = wave + kWaves * u;
-    if (un < units)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(r.gbase + off + un * G::kUnit + lane * 4),
-                                       (__attribute__((address_space(3))) void*)(slot + un * G::kUnit), 16, 0, 0);
-  }
+  // Wave w takes the CONSECUTIVE units [w units / 8, (w + 1) units / 8) -- three or four of 26, never more than UT: one LDS base
+  // (M0) per trip, the further units through the instruction's immediate offset, which applies to both addresses (DESIGN section
+  // 7 item 26: what the loader wave does).  Dealt round-robin (w, w + 8, ...) the units of a wave lay 8 KiB apart, beyond the 4 KiB
+  // immediate: an address, an M0 write and the idle slot behind it per unit.  Unit un lands at slot + un KiB either way.
+  // The loads go through the split buffer's descriptor (wb: the buffer r.gbase points to) -- `buffer_load_dwordx4 ... lds`, the
+  // same LDS-DMA path as global_load_lds with 32-bit offsets: the group's offset is ONE scalar
+  // addition per trip where the flat form built a 64-bit address per lane.
+  static_assert(G::UT * G::kUnit * 4 <= 4096, "a wave's units must lie within the immediate offset of its first");
+  const int first = (unsigned)(wave * units) / kWaves, count = (unsigned)((wave + 1) * units) / kWaves - first;
+  dma_units<0, G::UT, G::kUnit * 4>(wb, (off + first * G::kUnit) * 4, lane, slot + first * G::kUnit, count);
   return true;
 }
 template <int HP, int MODE>
-__device__ __forceinline__ void rings_start(RingS<HP, MODE>& r, const WBuf&, int W, int wave, int lane) {
-  rings_dma(r, r.slot(r.par), W, -1, 0, wave, lane);
+__device__ __forceinline__ void rings_start(RingS<HP, MODE>& r, const WBuf& wb, int W, int wave, int lane) {
+  rings_dma(r, wb, r.slot(r.par), W, -1, 0, wave, lane);
 }
 // trip tr has passed its opening barrier: nobody reads slot(par ^ 1) any more; the group of trip tr + 1 must have landed
 // at the next barrier (trip_barrier waits vmcnt(0))
 template <int HP, int MODE>
-__device__ __forceinline__ void rings_stage(RingS<HP, MODE>& r, const WBuf&, int W, int nextW, int tr, int wave, int lane) {
-  rings_dma(r, r.slot(r.par ^ 1), W, nextW, tr + 1, wave, lane);
+__device__ __forceinline__ void rings_stage(RingS<HP, MODE>& r, const WBuf& wb, int W, int nextW, int tr, int wave, int lane) {
+  rings_dma(r, wb, r.slot(r.par ^ 1), W, nextW, tr + 1, wave, lane);
 }
 
-// The barrier that opens a trip.  With LDS-DMA the group this trip reads was written by global_load_lds instructions of ALL
+// The barrier that opens a trip.  With LDS-DMA the group this trip reads was written by the LDS-DMA loads (rings_dma) of ALL
 // waves: each wave retires its own (vmcnt) before the barrier -- hipcc does not track these loads for the __syncthreads
 // fence on every path (seen in the ISA: barriers with lgkmcnt(0) only, and a run-to-run difference in the results).
 __device__ __forceinline__ void trip_barrier() {
