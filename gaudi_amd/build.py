@@ -13,14 +13,17 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libgaudi_hip.so")
-HEADERS = ["device_common.h", "edm_device.h", "pred_device.h", "sampler_kernel.h", "w8_common.h", "w8_split.h", "w8_nodes_f16.h", "w8_edm.h", "w8_pred.h", "pred_host.inc", "stability.inc", "nll_host.inc",
-           "pred_train.h", "pred_train_host.inc", "train_device.h", "edm_train.h", "edm_train_host.inc",
-           os.path.join("..", "..", "include", "gaudi_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize"]
 
 
 def _sources():
     return ["gaudi_hip.hip"] + sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "kern*_*.hip")))
+
+
+def _headers():
+    """What every translation unit may include: a header missing from a hand-kept list means silently stale objects."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [
+        os.path.join(PKG, "..", "include", "gaudi_hip.h")]
 
 
 def _stale(target: str, deps) -> bool:
@@ -43,7 +46,7 @@ def csrc_digest() -> str:
 
 
 def needs_build() -> bool:
-    deps = [os.path.join(CSRC, f) for f in _sources() + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in _sources()] + _headers()
     return _stale(LIB, deps)
 
 
@@ -52,7 +55,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
+    hdrs = _headers()
     todo = []
     objs = []
     for src in _sources():

@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "../../include/gaudi_hip.h"
-#include "sampler_kernel.h"
+#include "kernel_table.h"
 
 using namespace gaudi;
 
@@ -66,6 +66,28 @@ struct PinBuf {
   T* as() const { return (T*)p; }
 };
 
+// Where a launch keeps its node buffers ([node slots][HP + 4] floats each); the values are what gaudi_node_buffers reports
+enum NodeBuf : int {
+  kResident = 0,         // all in LDS
+  kAllGlobal = 1,        // all in the workgroup's global scratch (4 waves: V4G; 8 waves: V8G, round 4)
+  kPqLds = 2,            // V8G with P and Q in LDS (round 6, kern8gp_*.hip)
+  kPredFifthGlobal = 3,  // resident but the predictor's fifth buffer: wide groups on the FULL ring (round 6, kern8mp_*.hip)
+};
+// What the CURRENT call runs on: decided by stage_graph, read by launch, the fill_* functions, run_chain and the getters
+struct LaunchPlan {
+  int waves = 4;             // kernel family (an 8-wave handle falls back to 4 waves for graphs that do not fit)
+  int ring = 0;              // 8 waves: 1 = split operands on the full weight ring, 2 = on the half ring, 0 = fp32 instructions
+  bool mr = false;           // 8 waves: the predictor takes several rounds of edge tiles
+  NodeBuf nodes = kResident;
+  bool two = false;          // guided steps are two launches (denoiser-only kernel, then predictor-only kernel): no fused instantiation
+  bool fr = false;           // 8 waves: launches on the resident full-ring kernel take its FR instantiation where one exists
+  int ef = 2;                // edge features of the denoiser's first Linears (24: a sin_embedding denoiser, 4-wave family only)
+  int groups = 0;            // workgroups (= molecules unless packed)
+  int nslots = 0;            // node slots per workgroup (= N unless the call runs wide groups)
+  int hk = 0;                // floats of the kept split copy of h behind the LDS plan (0: none)
+  int pubx = 0, pub_ch = 0;  // reverse pass: extra floats of the du publish buffer, feature tiles published per chunk (plan_pub8)
+};
+
 struct gaudi_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -100,13 +122,9 @@ struct gaudi_handle {
   hipEvent_t cb_event = nullptr;
   int steps_per_launch = 25;
   int variant = 8;            // 8 = two waves per SIMD (sampler_kernel8, default), 4 = one wave per SIMD (GAUDI_WAVES=4)
-  int run_variant = 4;        // what the CURRENT call runs on (an 8-wave handle falls back to 4 waves for graphs that do not fit)
+  LaunchPlan plan;            // what the CURRENT call runs on
   bool split = true;          // 8-wave kernels: GEMMs on the fp16 matrix pipe with operands split into fp16 pairs (GAUDI_EDGE_MATH=fp32: off)
-  int run_split = 0;          // ... and how the CURRENT call uses them: 1 = full weight ring, 2 = half ring, 0 = fp32 instructions
-  bool run_gn = false;        // the CURRENT call runs on the 4-wave kernels with node buffers in global memory (large molecules)
-  bool run_two = false;       // ... and its guided steps are two launches (denoiser-only kernel, then predictor-only kernel): no fused instantiation
-  int run_gn8 = 0;            // ... on the 8-wave kernels with node buffers in global memory (V8G, round 4): 1 all five, 2 P / Q in LDS
-  bool run_pg = false;        // ... a wide-group launch on the FULL ring with the predictor's fifth node buffer in the global scratch (kern8mp_*.hip)
+  bool no_fr = false;         // GAUDI_NO_FR=1: never the FR instantiation of the resident full-ring kernel (kern8s2_*.hip)
   bool wide_full = true;      // GAUDI_WIDE_FULL=0: wide groups that do not fit the full ring run on the half ring (round 5)
   bool gn8_pq = true;         // GAUDI_GN8_PQ=0: never the P / Q-in-LDS form (kern8gp_*.hip)
   bool gn8 = true;            // GAUDI_GN8=0: molecules beyond the LDS limit go to the 4-wave V4G kernels, as in round 3
@@ -118,12 +136,9 @@ struct gaudi_handle {
                               // classic packing shares next to nothing (default since round 5: the fp16-pair node GEMMs made the
                               // shared weight stream worth the second round), 2 = always (GAUDI_PAIRS)
   int num_cus = 256;
-  int run_nslots = 0;         // node slots per workgroup of the current call (= N unless the call runs wide groups)
   bool pred_rounds = true;    // GAUDI_PRED_ROUNDS=0: guided calls with more than 128 edge slots go to the 4-wave kernels
   bool pack_now = false;      // set by run_chain around stage_graph: this call may pack
-  int run_groups = 0;         // workgroups of the CURRENT call (= molecules unless packed)
   bool force_mr = false;      // GAUDI_FORCE_MR
-  bool run_mr = false;        // the current call runs the 8-wave kernels whose predictor takes several rounds of edge tiles
   bool force_gn = false;      // GAUDI_FORCE_GN=1 at gaudi_create: use them whenever they exist (test knob)
   bool fix_noise = false;     // en_diffusion.py:562-566: one raw draw per call, broadcast over the batch
   long long fix_key = 0;      // global sample index whose Philox stream is shared
@@ -145,7 +160,6 @@ struct gaudi_handle {
   int call_narrow = 0;
   const int32_t* call_molmap = nullptr;
   bool keep_h = true;         // GAUDI_KEEP_H=0: every node GEMM that reads h splits it again (round 5)
-  int run_hk = 0;             // floats of the kept split copy of h behind the current call's LDS plan (0: none)
   bool gn8_pack = true;       // GAUDI_GN8_PACK=0: V8G launches keep a molecule's nodes where the masks have them (round 5)
   bool family_split = false;  // GAUDI_FAMILY_SPLIT=1: per-molecule kernel family (below).  Off by default: the two buckets run as two launches
                               // per 25 steps on one stream, each with its own tail -- c4x 76.8 against 84.3 mol/s in one family
@@ -762,208 +776,89 @@ static int build_meta8(int B, int N, const float* node_mask, const float* edge_m
 }
 
 // -------------------------------------------------------------------------------------------------
-// kernel table: the instantiations live in kern_*.hip (compiled in parallel), each exporting a lookup
-typedef void (*kernel_fn)(const KParams);
-#ifdef GAUDI_STAMP_STUBS  // diagnostic build: only the two production kernels are linked
-#define GAUDI_KERNEL_TUS(X) X(edm_192) X(fused_192_208)
-#else
-#define GAUDI_KERNEL_TUS(X)                                                                            \
-  X(edm_small) X(edm_192) X(edm_208) X(edm_256) X(pred_small) X(pred_192) X(pred_208) X(pred_256)      \
-  X(fused_tiny) X(fused_128_128) X(fused_192_192) X(fused_192_208) X(fused_208_208) X(fused_256_256)
-#endif
-#define X(name) kernel_fn gaudi_kern_##name(int hpe, int hpp);
-GAUDI_KERNEL_TUS(X)
-#undef X
+// kernel table: the instantiations live in kern*_*.hip (compiled in parallel); each registers its entries here at load time
+// (kernel_table.h).  A build that links fewer of them (tools/build_stamped.sh, tools/build_variant.sh) finds fewer kernels.
+KernelTable* gaudi::g_kernel_tables;
 
-static kernel_fn pick_kernel(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern_##name(hpe, hpp);
-  GAUDI_KERNEL_TUS(X)
-#undef X
-  return f;
+static kernel_fn find_kernel(const KernelKey& k) {
+  for (const KernelTable* t = g_kernel_tables; t; t = t->next)
+    for (int i = 0; i < t->n; ++i)
+      if (t->entries[i].key == k) return t->entries[i].fn;
+  return nullptr;
 }
-
-// the 4-wave kernels with node buffers in global memory (kerng_*.hip): molecules beyond the LDS limit
-#ifdef GAUDI_STAMP_STUBS
-static kernel_fn pick_kernel_g(int, int) { return nullptr; }
-static bool have_kernels_g(int, int) { return false; }
-#else
-kernel_fn gaudi_kerng_edm(int hpe, int hpp);
-kernel_fn gaudi_kerng_pred(int hpe, int hpp);
-// there is no fused (EDM + predictor) V4G instantiation: at the default widths it sits on the register cliff (512 registers,
-// 1120 spilled scalars) and faulted; a guided step of a large molecule is two launches, EDM-only then predictor-only
-static kernel_fn pick_kernel_g(int hpe, int hpp) {
-  kernel_fn f = gaudi_kerng_edm(hpe, hpp);
-  if (!f) f = gaudi_kerng_pred(hpe, hpp);
-  return f;
+static std::string key_name(const KernelKey& k) {
+  char buf[160];
+  snprintf(buf, sizeof buf, "waves=%d SP=%d MR=%d GN=%d FR=%d PG=%d EF=%d HPE=%d HPP=%d VT=%d", k.waves, k.sp, (int)k.mr, k.gn, (int)k.fr,
+           (int)k.pg, k.ef, k.hpe, k.hpp, (int)k.vt);
+  return buf;
 }
-static bool have_kernels_g(int hpe, int hpp) {
-  return (!hpe || pick_kernel_g(hpe, 0)) && (!hpp || pick_kernel_g(0, hpp));
+// two translation units registering one key is a build mistake: the first such key by name, or "" (gaudi_create)
+static std::string duplicate_kernel_key() {
+  std::vector<KernelKey> seen;
+  for (const KernelTable* t = g_kernel_tables; t; t = t->next)
+    for (int i = 0; i < t->n; ++i) {
+      if (std::find(seen.begin(), seen.end(), t->entries[i].key) != seen.end()) return key_name(t->entries[i].key);
+      seen.push_back(t->entries[i].key);
+    }
+  return "";
 }
-#endif
-
-// the 4-wave kernels of sin_embedding denoisers (kernse_*.hip: 24 edge features instead of 2, edm_device.h); the predictor-only
-// launches of such a handle (no sin_embedding there) take the ordinary kernels
-#ifdef GAUDI_STAMP_STUBS
-static kernel_fn pick_kernel_se(int, int, bool) { return nullptr; }
-#else
-kernel_fn gaudi_kernse_edm(int hpe, int hpp, int gn);
-kernel_fn gaudi_kernse_edm_more(int hpe, int hpp, int gn);
-kernel_fn gaudi_kernse_fused(int hpe, int hpp, int gn);
-static kernel_fn pick_kernel_se(int hpe, int hpp, bool gn) {
-  kernel_fn f = gaudi_kernse_edm(hpe, hpp, gn);
-  if (!f) f = gaudi_kernse_edm_more(hpe, hpp, gn);
-  if (!f) f = gaudi_kernse_fused(hpe, hpp, gn);
-  return f;
+// the template argument GN of a residency (sampler_kernel.h: V4T / V8T)
+static int gn_of(NodeBuf nodes) { return nodes == kAllGlobal ? 1 : nodes == kPqLds ? 2 : 0; }
+// 4-wave kernels: node buffers resident or in global memory (V4G: molecules beyond the LDS limit), ef = 24 for a sin_embedding
+// denoiser.  There is no fused (EDM + predictor) V4G instantiation: at the default widths it sits on the register cliff (512
+// registers, 1120 spilled scalars) and faulted; a guided step of a large molecule is two launches, EDM-only then predictor-only
+static KernelKey key4(int hpe, int hpp, bool gn = false, int ef = 2) {
+  KernelKey k{};  // (fields by name: a reordered KernelKey must not change what is looked up)
+  k.waves = 4;
+  k.gn = gn ? 1 : 0;
+  k.ef = ef;
+  k.hpe = hpe;
+  k.hpp = hpp;
+  return k;
 }
-#endif
-
-// the 8-wave instantiations (kern8_*.hip)
-#ifdef GAUDI_STAMP_STUBS
-#define GAUDI_KERNEL8_TUS(X) X(edm_192) X(fused_192_208)
-#else
-#define GAUDI_KERNEL8_TUS(X)                                                                           \
-  X(edm_small) X(edm_192) X(edm_208) X(edm_256) X(pred_small) X(pred_192) X(pred_208) X(pred_256)      \
-  X(fused_tiny) X(fused_128_128) X(fused_192_192) X(fused_192_208) X(fused_208_208) X(fused_256_256)
-#endif
-#define X(name) kernel_fn gaudi_kern8_##name(int hpe, int hpp);
-GAUDI_KERNEL8_TUS(X)
-#undef X
-static kernel_fn pick_kernel8(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8_##name(hpe, hpp);
-  GAUDI_KERNEL8_TUS(X)
-#undef X
-  return f;
+// 8-wave kernels: ring = 0 fp32 instructions, 1 / 2 split operands (fp16 pairs) on the full / half weight ring; mr: the call holds a
+// graph of more than one round of edge tiles AND runs the predictor; V8G (kAllGlobal, kPqLds) and the wide-group kernel on the full
+// ring (kPredFifthGlobal) exist as ring = 1, mr = true only
+static KernelKey key8(int hpe, int hpp, int ring, bool mr, NodeBuf nodes = kResident) {
+  KernelKey k{};
+  k.waves = 8;
+  k.sp = ring;
+  k.mr = mr;
+  k.gn = gn_of(nodes);
+  k.pg = nodes == kPredFifthGlobal;
+  k.ef = 2;
+  k.hpe = hpe;
+  k.hpp = hpp;
+  return k;
 }
-
-// ... and their split-operand (fp16 pairs) versions (kern8s_*.hip); a size without one runs on the fp32-MFMA kernel
-#ifdef GAUDI_STAMP_STUBS
-#define GAUDI_KERNEL8S_TUS(X) X(edm_192) X(fused_192_208)
-#else
-#define GAUDI_KERNEL8S_TUS(X) X(edm_small) X(edm_192) X(pred_small) X(pred_208) X(fused_tiny) X(fused_192_208)
-#endif
-#define X(name) kernel_fn gaudi_kern8s_##name(int hpe, int hpp);
-GAUDI_KERNEL8S_TUS(X)
-#undef X
-static kernel_fn pick_kernel8s(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8s_##name(hpe, hpp);
-  GAUDI_KERNEL8S_TUS(X)
-#undef X
-  return f;
+static bool have_kernel8(int hpe, int hpp, int ring, bool mr, NodeBuf nodes = kResident) {
+  return find_kernel(key8(hpe, hpp, ring, mr, nodes)) != nullptr;
 }
-
-// ... the same kernel with FR set (kern8s2_*.hip: sampler_kernel.h, V8T): taken for more than 16 node slots where it exists
-#ifdef GAUDI_STAMP_STUBS
-#define GAUDI_KERNEL8S2_TUS(X)
-#else
-#define GAUDI_KERNEL8S2_TUS(X) X(edm_192) X(fused_tiny) X(fused_192_208)
-#endif
-#define X(name) kernel_fn gaudi_kern8s2_##name(int hpe, int hpp);
-GAUDI_KERNEL8S2_TUS(X)
-#undef X
-static kernel_fn pick_kernel8s2(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8s2_##name(hpe, hpp);
-  GAUDI_KERNEL8S2_TUS(X)
-#undef X
-  (void)hpe; (void)hpp;
-  return f;
+// node buffers of ONE launch of a call: the wide-group form is the fused kernel's; the call's other launches are resident
+static NodeBuf launch_nodes(const LaunchPlan& p, int hpe, int hpp) {
+  return p.nodes == kPredFifthGlobal && !(hpe && hpp) ? kResident : p.nodes;
 }
-
-// ... and with the half-size ring (kern8h_*.hip): larger molecules
-#ifdef GAUDI_STAMP_STUBS
-#define GAUDI_KERNEL8H_TUS(X) X(fused_192_208)
-#else
-#define GAUDI_KERNEL8H_TUS(X) X(edm_192) X(fused_tiny) X(fused_192_208)
-#endif
-#define X(name) kernel_fn gaudi_kern8h_##name(int hpe, int hpp);
-GAUDI_KERNEL8H_TUS(X)
-#undef X
-static kernel_fn pick_kernel8h(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8h_##name(hpe, hpp);
-  GAUDI_KERNEL8H_TUS(X)
-#undef X
-  return f;
-}
-// ... and the kernels whose predictor runs several rounds of edge tiles (kern8m_*.hip: graphs of more than 128 slots)
-#if defined(GAUDI_STAMP_STUBS) && !defined(GAUDI_STAMP_M)
-static kernel_fn pick_kernel8m(int, int, int) { return nullptr; }
-#else
-#ifdef GAUDI_STAMP_STUBS  // tools/build_stamped.sh m: the fused MR half-ring kernel (what wide groups run) with phase stamps
-#define GAUDI_KERNEL8M_TUS(X) X(fused_192_208_h)
-#else
-#define GAUDI_KERNEL8M_TUS(X) \
-  X(fused_192_208_s) X(fused_192_208_h) X(fused_192_208_f) X(pred_208_s) X(pred_208_h) X(pred_208_f) X(fused_tiny) X(pred_small)
-#endif
-#define X(name) kernel_fn gaudi_kern8m_##name(int hpe, int hpp, int mode);
-GAUDI_KERNEL8M_TUS(X)
-#undef X
-static kernel_fn pick_kernel8m(int hpe, int hpp, int mode) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8m_##name(hpe, hpp, mode);
-  GAUDI_KERNEL8M_TUS(X)
-#undef X
-  return f;
-}
-#endif
-// ... and the 8-wave kernels with the node buffers in global memory (kern8g_*.hip: V8G)
-#if defined(GAUDI_STAMP_STUBS) && !defined(GAUDI_STAMP_G)
-static kernel_fn pick_kernel8g(int, int) { return nullptr; }
-#else
-#ifdef GAUDI_STAMP_STUBS  // tools/build_stamped.sh g: the fused V8G kernel with phase stamps
-#define GAUDI_KERNEL8G_TUS(X) X(fused_192_208)
-#else
-#define GAUDI_KERNEL8G_TUS(X) X(fused_192_208) X(edm_192) X(pred_208) X(fused_tiny) X(edm_small) X(pred_small)
-#endif
-#define X(name) kernel_fn gaudi_kern8g_##name(int hpe, int hpp);
-GAUDI_KERNEL8G_TUS(X)
-#undef X
-static kernel_fn pick_kernel8g(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8g_##name(hpe, hpp);
-  GAUDI_KERNEL8G_TUS(X)
-#undef X
-  return f;
-}
-#endif
-// ... of which P and Q stay in LDS (kern8gp_*.hip, round 6)
-#ifdef GAUDI_STAMP_STUBS
-static kernel_fn pick_kernel8gp(int, int) { return nullptr; }
-#else
-#define GAUDI_KERNEL8GP_TUS(X) X(fused_192_208) X(edm_192) X(pred_208) X(tiny)
-#define X(name) kernel_fn gaudi_kern8gp_##name(int hpe, int hpp);
-GAUDI_KERNEL8GP_TUS(X)
-#undef X
-static kernel_fn pick_kernel8gp(int hpe, int hpp) {
-  kernel_fn f = nullptr;
-#define X(name) \
-  if (!f) f = gaudi_kern8gp_##name(hpe, hpp);
-  GAUDI_KERNEL8GP_TUS(X)
-#undef X
-  return f;
-}
-#endif
-// ... and the wide-group kernels on the full ring (kern8mp_fused.hip, round 6)
-#ifdef GAUDI_STAMP_STUBS
-static kernel_fn pick_kernel8mp(int, int) { return nullptr; }
-#else
-kernel_fn gaudi_kern8mp_fused(int hpe, int hpp);
-static kernel_fn pick_kernel8mp(int hpe, int hpp) { return gaudi_kern8mp_fused(hpe, hpp); }
-#endif
-// mr: the call holds a graph of more than one round of edge tiles AND runs the predictor
-static kernel_fn pick_kernel8_mode(int hpe, int hpp, int mode, bool mr = false) {
-  if (mr) return pick_kernel8m(hpe, hpp, mode);
-  return mode == 1 ? pick_kernel8s(hpe, hpp) : mode == 2 ? pick_kernel8h(hpe, hpp) : pick_kernel8(hpe, hpp);
+// The kernel of a launch of the networks (hpe, hpp) under a plan.  MR applies to launches that run the predictor; a value-target
+// launch (vt) runs the VT instantiation of its kernel, which exists for launches with a predictor; the predictor-only launches of
+// a sin_embedding handle (no sin_embedding there) take the ordinary kernels.
+static kernel_fn plan_kernel(const LaunchPlan& p, int hpe, int hpp, bool vt) {
+  if (p.waves != 8) {
+    KernelKey k = key4(hpe, hpp, p.nodes == kAllGlobal, hpe ? p.ef : 2);
+    k.vt = vt && hpp;
+    return find_kernel(k);
+  }
+  const NodeBuf nodes = launch_nodes(p, hpe, hpp);
+  const bool mr = p.mr && hpp;
+  KernelKey k = nodes == kResident ? key8(hpe, hpp, p.ring, mr) : key8(hpe, hpp, 1, true, nodes);
+  k.vt = vt && hpp;
+  // two column tiles per node GEMM on the resident full-ring kernel: its FR instantiation (same arithmetic, same results).
+  // (a kPredFifthGlobal plan is an mr plan: its fused launch never comes here)
+  if (p.fr && nodes == kResident && !mr) {
+    k.fr = true;
+    if (kernel_fn f = find_kernel(k)) return f;
+    k.fr = false;
+  }
+  return find_kernel(k);
 }
 
 // smallest instantiated padded hidden size >= H (0 if none)
@@ -992,12 +887,12 @@ static size_t gnode_floats(int hpe, int hpp, int N) {
   return std::max((size_t)(hpe ? 4 * N * (hpe + 4) : 0), (size_t)(hpp ? 5 * N * (hpp + 4) : 0));
 }
 
-// gn: 0 resident, 1 the five node buffers in global memory, 2 of which P / Q in LDS (w8_edm.h: gn_lds_buffers); 3 (round 6: wide
-// groups on the full ring) the resident kernels with the PREDICTOR's fifth node buffer in global memory (w8_pred.h: PredSmem, PG)
-static size_t lds_floats8_base(int hpe, int hpp, int N, int D, int S, int split, int gn = 0) {
+// nodes: kAllGlobal / kPqLds keep w8_edm.h: gn_lds_buffers node buffers in LDS; kPredFifthGlobal is the resident plan with four
+// predictor buffers (w8_pred.h: PredSmem, PG)
+static size_t lds_floats8_base(int hpe, int hpp, int N, int D, int S, int split, NodeBuf nodes = kResident) {
   size_t net = 0;
-  const int pbuf = gn == 3 ? 4 : 5;
-  if (gn == 3) gn = 0;
+  const int pbuf = nodes == kPredFifthGlobal ? 4 : 5;
+  const int gn = gn_of(nodes);
   if (hpe) net = std::max(net, (size_t)((gn ? w8::gn_lds_buffers(gn) : 5) * N * (hpe + 4) + w8::edge_ring_floats(hpe, split) + 8 * N + 2 * align4(N) + 96 + S * 9 + 8 * hpe));
   if (hpp) net = std::max(net, (size_t)(w8::edge_ring_floats(hpp, split) + (gn ? w8::gn_lds_buffers(gn) : pbuf) * N * (hpp + 4) + 12 * N + 2 * align4(N) + 96 + S * 10 + 32 + 10 * hpp));
   return common_floats8(N, D, S) + net;
@@ -1015,21 +910,21 @@ static bool gn8_stage_fits(int hpe, int hpp, int N) {
 // largest pub_ch that fits 160 KiB, then the extra floats that choice needs.  false: the molecule does not fit.
 // fp16-pair node GEMMs (every split-operand kernel): the split copy of ONE GEMM input must fit the region the kernels use -- the
 // ring's free slot (full ring), the whole ring where it idles across node phases (half ring, gn) -- for N node columns
-static bool node_f16_fits(int hp, int N, int split, bool gn) {
+static bool node_f16_fits(int hp, int N, int split, NodeBuf nodes) {
+  const bool gn = gn_of(nodes) != 0;
   if (!hp || !split || !GAUDI_NODE_F16) return true;
   if (N > (gn ? 48 : 32)) return false;  // column tiles of one pass: three in the gn kernels, two in the resident ones
   const int nct = N <= 16 ? 1 : N <= 32 ? 2 : 3;
   const int ring = w8::edge_ring_floats(hp, split);
   return w8::nh_split_floats(hp, nct) <= (w8::node_ring_idle(hp, split, gn) ? ring : ring / 2);
 }
-static bool plan_pub8(int hpe, int hpp, int N, int D, int S, int split, int& pubx, int& pub_ch, int gn = 0) {
+static bool plan_pub8(int hpe, int hpp, int N, int D, int S, int split, int& pubx, int& pub_ch, NodeBuf nodes = kResident) {
   pubx = 0;
   pub_ch = 0;
-  const int gn_lds = gn;  // (3: the resident kernels' planning with four predictor buffers in LDS)
-  if (gn == 3) gn = 0;
-  if (!node_f16_fits(hpe, N, split, gn != 0) || !node_f16_fits(hpp, N, split, gn != 0)) return false;
+  const int gn = gn_of(nodes);  // (kPredFifthGlobal: the resident kernels' planning with four predictor buffers in LDS)
+  if (!node_f16_fits(hpe, N, split, nodes) || !node_f16_fits(hpp, N, split, nodes)) return false;
   const long long cap = 160 * 1024 / 4 - 64;  // floats (a little headroom for the runtime's own static LDS)
-  const long long base = (long long)lds_floats8_base(hpe, hpp, N, D, S, split, gn_lds);
+  const long long base = (long long)lds_floats8_base(hpe, hpp, N, D, S, split, nodes);
   if (base > cap) return false;
   if (!hpp) return true;
   const int T = hpp / 16;
@@ -1044,28 +939,22 @@ static bool plan_pub8(int hpe, int hpp, int N, int D, int S, int split, int& pub
   pubx = (int)std::max(0LL, (long long)S * (16 * pub_ch + 4) - own);
   return true;
 }
-static size_t lds_bytes8(int hpe, int hpp, int N, int D, int S, int pubx, int split, int gn = 0) {
-  return sizeof(float) * (lds_floats8_base(hpe, hpp, N, D, S, split, gn) + (hpp ? pubx : 0));
+static size_t lds_bytes8(int hpe, int hpp, int N, int D, int S, int pubx, int split, NodeBuf nodes = kResident) {
+  return sizeof(float) * (lds_floats8_base(hpe, hpp, N, D, S, split, nodes) + (hpp ? pubx : 0));
 }
 
-static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp_, long long steps) {
-  const bool v8 = h->run_variant == 8;
-  // a value-target launch (KParams::vt) runs the VT instantiation of its kernel; every other launch the one it always ran
-  const int hpp = hpp_, hpp_k = P.vt != nullptr && hpp_ ? (hpp_ | kVtKernel) : hpp_;
-  const bool se = hpe && h->ecfg.sin_embedding;  // stage_graph keeps such a call on the 4-wave family
-  kernel_fn fn = v8   ? (h->run_pg && hpe && hpp ? pick_kernel8mp(hpe, hpp_k) : h->run_gn8 == 2 ? pick_kernel8gp(hpe, hpp_k) : h->run_gn8 ? pick_kernel8g(hpe, hpp_k) : pick_kernel8_mode(hpe, hpp_k, h->run_split, h->run_mr && hpp))
-                 : se ? pick_kernel_se(hpe, hpp_k, h->run_gn)
-                      : h->run_gn ? pick_kernel_g(hpe, hpp_k) : pick_kernel(hpe, hpp_k);
-  // two column tiles per node GEMM on the resident full-ring kernel: its FR instantiation (same arithmetic, same results)
-  if (v8 && !h->run_gn8 && h->run_split == 1 && !(h->run_mr && hpp) && P.N > 16 && !getenv("GAUDI_NO_FR"))
-    if (kernel_fn f2 = pick_kernel8s2(hpe, hpp_k)) fn = f2;
+static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long steps) {
+  const LaunchPlan& plan = h->plan;
+  const bool v8 = plan.waves == 8;
+  const bool se = hpe && plan.ef > 2;  // stage_graph keeps such a call on the 4-wave family
+  const kernel_fn fn = plan_kernel(plan, hpe, hpp, P.vt != nullptr);
   if (!fn)
     return fail(h, GAUDI_E_INVALID,
                 "no kernel instantiated for padded hidden sizes (" + std::to_string(hpe) + "," + std::to_string(hpp) + ")" +
                     (v8 ? " in the 8-wave family" : se ? " among the sin_embedding kernels" : ""));
-  size_t lds = v8 ? lds_bytes8(hpe, hpp, P.N, 3 + P.F, P.EW, P.pubx, h->run_split, h->run_pg && hpe && hpp ? 3 : h->run_gn8)
-                  : lds_bytes(hpe, hpp, P.N, 3 + P.F, P.EW, h->run_gn, se ? 24 : 2);
-  if (v8 && P.hk_off) lds = sizeof(float) * ((size_t)P.hk_off + (size_t)h->run_hk);  // the kept split copy of h sits behind the FUSED plan
+  size_t lds = v8 ? lds_bytes8(hpe, hpp, P.N, 3 + P.F, P.EW, P.pubx, plan.ring, launch_nodes(plan, hpe, hpp))
+                  : lds_bytes(hpe, hpp, P.N, 3 + P.F, P.EW, plan.nodes == kAllGlobal, se ? 24 : 2);
+  if (v8 && P.hk_off) lds = sizeof(float) * ((size_t)P.hk_off + (size_t)plan.hk);  // the kept split copy of h sits behind the FUSED plan
   if (lds > 160 * 1024)
     return fail(h, GAUDI_E_CAPACITY, "molecule needs " + std::to_string(lds) + " B of LDS (>160 KiB): N too large");
   {
@@ -1220,8 +1109,9 @@ static void pack_groups(int B, int N, const float* node_mask, const float* edge_
 
 // upload masks + metadata, fill the graph part of KParams
 // -> GAUDI_OK, or a positive value = "run this call on the 4-wave kernels" (graph outside the 8-wave kernels' limits)
+// plan: written once, at the end (a fall-back or an error leaves it as it came)
 static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, KParams& P, int hpe,
-                        int hpp) {
+                        int hpp, LaunchPlan& plan) {
   if (std::max(h->plan_force_waves, h->call_force_waves) == 4) return 1;  // the whole logical batch runs on 4 waves
   Meta8 M;
   std::string err;
@@ -1238,25 +1128,29 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   // waves).  A molecule keeps its own tiles (component starts are tile-aligned), its nodes keep their relative order, its
   // noise is keyed by its own sample and node indices, and every per-molecule reduction runs per component in the order
   // the molecule's own workgroup would use: the result does not depend on the packing, bit for bit.
-  if (!pick_kernel8_mode(hpe, hpp, 0, mr) && !pick_kernel8_mode(hpe, hpp, 1, mr) && !pick_kernel8_mode(hpe, hpp, 2, mr)) return 1;
+  if (!have_kernel8(hpe, hpp, 0, mr) && !have_kernel8(hpe, hpp, 1, mr) && !have_kernel8(hpe, hpp, 2, mr)) return 1;
   const int Dz = 3 + (hpe ? h->ecfg.in_node_nf : h->pcfg.in_nf);
-  int pubx = 0, pub_ch = 0;
   // the arithmetic of the edge GEMMs for S edge slots on NS node slots: split operands when the kernel exists and its larger weight
   // ring fits (1 = full ring, 2 = half ring); else fp32 MFMAs (0); else -1 = this call runs on 4 waves
   // the split-operand kernels run their node GEMMs on fp16 pairs: a weight set whose images were refused (NodeScale) keeps the
   // fp32-instruction kernels
   const bool node_f16_ok = !GAUDI_NODE_F16 || ((!hpe || h->edm_hinv > 0.f) && (!hpp || h->pred_hinv > 0.f));
-  auto plan_for = [&](int NS, int S, bool mrk) -> int {
+  struct RingPlan {
+    int mode = -1, pubx = 0, pub_ch = 0;
+  };
+  auto plan_for = [&](int NS, int S, bool mrk) -> RingPlan {
+    RingPlan r;
     if (h->split && (!hpe || h->edm_ws_bytes) && (!hpp || h->pred_ws_bytes) && node_f16_ok)
       for (int mode = 1; mode <= 2; ++mode)
-        if (pick_kernel8_mode(hpe, hpp, mode, mrk) && plan_pub8(hpe, hpp, NS, Dz, S, mode, pubx, pub_ch)) return mode;
-    return pick_kernel8_mode(hpe, hpp, 0, mrk) && plan_pub8(hpe, hpp, NS, Dz, S, 0, pubx, pub_ch) ? 0 : -1;
+        if (have_kernel8(hpe, hpp, mode, mrk) && plan_pub8(hpe, hpp, NS, Dz, S, mode, r.pubx, r.pub_ch)) return RingPlan{mode, r.pubx, r.pub_ch};
+    return have_kernel8(hpe, hpp, 0, mrk) && plan_pub8(hpe, hpp, NS, Dz, S, 0, r.pubx, r.pub_ch) ? RingPlan{0, r.pubx, r.pub_ch} : RingPlan{};
   };
-  int mode_u = plan_for(N, M.S, mr);
+  RingPlan acc = plan_for(N, M.S, mr);  // the accepted plan: the unpacked resident one until a later stage replaces it
+  int mode_u = acc.mode;
   Pack pk;
   const int B0 = B;
   const float* nm_used = node_mask;
-  int n_slots = N, mode_run = mode_u;
+  int n_slots = N;
   bool mr_run = mr;
   bool narrow_taken = false, use_pack = false, pg_run = false;
   // Round 6: a bucket of molecules that fit the resident kernels on their own (gaudi_sample: per-molecule kernel family) while the
@@ -1267,13 +1161,14 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
     rc = build_meta8(pk.G, h->call_narrow, pk.umask.data(), pk.uemask.data(), M2, err, 0, pk.align.data());
     if (rc != GAUDI_OK) return fail(h, rc, "per-molecule kernel family: " + err);
     const bool mr2 = hpp && M2.S > 16 * w8::kWaves;
-    const int mode2 = plan_for(h->call_narrow, M2.S, mr2);
-    if (mode2 < 1 || mr2) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the resident plan of the small bucket does not fit");
+    const RingPlan p2 = plan_for(h->call_narrow, M2.S, mr2);
+    if (p2.mode < 1 || mr2) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the resident plan of the small bucket does not fit");
     M = std::move(M2);
     B = pk.G;
     nm_used = pk.umask.data();
     n_slots = h->call_narrow;
-    mode_run = mode_u = mode2;
+    acc = p2;
+    mode_u = p2.mode;
     mr_run = mr2;
     narrow_taken = use_pack = true;
   }
@@ -1282,19 +1177,18 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   // such calls fell to the 4-wave V4G kernels (fp32 matrix instructions, two launches per guided step)
   // Round 6: of the five, P and Q stay in LDS where that plan fits (kern8gp_*.hip; +3.6 % on 40-node molecules) -- a function of
   // the widths, N and the edge slots the plan is made with (the whole batch's: call_min_slots / plan_min_slots), like the rest
-  int gn8 = 0;
+  NodeBuf gn8 = kResident;
+  RingPlan gplan{1, 0, 0};
   if (!narrow_taken && (mode_u < 0 || h->force_gn8) && h->gn8 && h->split && (!hpe || h->edm_ws_bytes) && (!hpp || h->pred_ws_bytes) && node_f16_ok &&
       (GAUDI_NODE_F16 || gn8_stage_fits(hpe, hpp, N))) {
-    if (h->gn8_pq && GAUDI_NODE_F16 && pick_kernel8gp(hpe, hpp) && plan_pub8(hpe, hpp, N, Dz, M.S, 1, pubx, pub_ch, 2)) gn8 = 2;
-    else if (pick_kernel8g(hpe, hpp) && plan_pub8(hpe, hpp, N, Dz, M.S, 1, pubx, pub_ch, 1)) gn8 = 1;
+    if (h->gn8_pq && GAUDI_NODE_F16 && have_kernel8(hpe, hpp, 1, true, kPqLds) && plan_pub8(hpe, hpp, N, Dz, M.S, 1, gplan.pubx, gplan.pub_ch, kPqLds)) gn8 = kPqLds;
+    else if (have_kernel8(hpe, hpp, 1, true, kAllGlobal) && plan_pub8(hpe, hpp, N, Dz, M.S, 1, gplan.pubx, gplan.pub_ch, kAllGlobal)) gn8 = kAllGlobal;
   }
   if (gn8) {
+    acc = gplan;
     mode_u = 1;
-  } else if (h->force_gn8 && mode_u >= 0) {
-    plan_for(N, M.S, mr);  // (restore pubx / pub_ch of the resident plan)
   }
   if (mode_u < 0) return 1;
-  if (!narrow_taken) mode_run = mode_u;
   // V8G sampling calls (round 6): every molecule alone in its workgroup as before, but its nodes COMPACTED to the front slots
   // (a hetero molecule's rings and orientation nodes are two blocks of the padded index range: n rings occupy columns up to
   // N / 2 + n) -- fewer node-GEMM column tiles; the packed form also carries the molecule's index in the request (call_molmap).
@@ -1307,8 +1201,8 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
       M = std::move(M2);
       B = pk.G;
       nm_used = pk.umask.data();
-      pubx = pubx2;
-      pub_ch = pub_ch2;
+      acc.pubx = pubx2;
+      acc.pub_ch = pub_ch2;
       use_pack = true;
     } else {
       if (h->call_molmap) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the packed V8G plan does not fit");
@@ -1382,7 +1276,6 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
         cands.push_back({ng, 2 * w8::kWaves});
       }
     cands.push_back({N, w8::kWaves});
-    bool taken = false;
     for (const Cand& cd : cands) {
       const bool wide = cd.NG > N;
       pack_groups(B, N, node_mask, edge_mask, M, pk, cd.NG, cd.TG, false, kMaxComp, nullptr, wide ? max_multi : INT_MAX);
@@ -1396,41 +1289,34 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
       // a packed launch has more edge slots per workgroup; it must keep the ARITHMETIC the unpacked plan has -- split operands
       // (full or half ring: the same sums in the same order) or fp32 instructions -- because the plan of a sharded batch is the
       // same on every rank (gaudi_set_plan_hint) and packing must not move a rank off it
-      int mode2 = plan_for(cd.NG, M2.S, mr2);
-      if (mode2 < 0 || (mode2 != 0) != (mode_u != 0)) continue;
+      RingPlan p2 = plan_for(cd.NG, M2.S, mr2);
+      if (p2.mode < 0 || (p2.mode != 0) != (mode_u != 0)) continue;
       // Round 6: a wide group that fits the HALF ring only (two cata-11 molecules at the default widths: five predictor buffers of 22
       // node slots + the 52 KiB ring are 171 KB) runs on the FULL ring with the predictor's fifth node buffer in the workgroup's global
       // scratch (kern8mp_fused.hip) -- the same sums in the same order, one trip per K chunk instead of two
-      pg_run = false;
-      if (wide && mode2 == 2 && mr2 && h->wide_full && hpe && hpp && pick_kernel8mp(hpe, hpp)) {
-        if (plan_pub8(hpe, hpp, cd.NG, Dz, M2.S, 1, pubx, pub_ch, 3)) {
-          mode2 = 1;
-          pg_run = true;
-        } else {
-          plan_for(cd.NG, M2.S, mr2);  // (restore pubx / pub_ch of the half-ring plan)
-        }
+      RingPlan full{1, 0, 0};
+      if (wide && p2.mode == 2 && mr2 && h->wide_full && hpe && hpp && have_kernel8(hpe, hpp, 1, true, kPredFifthGlobal) &&
+          plan_pub8(hpe, hpp, cd.NG, Dz, M2.S, 1, full.pubx, full.pub_ch, kPredFifthGlobal)) {
+        p2 = full;
+        pg_run = true;
       }
       M = std::move(M2);
       B = pk.G;
       nm_used = pk.umask.data();
       n_slots = cd.NG;
-      mode_run = mode2;
+      acc = p2;
       mr_run = mr2;
-      taken = use_pack = true;
+      use_pack = true;
       break;
-    }
-    if (!taken) {
-      pg_run = false;
-      plan_for(N, M.S, mr);  // keep the unpacked plan (pubx / pub_ch)
     }
   }
   const bool packed = use_pack;
-  h->run_split = mode_run;
-  P.pubx = pubx;
-  P.pub_ch = pub_ch;
+  const NodeBuf nodes = pg_run ? kPredFifthGlobal : gn8;
+  P.pubx = acc.pubx;
+  P.pub_ch = acc.pub_ch;
   if (getenv("GAUDI_DEBUG_PLAN"))
-    fprintf(stderr, "[plan] molecules=%d workgroups=%d N=%d node slots=%d S=%d split=%d mr=%d pub_ch=%d pubx=%d lds=%zu\n", B0, B, N, n_slots,
-            M.S, h->run_split, gn8 ? 2 : pg_run ? 3 : (int)mr_run, pub_ch, pubx, lds_bytes8(hpe, hpp, n_slots, Dz, M.S, pubx, h->run_split, pg_run ? 3 : gn8));
+    fprintf(stderr, "[plan] molecules=%d workgroups=%d N=%d node slots=%d S=%d split=%d mr=%d nodes=%d pub_ch=%d pubx=%d lds=%zu\n", B0, B, N,
+            n_slots, M.S, acc.mode, (int)mr_run, (int)nodes, acc.pub_ch, acc.pubx, lds_bytes8(hpe, hpp, n_slots, Dz, M.S, acc.pubx, acc.mode, nodes));
   auto up = [&](DevBuf& d, const void* src, size_t bytes) -> hipError_t {
     hipError_t e = d.reserve(bytes);
     if (e != hipSuccess) return e;
@@ -1467,22 +1353,17 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   P.rowmap = packed ? h->d_rowmap.as<int32_t>() : nullptr;
   P.compmol = packed ? h->d_compmol.as<int32_t>() : nullptr;
   P.ncomp = packed ? h->d_ncomp.as<int32_t>() : nullptr;
-  h->run_groups = B;
-  h->run_nslots = n_slots;
-  h->run_mr = mr_run;
-  h->run_gn8 = gn8;
-  h->run_pg = pg_run;
   // Kept split copy of h (w8_nodes_f16.h: node_ctx_keep): behind everything the plan of BOTH networks needs, when 160 KiB leave the
   // room -- C2 / C3 do (46 KB free), 20-22 node slots do not.  Same results either way (the copy is a function of h alone).
   P.hk_off = 0;
-  h->run_hk = 0;
-  if (h->keep_h && GAUDI_NODE_F16 && mode_run >= 1 && !gn8 && !pg_run) {
-    const size_t plan = lds_bytes8(hpe, hpp, n_slots, Dz, M.S, pubx, mode_run, false) / sizeof(float);
-    const size_t at = (plan + 3) & ~(size_t)3;
+  int hk = 0;
+  if (h->keep_h && GAUDI_NODE_F16 && acc.mode >= 1 && nodes == kResident) {
+    const size_t floats = lds_bytes8(hpe, hpp, n_slots, Dz, M.S, acc.pubx, acc.mode) / sizeof(float);
+    const size_t at = (floats + 3) & ~(size_t)3;
     const size_t need = (size_t)w8::nh_keep_floats(std::max(hpe, hpp), n_slots);
     if ((at + need) * sizeof(float) + 1024 <= 160 * 1024) {
       P.hk_off = (int)at;
-      h->run_hk = (int)need;
+      hk = (int)need;
     }
   }
   if (pg_run) {  // one [node slots][hpp + 4] buffer per workgroup
@@ -1497,6 +1378,17 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
     P.gnode = h->d_gnode.as<float>();
     P.gnode_stride = (long long)stride;
   }
+  plan.waves = 8;
+  plan.ring = acc.mode;
+  plan.mr = mr_run;
+  plan.nodes = nodes;
+  // (the FR instantiation: launches on the resident full-ring kernel with two column tiles per node GEMM, launch / plan_kernel)
+  plan.fr = !h->no_fr && gn8 == kResident && acc.mode == 1 && n_slots > 16;
+  plan.groups = B;
+  plan.nslots = n_slots;
+  plan.hk = hk;
+  plan.pubx = acc.pubx;
+  plan.pub_ch = acc.pub_ch;
   return GAUDI_OK;
 }
 
@@ -1506,25 +1398,17 @@ static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, co
   if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
   // a node slot's row word holds molecule * N + node in 28 bits (sampler_kernel.h: row_of / comp_of)
   if ((int64_t)B * N >= (1 << 28)) return fail(h, GAUDI_E_CAPACITY, "B * N must stay below 2^28 per call: cut the request into several calls");
-  h->run_variant = h->variant;
-  h->run_split = 0;
-  h->run_gn = false;
-  h->run_two = false;
-  h->run_gn8 = 0;
-  h->run_pg = false;
-  h->run_mr = false;
-  h->run_groups = B;
-  h->run_nslots = N;
+  LaunchPlan plan;  // (assigned to the handle where this function succeeds: a failed call leaves the last call's plan)
   // a sin_embedding denoiser (24 edge features per first Linear, egnn_new.py:269-273) exists in the 4-wave family only
   const bool se = hpe && h->ecfg.sin_embedding;
   if (h->variant == 8 && !h->force_gn && !se) {
-    const int rc8 = stage_graph8(h, B, N, node_mask, edge_mask, P, hpe, hpp);
+    const int rc8 = stage_graph8(h, B, N, node_mask, edge_mask, P, hpe, hpp, plan);
+    if (rc8 == GAUDI_OK) h->plan = plan;
     if (rc8 <= 0) return rc8;
-    h->run_variant = 4;  // fall back to the 4-wave kernels for this call
-    h->run_split = 0;
-    P.pubx = P.pub_ch = 0;
+    P.pubx = P.pub_ch = 0;  // fall back to the 4-wave kernels for this call
   }
-  h->run_variant = 4;
+  plan.groups = B;
+  plan.nslots = N;
   // the 4-wave reverse pass parks [4 waves][N * 3] partial coordinate gradients in its 4 x 16 x (HP + 4) transposition scratch
   if (hpp && 4 * N * 3 > 4 * 16 * (hpp + 4))
     return fail(h, GAUDI_E_CAPACITY, "N too large for the 4-wave predictor kernels at this hidden size");
@@ -1567,11 +1451,12 @@ static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, co
   // hetero batch of 18-20 nodes fits the resident kernels where the dense graph would not).
   const int Dz = 3 + (hpe ? h->ecfg.in_node_nf : h->pcfg.in_nf);
   const bool part_of_batch = h->plan_min_slots || h->plan_force_waves || h->call_min_slots || h->call_force_waves || h->call_cut;
-  const int ef = se ? 24 : 2;
-  const bool have_g = se ? (pick_kernel_se(hpe, 0, true) && (!hpp || pick_kernel_g(0, hpp))) : have_kernels_g(hpe, hpp);
+  const int ef = plan.ef = se ? 24 : 2;
+  // (the V4G predictor-only kernel is the ordinary one for a sin_embedding handle too)
+  const bool have_g = (!hpe || find_kernel(key4(hpe, 0, true, ef))) && (!hpp || find_kernel(key4(0, hpp, true)));
   if (h->force_gn || lds_bytes(hpe, hpp, N, Dz, part_of_batch ? std::max(M.EW, dense_ew4(N)) : M.EW, false, ef) > 160 * 1024) {
     if (have_g && lds_bytes(hpe, hpp, N, Dz, M.EW, true, ef) <= 160 * 1024) {
-      h->run_gn = true;
+      plan.nodes = kAllGlobal;
       const size_t stride = (gnode_floats(hpe, hpp, N) + 63) / 64 * 64;
       HIPCHECK(h, h->d_gnode.reserve(sizeof(float) * stride * (size_t)B));
       P.gnode = h->d_gnode.as<float>();
@@ -1580,7 +1465,8 @@ static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, co
   }
   // Guided steps as two launches: the V4G kernels have no fused instantiation, and a sin_embedding denoiser has one at the tiny and the
   // default width pairs only -- every other width runs its denoiser-only kernel followed by the ordinary predictor-only kernel
-  h->run_two = h->run_gn || (se && hpp && !pick_kernel_se(hpe, hpp, false));
+  plan.two = plan.nodes == kAllGlobal || (se && hpp && !find_kernel(key4(hpe, hpp, false, ef)));
+  h->plan = plan;
   return GAUDI_OK;
 }
 
@@ -1588,7 +1474,7 @@ static void fill_edm(gaudi_handle* h, KParams& P) {
   const gaudi_edm_config& c = h->ecfg;
   P.F = c.in_node_nf;
   P.T = c.diffusion_steps;
-  P.edm.w = (h->variant == 8 && h->run_variant == 4) ? h->edm_w4.as<float>() : h->edm_w.as<float>();
+  P.edm.w = (h->variant == 8 && h->plan.waves == 4) ? h->edm_w4.as<float>() : h->edm_w.as<float>();
   P.edm.w_bytes = (unsigned)h->edm_w_bytes;
   P.edm.F = c.in_node_nf;
   P.edm.L = c.n_layers;
@@ -1600,7 +1486,7 @@ static void fill_edm(gaudi_handle* h, KParams& P) {
   // aggregation_method 'mean' (normalization_factor = 0 in the config): unsorted_segment_sum divides by the number of edges of
   // the dense list that share the row, masked ones included (egnn_new.py:416-420) = the call's padded node count
   P.edm.normf = c.normalization_factor > 0.f ? c.normalization_factor : (float)P.NR;
-  P.edm.ktail = h->run_variant == 8 && has_ktail(c.hidden_nf, h->HPE);
+  P.edm.ktail = h->plan.waves == 8 && has_ktail(c.hidden_nf, h->HPE);
   P.edm.ws = h->edm_ws.as<float>();
   P.edm.ws_bytes = (unsigned)h->edm_ws_bytes;
   P.edm.hinv = h->edm_hinv;
@@ -1619,6 +1505,11 @@ extern "C" {
 int gaudi_create(int device, gaudi_handle** out) {
   if (!out) return GAUDI_E_INVALID;
   *out = nullptr;
+  static const std::string dup = duplicate_kernel_key();
+  if (!dup.empty()) {
+    fprintf(stderr, "libgaudi_hip: two translation units register the kernel %s\n", dup.c_str());
+    return GAUDI_E_INVALID;
+  }
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return GAUDI_E_HIP;
   gaudi_handle* h = new gaudi_handle();
@@ -1642,7 +1533,8 @@ int gaudi_create(int device, gaudi_handle** out) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->num_cus = cus;
   }
   if (const char* v = getenv("GAUDI_PRED_ROUNDS")) h->pred_rounds = atoi(v) != 0;
-  h->run_variant = h->variant;
+  h->no_fr = getenv("GAUDI_NO_FR") != nullptr;
+  h->plan.waves = h->variant;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return GAUDI_E_HIP;
@@ -1691,7 +1583,7 @@ int gaudi_profile_clock(gaudi_handle* h, double* shader_mhz) {
 }
 int gaudi_last_keep_h(const gaudi_handle* h, int32_t* lds_floats) {
   if (!h || !lds_floats) return GAUDI_E_INVALID;
-  *lds_floats = h->run_hk;
+  *lds_floats = h->plan.hk;
   return GAUDI_OK;
 }
 int gaudi_last_family_split(const gaudi_handle* h, int32_t* resident_molecules) {
@@ -2111,7 +2003,7 @@ static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, cons
   }
   float* zin = h->d_zin.as<float>();
   float* zout = h->d_zout.as<float>();
-  if (h->run_two && target_w) {
+  if (h->plan.two && target_w) {
     // Large molecules (V4G kernels) and sin_embedding denoisers without a fused kernel, guided: every reverse step is two launches -- the EDM-only kernel runs the step up to
     // z_s before guidance (split = 1: denoise, update with noise), the predictor-only kernel the guidance update, the
     // projection and the NaN scrub (MODE_GUIDE) -- then one decode pass.
@@ -2277,7 +2169,7 @@ static int resident_node_limit(gaudi_handle* h, int N, bool guided) {
   for (int ng = std::min(N - 1, 32); ng >= 8; --ng)
     for (int mode = 1; mode <= 2; ++mode) {
       int pubx = 0, pub_ch = 0;
-      if (pick_kernel8_mode(hpe, hpp, mode, false) && plan_pub8(hpe, hpp, ng, Dz, 16 * w8::kWaves, mode, pubx, pub_ch)) return ng;
+      if (have_kernel8(hpe, hpp, mode, false) && plan_pub8(hpe, hpp, ng, Dz, 16 * w8::kWaves, mode, pubx, pub_ch)) return ng;
     }
   return 0;
 }
@@ -2343,7 +2235,7 @@ static int sample_impl(gaudi_handle* h, int B, int N, const float* node_mask, co
       int pubx = 0, pub_ch = 0;
       bool fits = false;  // the unpacked resident plan of the whole call, any split mode
       for (int mode = 1; mode <= 2 && !fits; ++mode)
-        fits = pick_kernel8_mode(h->HPE, hpp, mode, hpp && M.S > 16 * w8::kWaves) && plan_pub8(h->HPE, hpp, N, D, M.S, mode, pubx, pub_ch);
+        fits = have_kernel8(h->HPE, hpp, mode, hpp && M.S > 16 * w8::kWaves) && plan_pub8(h->HPE, hpp, N, D, M.S, mode, pubx, pub_ch);
       if (!fits && (lim = resident_node_limit(h, N, target_w != nullptr)) > 0) {
         const std::vector<std::vector<int>> used = used_nodes(B, N, node_mask, edge_mask);
         for (int b = 0; b < B; ++b) ((int)used[b].size() <= lim && M.ntiles[b] <= w8::kWaves ? small : large).push_back(b);
@@ -2639,7 +2531,7 @@ static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask,
   // Large molecules (V4G kernels: node buffers in global memory) have no fused EDM + predictor instantiation (DESIGN.md
   // 7.12): phase A is the EDM-only kernel (split = 1: z_t -> z_s before guidance) followed by the predictor-only kernel's
   // forward half (MODE_GUIDE, split = 1), phase B the predictor-only kernel's second half (MODE_GUIDE, split = 2).
-  const bool gn = h->run_two;
+  const bool gn = h->plan.two;
   // GAUDI_DEBUG_CB: where a callback step's host time goes (enqueue / wait for pred / the caller's function)
   const bool dbg_cb = getenv("GAUDI_DEBUG_CB") != nullptr;
   double t_enq = 0, t_wait = 0, t_user = 0;
@@ -2927,28 +2819,27 @@ int gaudi_host_pack_plan_wide(int B, int N, int node_slots, int tiles, const flo
 int gaudi_kernel_variant(const gaudi_handle* h, int32_t* configured, int32_t* last_call) {
   if (!h) return GAUDI_E_INVALID;
   if (configured) *configured = h->variant;
-  if (last_call) *last_call = h->run_variant;
+  if (last_call) *last_call = h->plan.waves;
   return GAUDI_OK;
 }
 
 int gaudi_last_workgroups(const gaudi_handle* h, int32_t* workgroups, int32_t* node_slots) {
   if (!h || !workgroups) return GAUDI_E_INVALID;
-  *workgroups = h->run_groups;
-  if (node_slots) *node_slots = h->run_nslots;
+  *workgroups = h->plan.groups;
+  if (node_slots) *node_slots = h->plan.nslots;
   return GAUDI_OK;
 }
 
 int gaudi_node_buffers(const gaudi_handle* h, int32_t* last_call) {
   if (!h || !last_call) return GAUDI_E_INVALID;
-  // 0 resident, 1 global scratch, 2 global scratch with P / Q in LDS (8-wave kernels), 3 resident except the predictor's fifth buffer
-  *last_call = h->run_gn ? 1 : h->run_pg ? 3 : h->run_gn8;
+  *last_call = (int32_t)h->plan.nodes;
   return GAUDI_OK;
 }
 
 int gaudi_edge_math(const gaudi_handle* h, int32_t* configured, int32_t* last_call) {
   if (!h) return GAUDI_E_INVALID;
   if (configured) *configured = (h->variant == 8 && h->split) ? 1 : 0;
-  if (last_call) *last_call = h->run_split;
+  if (last_call) *last_call = h->plan.ring;
   return GAUDI_OK;
 }
 

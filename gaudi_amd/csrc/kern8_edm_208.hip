@@ -1,10 +1,11 @@
-// kern8_edm_208.hip -- sampler_kernel8 (8 waves, two per SIMD) instantiations [(208, 0)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8_edm_208).
-#include "sampler_kernel.h"
+// kern8_edm_208.hip -- sampler_kernel_v<V8, ...> (8 waves, two per SIMD) instantiations [(208, 0)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8_edm_208(int hpe, int hpp) {
-  if (hpe == 208 && hpp == 0) return gaudi::sampler_kernel8<208, 0>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8, 208, 0>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,13 +1,14 @@
-// kern8_edm_small.hip -- sampler_kernel8 (8 waves, two per SIMD) instantiations [(32, 0), (48, 0), (64, 0), (128, 0)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8_edm_small).
-#include "sampler_kernel.h"
+// kern8_edm_small.hip -- sampler_kernel_v<V8, ...> (8 waves, two per SIMD) instantiations [(32, 0), (48, 0), (64, 0), (128, 0)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8_edm_small(int hpe, int hpp) {
-  if (hpe == 32 && hpp == 0) return gaudi::sampler_kernel8<32, 0>;
-  if (hpe == 48 && hpp == 0) return gaudi::sampler_kernel8<48, 0>;
-  if (hpe == 64 && hpp == 0) return gaudi::sampler_kernel8<64, 0>;
-  if (hpe == 128 && hpp == 0) return gaudi::sampler_kernel8<128, 0>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8, 32, 0>(),
+    entry<V8, 48, 0>(),
+    entry<V8, 64, 0>(),
+    entry<V8, 128, 0>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

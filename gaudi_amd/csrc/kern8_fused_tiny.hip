@@ -1,15 +1,14 @@
-// kern8_fused_tiny.hip -- sampler_kernel8 (8 waves, two per SIMD) instantiations [(32, 48), (32, 32), (48, 48), (64, 64)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8_fused_tiny).
-#include "sampler_kernel.h"
+// kern8_fused_tiny.hip -- sampler_kernel_v<V8, ...> (8 waves, two per SIMD) instantiations [(32, 48), (32, 32), (48, 48), (64, 64)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8_fused_tiny(int hpe, int hpp) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 32 && hpp == 48) return vt ? gaudi::sampler_kernel8<32, 48, true> : gaudi::sampler_kernel8<32, 48>;
-  if (hpe == 32 && hpp == 32) return vt ? gaudi::sampler_kernel8<32, 32, true> : gaudi::sampler_kernel8<32, 32>;
-  if (hpe == 48 && hpp == 48) return vt ? gaudi::sampler_kernel8<48, 48, true> : gaudi::sampler_kernel8<48, 48>;
-  if (hpe == 64 && hpp == 64) return vt ? gaudi::sampler_kernel8<64, 64, true> : gaudi::sampler_kernel8<64, 64>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8, 32, 48, true>(), entry<V8, 32, 48>(),
+    entry<V8, 32, 32, true>(), entry<V8, 32, 32>(),
+    entry<V8, 48, 48, true>(), entry<V8, 48, 48>(),
+    entry<V8, 64, 64, true>(), entry<V8, 64, 64>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,12 +1,11 @@
-// kern8_pred_208.hip -- sampler_kernel8 (8 waves, two per SIMD) instantiations [(0, 208)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8_pred_208).
-#include "sampler_kernel.h"
+// kern8_pred_208.hip -- sampler_kernel_v<V8, ...> (8 waves, two per SIMD) instantiations [(0, 208)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8_pred_208(int hpe, int hpp) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 0 && hpp == 208) return vt ? gaudi::sampler_kernel8<0, 208, true> : gaudi::sampler_kernel8<0, 208>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8, 0, 208, true>(), entry<V8, 0, 208>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,15 +1,14 @@
-// kern8_pred_small.hip -- sampler_kernel8 (8 waves, two per SIMD) instantiations [(0, 32), (0, 48), (0, 64), (0, 128)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8_pred_small).
-#include "sampler_kernel.h"
+// kern8_pred_small.hip -- sampler_kernel_v<V8, ...> (8 waves, two per SIMD) instantiations [(0, 32), (0, 48), (0, 64), (0, 128)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8_pred_small(int hpe, int hpp) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 0 && hpp == 32) return vt ? gaudi::sampler_kernel8<0, 32, true> : gaudi::sampler_kernel8<0, 32>;
-  if (hpe == 0 && hpp == 48) return vt ? gaudi::sampler_kernel8<0, 48, true> : gaudi::sampler_kernel8<0, 48>;
-  if (hpe == 0 && hpp == 64) return vt ? gaudi::sampler_kernel8<0, 64, true> : gaudi::sampler_kernel8<0, 64>;
-  if (hpe == 0 && hpp == 128) return vt ? gaudi::sampler_kernel8<0, 128, true> : gaudi::sampler_kernel8<0, 128>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8, 0, 32, true>(), entry<V8, 0, 32>(),
+    entry<V8, 0, 48, true>(), entry<V8, 0, 48>(),
+    entry<V8, 0, 64, true>(), entry<V8, 0, 64>(),
+    entry<V8, 0, 128, true>(), entry<V8, 0, 128>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,14 +1,14 @@
 // kern8m_fused_192_208_s.hip -- 8-wave kernels whose predictor runs SEVERAL rounds of eight edge tiles (graphs of more than 128 live-edge slots:
-// fully connected molecules of 12+ nodes; w8_pred.h, template flag MR) [(192, 208), mode 1]; own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8m_fused_192_208_s.  mode: 0 = fp32 matrix instructions,
+// fully connected molecules of 12+ nodes; w8_pred.h, template flag MR) [(192, 208), SP = 1]; own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h).  SP: 0 = fp32 matrix instructions,
 // 1 / 2 = split operands with the full / half weight ring.
-#include "sampler_kernel.h"
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8m_fused_192_208_s(int hpe, int hpp, int mode) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 192 && hpp == 208 && mode == 1) return vt ? gaudi::sampler_kernel8m<1, 192, 208, true> : gaudi::sampler_kernel8m<1, 192, 208>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+using V = V8T<1, true>;
+const KernelEntry kEntries[] = {
+    entry<V, 192, 208, true>(), entry<V, 192, 208>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,10 +1,11 @@
-// kern8s_edm_192.hip -- sampler_kernel8s (8 waves, edge and node GEMMs on fp16-pair operands: w8_split.h, w8_nodes_f16.h) instantiations [(192, 0)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8s_edm_192).
-#include "sampler_kernel.h"
+// kern8s_edm_192.hip -- sampler_kernel_v<V8S, ...> (8 waves, edge and node GEMMs on fp16-pair operands: w8_split.h, w8_nodes_f16.h) instantiations [(192, 0)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8s_edm_192(int hpe, int hpp) {
-  if (hpe == 192 && hpp == 0) return gaudi::sampler_kernel8s<192, 0>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8S, 192, 0>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

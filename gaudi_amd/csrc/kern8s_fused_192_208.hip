@@ -1,12 +1,11 @@
-// kern8s_fused_192_208.hip -- sampler_kernel8s (8 waves, edge and node GEMMs on fp16-pair operands: w8_split.h, w8_nodes_f16.h) instantiations [(192, 208)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern8s_fused_192_208).
-#include "sampler_kernel.h"
+// kern8s_fused_192_208.hip -- sampler_kernel_v<V8S, ...> (8 waves, edge and node GEMMs on fp16-pair operands: w8_split.h, w8_nodes_f16.h) instantiations [(192, 208)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern8s_fused_192_208(int hpe, int hpp) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 192 && hpp == 208) return vt ? gaudi::sampler_kernel8s<192, 208, true> : gaudi::sampler_kernel8s<192, 208>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V8S, 192, 208, true>(), entry<V8S, 192, 208>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,10 +1,11 @@
-// kern_edm_192.hip -- sampler_kernel instantiations [(192, 0)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern_edm_192).
-#include "sampler_kernel.h"
+// kern_edm_192.hip -- sampler_kernel_v<V4, ...> instantiations [(192, 0)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern_edm_192(int hpe, int hpp) {
-  if (hpe == 192 && hpp == 0) return gaudi::sampler_kernel<192, 0>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V4, 192, 0>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

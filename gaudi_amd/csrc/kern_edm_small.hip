@@ -1,13 +1,14 @@
-// kern_edm_small.hip -- sampler_kernel instantiations [(32, 0), (48, 0), (64, 0), (128, 0)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern_edm_small).
-#include "sampler_kernel.h"
+// kern_edm_small.hip -- sampler_kernel_v<V4, ...> instantiations [(32, 0), (48, 0), (64, 0), (128, 0)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern_edm_small(int hpe, int hpp) {
-  if (hpe == 32 && hpp == 0) return gaudi::sampler_kernel<32, 0>;
-  if (hpe == 48 && hpp == 0) return gaudi::sampler_kernel<48, 0>;
-  if (hpe == 64 && hpp == 0) return gaudi::sampler_kernel<64, 0>;
-  if (hpe == 128 && hpp == 0) return gaudi::sampler_kernel<128, 0>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V4, 32, 0>(),
+    entry<V4, 48, 0>(),
+    entry<V4, 64, 0>(),
+    entry<V4, 128, 0>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -1,12 +1,11 @@
-// kern_pred_256.hip -- sampler_kernel instantiations [(0, 256)] (own translation unit so the
-// instantiations compile in parallel; looked up by gaudi_hip.hip through gaudi_kern_pred_256).
-#include "sampler_kernel.h"
+// kern_pred_256.hip -- sampler_kernel_v<V4, ...> instantiations [(0, 256)] (own translation unit so the
+// instantiations compile in parallel; registered in the kernel table (kernel_table.h)).
+#include "kernel_table.h"
 
-typedef void (*kernel_fn)(const gaudi::KParams);
-
-kernel_fn gaudi_kern_pred_256(int hpe, int hpp) {
-  const bool vt = (hpp & gaudi::kVtKernel) != 0;  // the value-target instantiation (sampler_kernel.h: VT)
-  hpp &= ~gaudi::kVtKernel;
-  if (hpe == 0 && hpp == 256) return vt ? gaudi::sampler_kernel<0, 256, true> : gaudi::sampler_kernel<0, 256>;
-  return nullptr;
-}
+namespace {
+using namespace gaudi;
+const KernelEntry kEntries[] = {
+    entry<V4, 0, 256, true>(), entry<V4, 0, 256>(),
+};
+KernelTable kTable(kEntries);
+}  // namespace

@@ -2,7 +2,7 @@
 
 static void fill_pred_common(gaudi_handle* h, KParams& P, int B, int N) {
   const gaudi_pred_config& c = h->pcfg;
-  P.pred.w = (h->variant == 8 && h->run_variant == 4) ? h->pred_w4.as<float>() : h->pred_w.as<float>();
+  P.pred.w = (h->variant == 8 && h->plan.waves == 4) ? h->pred_w4.as<float>() : h->pred_w.as<float>();
   P.pred.w_bytes = (unsigned)h->pred_w_bytes;
   P.pred.F = c.in_nf;
   P.pred.K = c.out_nf;
@@ -10,13 +10,13 @@ static void fill_pred_common(gaudi_handle* h, KParams& P, int B, int N) {
   P.pred.attention = c.attention;
   P.pred.use_tanh = c.tanh;
   P.pred.coords_range_layer = c.coords_range / (float)c.n_layers;
-  P.pred.ktail = h->run_variant == 8 && has_ktail(c.hidden_nf, h->HPP);
+  P.pred.ktail = h->plan.waves == 8 && has_ktail(c.hidden_nf, h->HPP);
   P.pred.ws = h->pred_ws.as<float>();
   P.pred.ws_bytes = (unsigned)h->pred_ws_bytes;
   P.pred.hinv = h->pred_hinv;
   // the stash is per WORKGROUP (P.B of them, P.N node slots each: more than a molecule's N in a wide-group launch); the
   // readout divides by the molecule's padded N (egnn_predictor/models.py:457)
-  P.stash_stride = h->run_variant == 8 ? w8::pred_stash_floats8(P.N, h->HPP, c.n_layers, P.EW)
+  P.stash_stride = h->plan.waves == 8 ? w8::pred_stash_floats8(P.N, h->HPP, c.n_layers, P.EW)
                                        : pred_stash_floats(P.N, h->HPP, c.n_layers, P.EW);
   P.readout_div = (float)(h->readout_n > 0 ? h->readout_n : N);
   (void)B;

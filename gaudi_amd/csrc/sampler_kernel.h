@@ -91,8 +91,6 @@ struct KParams {
   // workgroup, B = molecules.
   const struct VtDev* vt;
 };
-// flag in the hpp argument of the translation units' lookup functions (gaudi_kern*_*(hpe, hpp ...)): the VT instantiation
-constexpr int kVtKernel = 1 << 16;
 struct VtDev {                 // (in device memory)
   const float* par;            // [B][4 K + 1] per-molecule target parameters (device_common.h: target_seed)
   float* trace;                // [steps][B][K + 2] predictions at (z_s, t) | gradient 2-norm before the clip | clip coefficient, or nullptr
@@ -124,6 +122,9 @@ template <bool GN, int EF = 2>
 struct V4T {
   static constexpr int kThreads = gaudi::kThreads;
   static constexpr bool kGlobalNodes = GN;
+  // what the host's kernel table files an instantiation under (kernel_table.h: KernelKey); no device code reads these
+  static constexpr int kWaveCount = 4, kSplit = 0, kGN = GN ? 1 : 0, kEF = EF;
+  static constexpr bool kMR = false, kFR = false, kPG = false;
   using Graph = gaudi::MolGraph;
   template <int HP> using EdmSmem = gaudi::NetSmem<HP, GN, EF>;
   __device__ __forceinline__ static void set_rows(Graph&, const int*, int, int) {}  // the 4-wave kernels are never packed
@@ -349,6 +350,8 @@ struct V8T {
   static constexpr bool kFL = MR || GN != 0 || FR;
   static constexpr int kThreads = w8::kThreads;
   static constexpr int kSplit = SP;
+  static constexpr int kWaveCount = 8, kGN = GN, kEF = 2;  // (kernel_table.h: KernelKey, with kSplit; host only)
+  static constexpr bool kMR = MR, kFR = FR, kPG = PG;
   using Graph = w8::MolGraph;
   __host__ __device__ static int graph_floats(int N, int S) { return 2 * S + align16(N) + align16((N + 1 + S + 1) / 2); }
   __device__ __forceinline__ static float* load_graph(const KParams& P, int b, float* base, const float* sMask, Graph& mg, int tid, int wave) {
@@ -841,36 +844,5 @@ __global__ __launch_bounds__(V::kThreads) void sampler_kernel_v(const KParams P)
     }
   }
 }
-
-typedef void (*sampler_fn)(const KParams);
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel = &sampler_kernel_v<V4, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel_g = &sampler_kernel_v<V4G, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel_se = &sampler_kernel_v<V4S, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel_gse = &sampler_kernel_v<V4GS, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8 = &sampler_kernel_v<V8, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8s = &sampler_kernel_v<V8S, HPE, HPP, VT>;
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8s2 = &sampler_kernel_v<V8T<1, false, false, true>, HPE, HPP, VT>;  // (FR: kern8s2_*.hip)
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8h = &sampler_kernel_v<V8H, HPE, HPP, VT>;
-// ... whose predictor runs several rounds of edge tiles (kern8m_*.hip): SP = 0 / 1 / 2 as above
-template <int SP, int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8m = &sampler_kernel_v<V8T<SP, true>, HPE, HPP, VT>;
-// ... and with the node buffers in global memory (kern8g_*.hip: molecules beyond the LDS limit; split edge GEMMs, full ring,
-// several rounds of edge tiles in the predictor)
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8g = &sampler_kernel_v<V8T<1, true, 1>, HPE, HPP, VT>;
-// ... wide groups on the FULL ring: several rounds of edge tiles, the predictor's fifth node buffer in the global scratch (kern8mp_*.hip)
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8mp = &sampler_kernel_v<V8T<1, true, 0, false, true>, HPE, HPP, VT>;
-// ... of which P and Q stay in LDS (kern8gp_*.hip: taken where that plan fits)
-template <int HPE, int HPP, bool VT = false>
-inline constexpr sampler_fn sampler_kernel8gp = &sampler_kernel_v<V8T<1, true, 2>, HPE, HPP, VT>;
 
 }  // namespace gaudi

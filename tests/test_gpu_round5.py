@@ -219,7 +219,7 @@ def test_fr_instantiation_of_the_resident_kernel_is_bit_identical(monkeypatch, w
         res = [eng.sample(nm, em, return_z0=True, seed=9, sample_offset=4, target_w=w, scale=0.6),
                eng.sample(nm, em, return_z0=True, seed=9, sample_offset=4)]
         assert eng.kernel_variant()[1] == 8 and eng.edge_math()[1] == 1, (eng.kernel_variant(), eng.edge_math())  # resident, full ring
-        assert eng.last_launch_shape()[1] > 16  # (what selects the FR instantiation: gaudi_hip.hip, launch())
+        assert eng.last_launch_shape()[1] > 16  # (what selects the FR instantiation: gaudi_hip.hip, stage_graph8 / plan_kernel)
         rng = np.random.default_rng(5)
         z = O._combined_noise(rng.standard_normal((B, N, D)).astype(np.float32), nm[:, :, None])
         eps = rng.standard_normal((B, N, D)).astype(np.float32)

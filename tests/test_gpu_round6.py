@@ -183,6 +183,29 @@ def test_kept_split_copy_of_h_changes_nothing(widths):
     assert rel_err(outs[1][4], O.step_guided(esd, eargs, psd, pargs, gamma, 3, z, nm, em, eps, w, 0.6)) < 1e-4
 
 
+def test_keep_h_figure_follows_the_call_that_ran():
+    """The plan of a call is one value, replaced as a whole: a call that falls back to the 4-wave family after a resident 8-wave
+    call on the same handle reports its own plan in every getter -- no kept copy of h among them (the figure used to survive
+    from the earlier call)."""
+    from oracle import gaudi_oracle as O
+    from tests.helpers import TINY, TINY_P
+    eargs, pargs = synth.edm_args(diffusion_steps=7, **TINY), synth.pred_args(**TINY_P)
+    esd = synth.synth_edm_state_dict(eargs, 1, seed=13, amplify_coord=True)
+    psd = synth.synth_predictor_state_dict(pargs, 1, 5, seed=14, amplify_coord=True)
+    nm, em = O.build_masks([5, 7, 7, 3], 7, False)
+    w = O.target_max_gap_weights(5)
+    eng = _engine(eargs, esd, pargs, psd)
+    eng.sample(nm, em, seed=3, target_w=w, scale=0.6)
+    assert eng.kernel_variant()[1] == 8 and eng.keep_h() > 0, (eng.kernel_variant(), eng.keep_h())  # the precondition
+    eng.set_plan_hint(0, 4)
+    eng.sample(nm, em, seed=3, target_w=w, scale=0.6)
+    assert eng.kernel_variant()[1] == 4
+    assert eng.edge_math()[1] == 0
+    assert eng.node_buffers_form() == 0
+    assert eng.keep_h() == 0
+    eng.close()
+
+
 def test_half_ring_mode_is_reached_and_checked():
     """since the fp16-pair ring shrank to 52 KiB the half-ring mode (two trips per K chunk, SplitGeo<HP, 2>) is only
     reached where 22 node slots leave no room for the full ring -- wide groups (two 11-ring cata molecules per workgroup) -- and

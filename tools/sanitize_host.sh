@@ -16,8 +16,8 @@ SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=
 echo "== build (sanitizers on the host compilation: $SAN)"
 cd gaudi_amd/csrc
 pids=""
-for tu in gaudi_hip kern_edm_192 kern_fused_192_208 kern8_edm_192 kern8_fused_192_208 kern8s_edm_192 kern8s_fused_192_208 kern8h_fused_192_208; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -g -std=c++17 -fPIC -fno-slp-vectorize $SAN -DGAUDI_STAMP_STUBS -w -c $tu.hip -o $OBJ/$tu.o &
+for tu in gaudi_hip kern_edm_192 kern_fused_192_208 kern8_edm_192 kern8_fused_192_208 kern8s_edm_192 kern8s_fused_192_208 kern8h_fused_192_208 kernt_pred_train kernt_edm_train; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -g -std=c++17 -fPIC -fno-slp-vectorize $SAN -w -c $tu.hip -o $OBJ/$tu.o &
   pids="$pids $!"
 done
 for p in $pids; do wait $p; done
