@@ -45,8 +45,21 @@ class StabilityAux(C.Structure):
                 ("a3_min", C.c_float), ("a3_max", C.c_float), ("a4_min", C.c_float), ("a4_max", C.c_float)]
 
 
+class AtomTables(C.Structure):
+    """include/gaudi_hip.h: gaudi_atom_tables."""
+    _fields_ = [("n_types", C.c_int32), ("ring_size", C.c_int32 * 16), ("ring_elem", (C.c_int32 * 6) * 16),
+                ("templ", ((C.c_double * 2) * 6) * 16), ("no_orientation", C.c_int32 * 16), ("extra_angle", C.c_double * 16),
+                ("n_template_h", C.c_int32 * 16), ("template_h_parent", (C.c_int32 * 2) * 16), ("h_elem", C.c_int32),
+                ("c_elem", C.c_int32), ("h_bond", C.c_double)]
+
+
+ATOMS_MAX_ATOMS = 384  # include/gaudi_hip.h: GAUDI_ATOMS_MAX_ATOMS / GAUDI_ATOMS_MAX_BONDS
+ATOMS_MAX_BONDS = 384
+ATOMS_PLACE_H, ATOMS_FINGERPRINT = 1, 2
+
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
+DP = C.POINTER(C.c_double)
 
 
 class TargetSpec(C.Structure):
@@ -87,8 +100,12 @@ EXPORTS = {
     "gaudi_check_stability": (C.c_int, [C.c_void_p, C.POINTER(RingTables), C.c_int, C.c_int, FP, IP, IP,
                                         C.POINTER(C.c_uint8), FP, FP, C.POINTER(StabilityAux)]),
     "gaudi_stability_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_rings_to_atoms": (C.c_int, [C.c_void_p, C.POINTER(RingTables), C.POINTER(AtomTables), C.c_int, C.c_int, FP, IP, IP,
+                                       C.c_int, C.c_int, C.c_int, IP, IP, DP, DP, IP, IP, IP, C.POINTER(C.c_uint64)]),
+    "gaudi_atoms_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
+    "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
     "gaudi_host_graph_meta": (C.c_int, [C.c_int, C.c_int, FP, FP, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), FP, C.c_int32,
                                         C.POINTER(C.c_int32)]),
@@ -153,6 +170,7 @@ _NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_g
 # points (same ABI version: no existing signature changed)
 _GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")  # ... and the time-grid chains
 _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fused value targets
+_ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
 
 _lib = None
 
@@ -180,7 +198,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory

@@ -164,3 +164,31 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
                                        flags.ctypes.data_as(C.POINTER(C.c_uint8)), fptr(dist), fptr(adj), None)
     eng._check(rc, "gaudi_check_stability")
     return dist, adj
+
+
+def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None):
+    """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
+    molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
+
+    What differs from the reference, plainly: there is no RDKit here.  ``mol_built`` is the fraction for which gor2goa did not
+    raise -- NOT the reference's ``mol_valid`` (no sanitisation, no valence check) -- and molecules are told apart by the 64-bit
+    fingerprint of their heavy-atom graph, not by InChI: equal keys do not prove that two molecules are the same.
+
+    -> (dict, built_list): ``mol_built``; ``mol_unique`` = distinct keys / built molecules (0.0 when none was built);
+    ``molecule_built_bool``; ``fingerprints`` (one int per molecule, 0 where not built); ``mol_novel`` = built molecules whose
+    key is not in ``train_fingerprints`` / built molecules, only when ``train_fingerprints`` is given."""
+    from .gor2goa import rings_to_atoms
+    recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine)
+    if not recs:
+        raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
+    built =[r["status"] == 0 for r in recs]
+    keys = [r["fingerprint"] if ok else 0 for r, ok in zip(recs, built)]
+    built_keys = [k for k, ok in zip(keys, built) if ok]
+    n_built = len(built_keys)
+    d = {"mol_built": n_built / float(len(recs)),
+         "mol_unique": len(set(built_keys)) / float(n_built) if n_built else 0.0,
+         "molecule_built_bool": built, "fingerprints": keys}
+    if train_fingerprints is not None:
+        train = {int(k) for k in train_fingerprints}
+        d["mol_novel"] = sum(k not in train for k in built_keys) / float(n_built) if n_built else 0.0
+    return d, [m for m, ok in zip(molecule_list, built) if ok]

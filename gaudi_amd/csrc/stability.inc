@@ -74,6 +74,16 @@ __device__ __forceinline__ float norm3(V3 a) {
 }
 constexpr float kRad2Deg = 57.29577951308232f;
 
+// coord2distances / positions2adj (utils/helpers.py:165-196) for one ring pair: shared with atoms.inc, so that both kernels agree
+// bit for bit on which rings are fused
+__device__ __forceinline__ float ring_dist(const float* a, const float* b) {
+  const V3 d = sub3(a, b);
+  return sqrt_rn(add_rn(add_rn(mul_rn(d.x, d.x), mul_rn(d.y, d.y)), mul_rn(d.z, d.z)));
+}
+__device__ __forceinline__ bool ring_bonded(const StabTables& T, int ti, int tj, float dist) {
+  return T.hi[ti][tj] > 0.f && T.lo[ti][tj] < dist && dist < T.hi[ti][tj];
+}
+
 // analyze/analyze.py:234-240
 __device__ __forceinline__ float angle3(const StabSmem& s, int a, int c, int b) {
   const V3 v1 = sub3(s.x[a], s.x[c]), v2 = sub3(s.x[b], s.x[c]);
@@ -152,10 +162,9 @@ __global__ __launch_bounds__(256) void stability_kernel(const StabParams P, cons
     if (lane < nr) {
       const int ti = s.type[lane];
       for (int j = 0; j < nr; ++j) {
-        const V3 d = sub3(s.x[lane], s.x[j]);
-        const float dist = sqrt_rn(add_rn(add_rn(mul_rn(d.x, d.x), mul_rn(d.y, d.y)), mul_rn(d.z, d.z)));
+        const float dist = ring_dist(s.x[lane], s.x[j]);
         const int tj = s.type[j];
-        const bool bonded = j != lane && T.hi[ti][tj] > 0.f && T.lo[ti][tj] < dist && dist < T.hi[ti][tj];
+        const bool bonded = j != lane && ring_bonded(T, ti, tj, dist);
         row |= bonded ? (1u << j) : 0u;
         close |= j != lane && dist < T.min_thr;
         if (P.dist) P.dist[((size_t)b * N + lane) * N + j] = dist;
@@ -275,24 +284,8 @@ __global__ __launch_bounds__(256) void stability_kernel(const StabParams P, cons
 
 }  // namespace gaudi
 
-extern "C" int gaudi_check_stability(gaudi_handle* h, const gaudi_ring_tables* tb, int B, int N, const float* x,
-                                     const int32_t* ring_type, const int32_t* n_nodes, uint8_t* flags_out,
-                                     float* dist_out, float* adj_out, gaudi_stability_aux* aux_out) {
-  if (!h || !tb || !x || !ring_type || !n_nodes || !flags_out || B < 0 || N < 1) return GAUDI_E_INVALID;
-  if (tb->n_types < 1 || tb->n_types > gaudi::kStabMaxTypes) return fail(h, GAUDI_E_INVALID, "n_types must be in 1..16");
-  if (B == 0) return GAUDI_OK;
-  const int max_rings = gaudi::kStabMaxRings;
-  for (int b = 0; b < B; ++b) {
-    const int n = n_nodes[b];
-    if (n < 1 || n > N) return fail(h, GAUDI_E_INVALID, "n_nodes must be in 1..N (an empty molecule has no stability)");
-    if ((tb->orientation ? n / 2 : n) > max_rings) return fail(h, GAUDI_E_CAPACITY, "more than 32 rings in one molecule");
-    for (int i = 0; i < n; ++i) {
-      const int t = ring_type[(size_t)b * N + i];
-      if (t < 0 || t >= tb->n_types) return fail(h, GAUDI_E_INVALID, "ring type outside the table");
-    }
-  }
-  HIPCHECK(h, hipSetDevice(h->device));
-  gaudi::StabTables T{};
+// The device image of gaudi_ring_tables: `tol` applied as the reference does, then fp32 (shared with atoms.inc).
+static int stab_device_tables(gaudi_handle* h, const gaudi_ring_tables* tb, gaudi::StabTables& T) {
   const double tol = tb->tol;
   T.n_types = tb->n_types;
   T.orientation = tb->orientation;
@@ -313,6 +306,28 @@ extern "C" int gaudi_check_stability(gaudi_handle* h, const gaudi_ring_tables* t
   }
   T.a4_180_thr = (float)(tb->a4_180 * (1 - tol));
   T.a4_0_thr = (float)(tb->a4_0 * (1 + tol));
+  return GAUDI_OK;
+}
+
+extern "C" int gaudi_check_stability(gaudi_handle* h, const gaudi_ring_tables* tb, int B, int N, const float* x,
+                                     const int32_t* ring_type, const int32_t* n_nodes, uint8_t* flags_out,
+                                     float* dist_out, float* adj_out, gaudi_stability_aux* aux_out) {
+  if (!h || !tb || !x || !ring_type || !n_nodes || !flags_out || B < 0 || N < 1) return GAUDI_E_INVALID;
+  if (tb->n_types < 1 || tb->n_types > gaudi::kStabMaxTypes) return fail(h, GAUDI_E_INVALID, "n_types must be in 1..16");
+  if (B == 0) return GAUDI_OK;
+  const int max_rings = gaudi::kStabMaxRings;
+  for (int b = 0; b < B; ++b) {
+    const int n = n_nodes[b];
+    if (n < 1 || n > N) return fail(h, GAUDI_E_INVALID, "n_nodes must be in 1..N (an empty molecule has no stability)");
+    if ((tb->orientation ? n / 2 : n) > max_rings) return fail(h, GAUDI_E_CAPACITY, "more than 32 rings in one molecule");
+    for (int i = 0; i < n; ++i) {
+      const int t = ring_type[(size_t)b * N + i];
+      if (t < 0 || t >= tb->n_types) return fail(h, GAUDI_E_INVALID, "ring type outside the table");
+    }
+  }
+  HIPCHECK(h, hipSetDevice(h->device));
+  gaudi::StabTables T{};
+  if (int rc = stab_device_tables(h, tb, T)) return rc;
 
   const size_t xb = sizeof(float) * (size_t)B * N * 3, tbytes = sizeof(int) * (size_t)B * N, nn = (size_t)B * N * N;
   HIPCHECK(h, h->d_sx.reserve(xb));

@@ -724,6 +724,30 @@ class Engine:
         self._check(self.lib.gaudi_stability_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_stability_profile_get")
         return n.value, ms.value
 
+    def atoms_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_rings_to_atoms since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_atoms_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_atoms_profile_get")
+        return n.value, ms.value
+
+    def rings_to_atoms(self, tables, atom_tables, x, ring_type, n_nodes, flags, max_atoms, max_bonds):
+        """gaudi_rings_to_atoms on packed arrays (x [B,N,3] float32, ring_type [B,N] int32, n_nodes [B] int32) -> dict of the
+        raw output arrays; gaudi_amd.gor2goa.rings_to_atoms is the interface on top."""
+        B, N = x.shape[0], x.shape[1]
+        out = dict(n_atoms=np.zeros(B, np.int32), atom_type=np.zeros((B, max_atoms), np.int32),
+                   xy=np.zeros((B, max_atoms, 2), np.float64), xyz=np.zeros((B, max_atoms, 3), np.float64),
+                   n_bonds=np.zeros(B, np.int32), bonds=np.zeros((B, max_bonds, 2), np.int32), status=np.zeros(B, np.int32),
+                   fingerprint=np.zeros(B, np.uint64))
+        ip = lambda a: a.ctypes.data_as(_lib.IP)
+        dp = lambda a: a.ctypes.data_as(_lib.DP)
+        rc = self.lib.gaudi_rings_to_atoms(self.h, C.byref(tables), C.byref(atom_tables), B, N, fptr(x), ip(ring_type), ip(n_nodes),
+                                           int(flags), int(max_atoms), int(max_bonds), ip(out["n_atoms"]), ip(out["atom_type"]),
+                                           dp(out["xy"]), dp(out["xyz"]), ip(out["n_bonds"]), ip(out["bonds"]), ip(out["status"]),
+                                           out["fingerprint"].ctypes.data_as(C.POINTER(C.c_uint64)))
+        self._check(rc, "gaudi_rings_to_atoms")
+        return out
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

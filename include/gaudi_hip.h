@@ -83,6 +83,8 @@ const char* gaudi_last_error(const gaudi_handle* h);
 const char* gaudi_last_warning(const gaudi_handle* h);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3 -- change no existing
+ * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
 
@@ -361,6 +363,68 @@ int gaudi_check_stability(gaudi_handle* h, const gaudi_ring_tables* tables, int 
 /* Number of stability-kernel launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_stability_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Graph of rings -> graph of atoms: data/gor2goa.py:133-261 (gor2goa) for B molecules in one launch. ----
+ * Constants of the conversion for one dataset, indexed by ring-type index as gaudi_ring_tables: the 2-D ring templates
+ * (data/gor2goa.py:18-51), the elements of the ring atoms (RINGS_DICT, data/ring.py:6-18) as indices into ATOMS_LIST[dataset]
+ * (data/aromatic_dataloader.py:26-30), and the per-type rules written out in gor2goa's body. */
+#define GAUDI_ATOMS_MAX_ATOMS 384  /* 32 rings x (6 ring atoms + 2 template H + 4 placed H) */
+#define GAUDI_ATOMS_MAX_BONDS 384
+typedef struct {
+  int32_t n_types;                 /* as gaudi_ring_tables.n_types                                                   */
+  int32_t ring_size[16];           /* ring atoms of the type: 4, 5 or 6; 0 = not a ring (the orientation type ".")   */
+  int32_t ring_elem[16][6];        /* element of ring atom k, index into ATOMS_LIST[dataset]                         */
+  double templ[16][6][2];          /* template position of ring atom k around the ring centre (Angstrom)             */
+  int32_t no_orientation[16];      /* 1: NO_ORIENTATION_RINGS -- turned towards the lowest-index fused ring           */
+  double extra_angle[16];          /* added to that angle: pi/6 for Bn, pi/4 for Cbd (gor2goa.py:161-164)             */
+  int32_t n_template_h[16];        /* template H's of the type: Bl / Pl 1, DhDb 2 (gor2goa.py:189-198)                */
+  int32_t template_h_parent[16][2];/* ring atom each of them is bonded to                                             */
+  int32_t h_elem, c_elem;          /* ATOMS_LIST[dataset].index("H") / .index("C")                                   */
+  double h_bond;                   /* X-H distance of place_hydrogens (Angstrom); no reference counterpart           */
+} gaudi_atom_tables;
+
+#define GAUDI_ATOMS_PLACE_H 1      /* flags of gaudi_rings_to_atoms */
+#define GAUDI_ATOMS_FINGERPRINT 2
+/* status_out codes: 0 = built; otherwise the reference raises for this input and the molecule has n_atoms = n_bonds = 0. */
+#define GAUDI_ATOMS_BUILT 0
+#define GAUDI_ATOMS_NO_NEIGHBOUR 1 /* a NO_ORIENTATION ring without a fused ring in a multi-ring molecule (nonzero()[0, 0])      */
+#define GAUDI_ATOMS_BAD_TYPE 2     /* the orientation type "." or a type outside the table among the rings (KeyError / IndexError) */
+#define GAUDI_ATOMS_NO_RINGS 3     /* no ring at all: a lone orientation node (np.stack of an empty list)                          */
+#define GAUDI_ATOMS_OVERFLOW 4     /* NOT a reference error: more than max_atoms / max_bonds results, more than 96 fused pairs or
+                                      more than 256 atoms before hydrogens are placed                                              */
+
+/* x [B,N,3], ring_type [B,N], n_nodes [B] as gaudi_check_stability takes them (`tables` gives the fused pairs: the same
+ * positions2adj, bit for bit).  One 64-lane wave per molecule restates gor2goa in the reference's order of operations and
+ * ATOM ORDER (bonds are index pairs): align_to_xy_plane (inertia tensor about the origin over all nodes, "centre of mass" = sum / 3,
+ * eigenvectors of the symmetric 3 x 3 in ascending-eigenvalue order WITH THE SIGNS numpy.linalg.eigh returns -- the atom order
+ * depends on them, so the kernel restates LAPACK's dsyevd path for n = 3, see gaudi_host_eigh3), ring templates
+ * turned towards the orientation node or the lowest-index fused ring, template H's at the origin, per fused pair (np.triu order)
+ * the closest ring atom to the centre-to-centre segment on either side (the `> 0` / `< 0` masks, first minimum), merged into
+ * midpoint atoms appended at the end, originals deleted, bonds renumbered and de-duplicated.  Geometry in double.
+ * A hetero molecule with an odd node count is built as the reference builds it: n // 2 rings, node n // 2 + i orients ring i.
+ * Outputs, rows of max_atoms <= GAUDI_ATOMS_MAX_ATOMS / max_bonds <= GAUDI_ATOMS_MAX_BONDS entries per molecule:
+ *   n_atoms_out [B], atom_type_out [B][max_atoms] (index into ATOMS_LIST[dataset]);
+ *   xy_out [B][max_atoms][2]: the aligned frame, what the reference returns;
+ *   xyz_out [B][max_atoms][3]: the same points in the input frame, sum / 3 + E[:, :2] . xy;
+ *   n_bonds_out [B], bonds_out [B][max_bonds][2]: each pair i <= j, the list sorted; status_out [B];
+ *   fingerprint_out [B] (needed with GAUDI_ATOMS_FINGERPRINT, else may be NULL).
+ * GAUDI_ATOMS_PLACE_H: every template H moves from the origin to h_bond from its ring atom, on the outward direction
+ * -(sum of unit vectors to the heavy neighbours) in the molecular plane, and every carbon with two heavy neighbours gets an H by
+ * the same construction (the reference adds those without coordinates, build_molecule_aromatic, gor2goa.py:288-293); the added
+ * H's follow all other atoms in ascending parent index.
+ * GAUDI_ATOMS_FINGERPRINT: a 64-bit key of the heavy-atom graph, equal for isomorphic molecules (stands in for the InChI of
+ * analyze_rdkit_validity_for_molecules, analyze/analyze.py:180-231): initial colour (element, heavy degree, attached H count
+ * with the H of a two-neighbour carbon counted whether placed or not, histogram of shortest-path lengths to the other heavy
+ * atoms), Weisfeiler-Lehman rounds until the number of colour classes stops growing, hash of the colour multiset and the
+ * counts.  Integer arithmetic only.  Equal keys do not prove isomorphism.  0 for a molecule that was not built.
+ * GAUDI_E_CAPACITY for more than 32 rings in one molecule. */
+int gaudi_rings_to_atoms(gaudi_handle* h, const gaudi_ring_tables* tables, const gaudi_atom_tables* atom_tables, int B, int N,
+                         const float* x, const int32_t* ring_type, const int32_t* n_nodes, int flags, int max_atoms,
+                         int max_bonds, int32_t* n_atoms_out, int32_t* atom_type_out, double* xy_out, double* xyz_out,
+                         int32_t* n_bonds_out, int32_t* bonds_out, int32_t* status_out, uint64_t* fingerprint_out);
+
+/* Number of gaudi_rings_to_atoms launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
+int gaudi_atoms_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -368,6 +432,10 @@ int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, i
 /* ---- Device-free host logic (no handle, no GPU): exposed so the CPU test suite can check it. ----
  * gamma [T+1] and (optionally) the per-step table [T][4] exactly as gaudi_load_edm builds them. */
 int gaudi_host_schedule(int T, float noise_power /* 0 = cosine */, float noise_precision, float* gamma_out, float* coef_out);
+/* The symmetric 3 x 3 eigensolver of gaudi_rings_to_atoms (align_to_xy_plane), the same source text compiled for the host:
+ * a [n][3][3] (the lower triangles are read) -> e_out [n][3][3], e_out[q][c][k] = component c of the eigenvector of the k-th
+ * smallest eigenvalue, with the signs numpy.linalg.eigh (LAPACK dsyevd, 'L') returns. */
+int gaudi_host_eigh3(int n, const double* a, double* e_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),

@@ -529,6 +529,64 @@ def synth_hetro_molecule(rng, n, tables, jitter, corrupt):
     return x.astype(np.float32), ty
 
 
+def synth_hetro_fused(rng, n, tables, jitter):
+    """A cata-condensed hetero molecule that could exist: ring templates grown edge to edge, only carbon-carbon edges are shared and
+    no atom belongs to three rings, so the atoms gor2goa merges coincide (before the jitter) and the result does not depend on the
+    order of the rings.  (synth_hetro_molecule above draws orientation nodes at random: fine for the stability check, but gor2goa
+    gives a merged atom the element of the lower-index ring, and on such input its result changes with the ring order.)
+    -> (x [2k,3] rings then orientation nodes, types [2k], fused pairs as a set of (i, j), i < j)."""
+    G, names = tables["goa"], tables["rings"]["hetro"]
+    R = len(names) - 1
+    tm = [np.array(G["templates"][G["ring_template"][s]], np.float64) for s in names[:R]]
+    el = [G["ring_atoms"][s] for s in names[:R]]
+    w = np.array([6, 1, 1, 1, 1, 1, 1, 1, 0.3, 1, 0.5])
+    rot = lambda a: np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+    cc_edges = lambda t: [k for k in range(len(el[t])) if el[t][k] == "C" and el[t][(k + 1) % len(el[t])] == "C"]
+    t0 = int(rng.choice(R, p=w / w.sum()))
+    a0 = rng.uniform(0, 2 * np.pi)
+    rings = [dict(t=t0, c=np.zeros(2), ang=a0, v=tm[t0] @ rot(a0).T, used=set())]
+    pairs = set()
+    tries = 0
+    while len(rings) < n and tries < 4000:
+        tries += 1
+        p = int(rng.integers(len(rings)))
+        P = rings[p]
+        free = [k for k in cc_edges(P["t"]) if k not in P["used"] and (k + 1) % len(P["v"]) not in P["used"]]
+        if not free:
+            continue
+        k = free[rng.integers(len(free))]
+        A, B = P["v"][k], P["v"][(k + 1) % len(P["v"])]
+        t = int(rng.choice(R, p=w / w.sum()))
+        m = cc_edges(t)[rng.integers(len(cc_edges(t)))]
+        a, b = tm[t][m], tm[t][(m + 1) % len(tm[t])]
+        best = None
+        for src, dst in (((a, b), (B, A)), ((a, b), (A, B))):
+            ang = np.arctan2(*(dst[1] - dst[0])[::-1]) - np.arctan2(*(src[1] - src[0])[::-1])
+            c = dst[0] - rot(ang) @ src[0]
+            if np.linalg.norm(c - P["c"]) > np.linalg.norm((A + B) / 2 - P["c"]) + 0.3:
+                best = (ang, c)
+        if best is None:
+            continue
+        ang, c = best
+        v = tm[t] @ rot(ang).T + c
+        if any(np.linalg.norm(c - q["c"]) < 3.4 for i, q in enumerate(rings) if i != p):
+            continue
+        if any(np.linalg.norm(v[:, None] - q["v"][None], axis=-1).min() < 1.1 for i, q in enumerate(rings) if i != p):
+            continue
+        P["used"] |= {k, (k + 1) % len(P["v"])}
+        rings.append(dict(t=t, c=c, ang=ang, v=v, used={m, (m + 1) % len(v)}))
+        pairs.add((p, len(rings) - 1))
+    k = len(rings)
+    cen = np.array([q["c"] for q in rings])
+    # the orientation node: on the template's +x axis (where the hetero atom sits); the centre itself for Bn / Cbd
+    ori = np.array([q["c"] + (0 if names[q["t"]] in G["no_orientation"] else 1.3) * np.array([np.cos(q["ang"]), np.sin(q["ang"])])
+                    for q in rings])
+    x = np.concatenate([np.concatenate([cen, ori]), np.zeros((2 * k, 1))], 1)
+    x += rng.standard_normal(x.shape) * jitter
+    x = (x - x.mean(0)) @ _rand_rot(rng)
+    return x.astype(np.float32), np.array([q["t"] for q in rings] + [R] * k, np.int64), pairs
+
+
 def g11_stability():
     """Graph-of-rings stability check (analyze/analyze.py:50-100) on seeded synthetic molecules + a few degenerate
     ones; stores the reference's flags, distance matrix, adjacency and the sorted 3-ring / 4-ring angle lists."""
@@ -1834,6 +1892,169 @@ def g29_value_target():
     save("g29_value_target", **out)
 
 
+def _g30_graph(types, bonds, names):
+    import networkx as nx
+    g = nx.Graph()
+    for i, t in enumerate(types):
+        g.add_node(i, el=names[int(t)])
+    g.add_edges_from((int(a), int(b)) for a, b in bonds)
+    return g
+
+
+def _g30_same(g1, g2):
+    import networkx as nx
+    return nx.is_isomorphic(g1, g2, node_match=lambda a, b: a["el"] == b["el"])
+
+
+def g30_gor2goa():
+    """Graph of rings -> graph of atoms (data/gor2goa.py:133-261) on seeded synthetic molecules, a few inputs the reference raises
+    on and the capacity edge.  Per molecule: the inputs, `threw`, the reference's atom types, sorted bond list and atom positions
+    (the pairwise distance matrix is a function of those: the tests form it in float64; stored as a matrix it would not fit a
+    committed file), `stable` (check_stability, all flags), `iso_class` (exact isomorphism with element match over the whole set),
+    `dist_spread` and a twin: the same molecule with its rings permuted, rotated and reflected, and the twin's own class.
+
+    Tie filter: the discrete result of gor2goa flips on exact ties (argmin, the > 0 masks), which no implementation can be held
+    to.  Every candidate is re-run on 8 copies perturbed at relative 2^-23 and on its twin; it is dropped when the atom types or
+    the bond set change (copies) or the result is not isomorphic (twin).  At most 10 % may be dropped.  dist_spread = the
+    largest change of the distance matrix over the 8 copies."""
+    from analyze import analyze as ref_an
+    from data.aromatic_dataloader import ATOMS_LIST
+    from data.gor2goa import gor2goa
+    tables = json.load(open(os.path.join(ROOT, "gaudi_amd", "data", "ring_tables.json")))
+    rng = np.random.default_rng(3000)
+    DOT = len(tables["rings"]["hetro"]) - 1
+    # (dataset, x, types, kind); kind 0 = synthetic, 1 = special (kept whatever the filters say about ties), 2 = a special whose
+    # result depends on the ring order by construction: its twin is rotated and reflected but keeps the order
+    cands = []
+    for i in range(84):
+        n = 1 + i % 11
+        x = synth_cata_molecule(rng, n, tree_prob=[1.0, 1.0, 0.5][i % 3], jitter=[0.01, 0.03][i % 2], zjit=[0.0, 0.02][(i // 2) % 2])
+        cands.append(("cata", x, np.zeros(len(x), np.int64), 0))
+    from utils import helpers as ref_h
+    n_rejected = 0
+    for i in range(84):
+        while True:  # geometry check, not a tie filter: the grown molecule must have the fused pairs it was grown with
+            x, ty, pairs = synth_hetro_fused(rng, 2 + i % 9, tables, jitter=[0.01, 0.03][i % 2])
+            k = len(x) // 2
+            _, adj = ref_h.positions2adj(torch.from_numpy(x[None, :k].copy()), torch.from_numpy(ty[None, :k].copy()), 0.1, dataset="hetro")
+            if {(int(a), int(b)) for a, b in zip(*np.triu(adj[0].numpy()).nonzero())} == pairs and k >= 2:
+                break
+            n_rejected += 1
+        cands.append(("hetro", x, ty, 0))
+    print(f"g30: {n_rejected} grown hetero molecules re-drawn (a fused pair outside the reference's distance windows)")
+    f32 = lambda a: np.array(a, np.float32)
+    pair = f32([[-1.225, 0.02, 0], [1.225, -0.02, 0.01]])
+    specials = [
+        ("cata", f32([[0.3, -0.2, 0.1]]), [0]),                                             # a single ring
+        ("cata", pair, [0, 0]),                                                             # a pair
+        ("cata", f32([[2.45 * (k - 15.5), 0.013 * np.sin(1.7 * k), 0.009 * np.cos(2.3 * k)] for k in range(32)]), [0] * 32),  # capacity edge
+        ("cata", f32([[0, 0, 0], [2.45, 0.03, 0], [9, 0.1, 0], [11.45, 0.05, 0.02]]), [0] * 4),  # two far-apart pairs: builds
+        ("cata", f32([[0, 0, 0], [2.45, 0.03, 0], [9, 0.1, 0]]), [0] * 3),                  # a pair and a lone ring: raises
+        ("hetro", f32([[0, 0, 0], [2.45, 0.03, 0], [0.1, 0.5, 0], [2.5, 0.6, 0]]), [0, DOT, DOT, DOT]),  # "." as a ring: raises
+        ("hetro", f32([[0, 0, 0], [0.4, 0.3, 0]]), [DOT, DOT]),                             # "." as the only ring: raises
+        ("hetro", f32([[0, 0, 0], [2.45, 0.03, 0], [4.9, -0.02, 0], [0.1, 0.5, 0], [2.5, 0.6, 0]]), [0, 0, 0, DOT, DOT]),  # odd node count
+        ("hetro", f32([[0.5, 0.2, 0]]), [DOT]),                                             # one orientation node, no ring: raises
+    ]
+    for ds, x, ty in specials:
+        cands.append((ds, x, np.array(ty, np.int64), 1))
+    # pyridine (ring 0) and benzene fused across the N-C edge: each merged atom has a different element on the two rings, and
+    # gor2goa gives it ring i's (i < j) -- one N, where ring j's element would give none.  The grown molecules share C-C edges only.
+    hn = tables["rings"]["hetro"]
+    cands.append(("hetro", f32([[0.01, -0.02, 0], [2.077, 1.199, 0.015], [1.31, 0.02, 0], [2.09, 1.21, 0]]),
+                  np.array([hn.index("Pd"), hn.index("Bn"), DOT, DOT], np.int64), 2))
+
+    def run(ds, x, ty):
+        try:
+            a, t, b = gor2goa(torch.from_numpy(np.ascontiguousarray(x, np.float32).copy()), torch.from_numpy(ty.copy()), ds)
+        except Exception:
+            return None
+        return a.numpy().astype(np.float64), t.numpy().astype(np.int64), sorted((int(p), int(q)) for p, q in b)
+
+    def pdist(a):
+        return np.sqrt(((a[:, None] - a[None]) ** 2).sum(-1))
+
+    kept, dropped = [], {"cata": 0, "hetro": 0}
+    for ds, x, ty, kind in cands:
+        names = ATOMS_LIST[ds]
+        res = run(ds, x, ty)
+        rec = dict(ds=ds, x=x, ty=ty, threw=res is None, spread=0.0)
+        # the twin: rings permuted (orientation nodes along with them), then a random rotation and a reflection
+        n = len(x)
+        nr = n if ds == "cata" else n // 2
+        perm = rng.permutation(nr) if kind != 2 else np.arange(nr)
+        full = np.concatenate([perm, nr + perm, np.arange(2 * nr, n)]) if ds != "cata" else perm
+        Q = _rand_rot(rng)
+        Q[:, 0] *= -1.0 if np.linalg.det(Q) > 0 else 1.0  # det -1: a reflection is in
+        rec["tx"], rec["tty"] = (x[full].astype(np.float64) @ Q).astype(np.float32), ty[full]
+        if res is not None:
+            atoms, types, bonds = res
+            ok = True
+            d0 = pdist(atoms)
+            for k in range(8):
+                xp = (x.astype(np.float64) * (1.0 + rng.uniform(-1, 1, x.shape) * 2.0 ** -23)).astype(np.float32)
+                rp = run(ds, xp, ty)
+                if rp is None or not np.array_equal(rp[1], types) or rp[2] != bonds:
+                    ok = False
+                    break
+                rec["spread"] = max(rec["spread"], float(np.abs(pdist(rp[0]) - d0).max()))
+            rt = run(ds, rec["tx"], rec["tty"])
+            if ok and (rt is None or not _g30_same(_g30_graph(types, bonds, names), _g30_graph(rt[1], rt[2], names))):
+                ok = False
+            if not ok:
+                if kind >= 1:
+                    raise RuntimeError("a special molecule of g30 sits on a tie: move it")
+                dropped[ds] += 1
+                continue
+            rec.update(atoms=atoms, types=types, bonds=np.array(bonds, np.int64).reshape(-1, 2), twin=rt)
+            st = ref_an.check_stability(torch.from_numpy(x.copy()), torch.from_numpy(ty.copy()), dataset=ds)
+            rec["stable"] = all(bool(st[k]) for k in ("orientation_nodes", "dist_stable", "connected", "angels3", "angels4"))
+        else:
+            rec.update(atoms=np.zeros((0, 2)), types=np.zeros(0, np.int64), bonds=np.zeros((0, 2), np.int64), twin=None, stable=False)
+        kept.append(rec)
+    total = len(cands)
+    n_drop = sum(dropped.values())
+    print(f"g30: dropped {n_drop} of {total} candidates on ties ({dropped}); cap {total // 10}")
+    assert n_drop * 10 <= total, "tie filter dropped more than 10 %"
+
+    # classes under exact isomorphism, originals and twins together
+    reps, cls, tcls = [], [], []
+    def classify(ds, types, bonds):
+        g = _g30_graph(types, bonds, ATOMS_LIST[ds])
+        sig = (g.number_of_nodes(), g.number_of_edges(), tuple(sorted(ATOMS_LIST[ds][int(t)] for t in types)),
+               tuple(sorted(d for _, d in g.degree())))
+        for k, (s2, g2) in enumerate(reps):
+            if s2 == sig and _g30_same(g, g2):
+                return k
+        reps.append((sig, g))
+        return len(reps) - 1
+    for r in kept:
+        cls.append(-1 if r["threw"] else classify(r["ds"], r["types"], r["bonds"]))
+    for r in kept:
+        tcls.append(-1 if r["twin"] is None else classify(r["ds"], r["twin"][1], r["twin"][2]))
+    M = len(kept)
+    NM = max(len(r["x"]) for r in kept)
+    X = np.zeros((M, NM, 3), np.float32)
+    TX = np.zeros((M, NM, 3), np.float32)
+    TY = np.zeros((M, NM), np.int8)
+    TTY = np.zeros((M, NM), np.int8)
+    for m, r in enumerate(kept):
+        k = len(r["x"])
+        X[m, :k], TX[m, :k], TY[m, :k], TTY[m, :k] = r["x"], r["tx"], r["ty"], r["tty"]
+    aoff = np.concatenate([[0], np.cumsum([len(r["types"]) for r in kept])]).astype(np.int64)
+    boff = np.concatenate([[0], np.cumsum([len(r["bonds"]) for r in kept])]).astype(np.int64)
+    n_stable_cata = sum(r["stable"] and r["ds"] == "cata" for r in kept)
+    print(f"g30: {M} molecules kept, {sum(r['threw'] for r in kept)} raise, {len(reps)} isomorphism classes, "
+          f"{n_stable_cata} stable cata, largest dist_spread {max(r['spread'] for r in kept):.2e}")
+    save("g30_gor2goa", x=X, types=TY, n=np.array([len(r["x"]) for r in kept], np.int32),
+         hetro=np.array([r["ds"] == "hetro" for r in kept]), threw=np.array([r["threw"] for r in kept]),
+         stable=np.array([r["stable"] for r in kept]), atom_off=aoff, bond_off=boff,
+         ref_atoms=np.concatenate([r["atoms"] for r in kept]).astype(np.float64),
+         ref_types=np.concatenate([r["types"] for r in kept]).astype(np.int8),
+         ref_bonds=np.concatenate([r["bonds"] for r in kept]).astype(np.int16),
+         iso_class=np.array(cls, np.int32), dist_spread=np.array([r["spread"] for r in kept], np.float64),
+         twin_x=TX, twin_types=TTY, twin_iso_class=np.array(tcls, np.int32))
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -1859,7 +2080,8 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target)
-    which = sys.argv[1:] or list(fns)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target, g30=g30_gor2goa)
+    fns["g30_gor2goa"] = g30_gor2goa  # (also under its full name)
+    which = sys.argv[1:] or [k for k in fns if k != "g30_gor2goa"]
     for w in which:
         fns[w]()

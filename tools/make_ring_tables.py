@@ -10,6 +10,15 @@ index the one-hot node features use:
     dist_lo/hi[dataset][i][j] bonded-distance window of ring types (i, j), 0/0 when the pair never bonds
     a3[dataset][i]            list of (low, high) windows for the 3-ring angle centred on ring type i
     a4[dataset]               {"0": q, "180": q} dihedral thresholds;   n_nodes[dataset]: ring-count histogram
+
+and the constants of the graph-of-rings -> graph-of-atoms conversion (data/gor2goa.py:18-51,133-198, data/ring.py:6-18,
+utils/ring_graph.py:9, data/aromatic_dataloader.py:26-30), keyed by ring symbol:
+
+    goa.templates[name]       2-D ring templates (hexagon, pentagon, square), one [x, y] per ring atom
+    goa.ring_template[sym]    which template a ring type uses;   goa.ring_atoms[sym]: its elements (RINGS_DICT)
+    goa.no_orientation        ring types turned towards a fused ring instead of an orientation node
+    goa.extra_angle[sym]      what gor2goa adds to that angle;   goa.template_h[sym]: ring atoms that carry a template H
+    goa.atoms[dataset]        ATOMS_LIST;   goa.h_bond: X-H distance used when hydrogens are placed (ours, not the reference's)
 """
 import json
 import os
@@ -23,7 +32,12 @@ for m in ["rdkit", "rdkit.Chem", "rdkit.Chem.Draw", "rdkit.Chem.rdmolops", "rdki
           "imageio", "torch.utils.tensorboard"]:
     sys.modules[m] = MagicMock()
 
-from data.aromatic_dataloader import RINGS_LIST  # noqa: E402
+import math  # noqa: E402
+
+from data import gor2goa as G  # noqa: E402
+from data.aromatic_dataloader import ATOMS_LIST, RINGS_LIST  # noqa: E402
+from data.ring import RINGS_DICT  # noqa: E402
+from utils.ring_graph import NO_ORIENTATION_RINGS  # noqa: E402
 from utils import helpers as H  # noqa: E402
 
 out = dict(rings={}, dist_lo={}, dist_hi={}, a3={}, a4={}, n_nodes={}, min_dist={})
@@ -46,6 +60,18 @@ for ds in ("cata", "hetro"):
     out["a3"][ds] = [[list(w) for w in H.angels3_dict[ds][s].values()] if s in H.angels3_dict[ds] else [] for s in rings]
     out["a4"][ds] = H.angels4_dict[ds]
     out["n_nodes"][ds] = {str(k): v for k, v in H.analyzed_rings[ds]["n_nodes"].items()}
+templates = {"hexagon": G.hexagon, "pentagon": G.pentagon, "square": G.square}
+out["goa"] = dict(
+    templates={k: [[float(c) for c in row] for row in v] for k, v in templates.items()},
+    ring_template={sym: next(k for k, v in templates.items() if v is arr) for sym, arr in G.rings.items()},
+    ring_atoms={sym: list(elems) for sym, elems in RINGS_DICT.items()},
+    no_orientation=list(NO_ORIENTATION_RINGS),
+    # the two rules below are literals inside gor2goa's body (data/gor2goa.py:161-164 and :189-198), restated here
+    extra_angle={"Bn": math.pi / 6, "Cbd": math.pi / 4},
+    template_h={"Bl": [4], "Pl": [4], "DhDb": [2, 5]},
+    atoms={ds: list(ATOMS_LIST[ds]) for ds in ("cata", "peri", "hetro")},
+    h_bond=1.09,
+)
 path = os.path.join(ROOT, "gaudi_amd", "data", "ring_tables.json")
 with open(path, "w") as f:
     json.dump(out, f, indent=1)
