@@ -130,6 +130,7 @@ EXPORTS = {
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gaudi_set_plan_hint": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "gaudi_last_warning": (C.c_char_p, [C.c_void_p]),
+    "gaudi_last_kernel_key": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "gaudi_abi_version": (C.c_int, []),
     "gaudi_last_family_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "gaudi_profile_clock": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -171,6 +172,7 @@ _NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_g
 _GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")  # ... and the time-grid chains
 _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fused value targets
 _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
+_KEY_EXPORTS = ("gaudi_last_kernel_key",)  # ... and the name of the kernel a launch ran
 
 _lib = None
 
@@ -198,7 +200,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory

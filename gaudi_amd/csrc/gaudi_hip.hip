@@ -81,6 +81,7 @@ struct LaunchPlan {
   NodeBuf nodes = kResident;
   bool two = false;          // guided steps are two launches (denoiser-only kernel, then predictor-only kernel): no fused instantiation
   bool fr = false;           // 8 waves: launches on the resident full-ring kernel take its FR instantiation where one exists
+  bool n1 = false;           // 8 waves: ... their N1 instantiation (at most 16 node slots, one tail k-step) where one exists
   int ef = 2;                // edge features of the denoiser's first Linears (24: a sin_embedding denoiser, 4-wave family only)
   int groups = 0;            // workgroups (= molecules unless packed)
   int nslots = 0;            // node slots per workgroup (= N unless the call runs wide groups)
@@ -126,6 +127,8 @@ struct gaudi_handle {
   LaunchPlan plan;            // what the CURRENT call runs on
   bool split = true;          // 8-wave kernels: GEMMs on the fp16 matrix pipe with operands split into fp16 pairs (GAUDI_EDGE_MATH=fp32: off)
   bool no_fr = false;         // GAUDI_NO_FR=1: never the FR instantiation of the resident full-ring kernel (kern8s2_*.hip)
+  bool no_n1 = false;         // GAUDI_NO_N1=1: never the N1 instantiation of the resident full-ring kernel (kern8s1_*.hip)
+  std::string last_key;       // key_name of the kernel the most recent launch ran (gaudi_last_kernel_key)
   bool wide_full = true;      // GAUDI_WIDE_FULL=0: wide groups that do not fit the full ring run on the half ring (round 5)
   bool gn8_pq = true;         // GAUDI_GN8_PQ=0: never the P / Q-in-LDS form (kern8gp_*.hip)
   bool gn8 = true;            // GAUDI_GN8=0: molecules beyond the LDS limit go to the 4-wave V4G kernels, as in round 3
@@ -789,8 +792,8 @@ static kernel_fn find_kernel(const KernelKey& k) {
 }
 static std::string key_name(const KernelKey& k) {
   char buf[160];
-  snprintf(buf, sizeof buf, "waves=%d SP=%d MR=%d GN=%d FR=%d PG=%d EF=%d HPE=%d HPP=%d VT=%d", k.waves, k.sp, (int)k.mr, k.gn, (int)k.fr,
-           (int)k.pg, k.ef, k.hpe, k.hpp, (int)k.vt);
+  snprintf(buf, sizeof buf, "waves=%d SP=%d MR=%d GN=%d FR=%d PG=%d N1=%d EF=%d HPE=%d HPP=%d VT=%d", k.waves, k.sp, (int)k.mr, k.gn,
+           (int)k.fr, (int)k.pg, (int)k.n1, k.ef, k.hpe, k.hpp, (int)k.vt);
   return buf;
 }
 // two translation units registering one key is a build mistake: the first such key by name, or "" (gaudi_create)
@@ -842,15 +845,18 @@ static NodeBuf launch_nodes(const LaunchPlan& p, int hpe, int hpp) {
 // The kernel of a launch of the networks (hpe, hpp) under a plan.  MR applies to launches that run the predictor; a value-target
 // launch (vt) runs the VT instantiation of its kernel, which exists for launches with a predictor; the predictor-only launches of
 // a sin_embedding handle (no sin_embedding there) take the ordinary kernels.
-static kernel_fn plan_kernel(const LaunchPlan& p, int hpe, int hpp, bool vt) {
+// key: the key of the kernel returned (what gaudi_last_kernel_key names).
+static kernel_fn plan_kernel(const LaunchPlan& p, int hpe, int hpp, bool vt, KernelKey* key = nullptr) {
+  KernelKey unused;
+  KernelKey& k = key ? *key : unused;
   if (p.waves != 8) {
-    KernelKey k = key4(hpe, hpp, p.nodes == kAllGlobal, hpe ? p.ef : 2);
+    k = key4(hpe, hpp, p.nodes == kAllGlobal, hpe ? p.ef : 2);
     k.vt = vt && hpp;
     return find_kernel(k);
   }
   const NodeBuf nodes = launch_nodes(p, hpe, hpp);
   const bool mr = p.mr && hpp;
-  KernelKey k = nodes == kResident ? key8(hpe, hpp, p.ring, mr) : key8(hpe, hpp, 1, true, nodes);
+  k = nodes == kResident ? key8(hpe, hpp, p.ring, mr) : key8(hpe, hpp, 1, true, nodes);
   k.vt = vt && hpp;
   // two column tiles per node GEMM on the resident full-ring kernel: its FR instantiation (same arithmetic, same results).
   // (a kPredFifthGlobal plan is an mr plan: its fused launch never comes here)
@@ -858,6 +864,12 @@ static kernel_fn plan_kernel(const LaunchPlan& p, int hpe, int hpp, bool vt) {
     k.fr = true;
     if (kernel_fn f = find_kernel(k)) return f;
     k.fr = false;
+  }
+  // at most 16 node slots there: its N1 instantiation (one column tile per node GEMM compiled in; same arithmetic, same results)
+  if (p.n1 && nodes == kResident && !mr) {
+    k.n1 = true;
+    if (kernel_fn f = find_kernel(k)) return f;
+    k.n1 = false;
   }
   return find_kernel(k);
 }
@@ -948,7 +960,8 @@ static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long
   const LaunchPlan& plan = h->plan;
   const bool v8 = plan.waves == 8;
   const bool se = hpe && plan.ef > 2;  // stage_graph keeps such a call on the 4-wave family
-  const kernel_fn fn = plan_kernel(plan, hpe, hpp, P.vt != nullptr);
+  KernelKey key{};
+  const kernel_fn fn = plan_kernel(plan, hpe, hpp, P.vt != nullptr, &key);
   if (!fn)
     return fail(h, GAUDI_E_INVALID,
                 "no kernel instantiated for padded hidden sizes (" + std::to_string(hpe) + "," + std::to_string(hpp) + ")" +
@@ -1009,6 +1022,7 @@ static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long
   }
 #endif
   HIPCHECK(h, hipGetLastError());
+  h->last_key = key_name(key);
   if (h->prof) {
     HIPCHECK(h, h->prof_log.end(h->stream, ev));
     h->prof_steps += steps;
@@ -1315,9 +1329,16 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   const NodeBuf nodes = pg_run ? kPredFifthGlobal : gn8;
   P.pubx = acc.pubx;
   P.pub_ch = acc.pub_ch;
+  // The N1 instantiation of the resident full-ring kernel (plan_kernel): one column tile per node GEMM, i.e. at most 16 node slots
+  // per workgroup, packed or not; and its tail blocks hold ONE k-step (w8_nodes_f16.h: kTailOne), so a network whose padded width
+  // has a tail block must be one of H % 16 == 4 (196 -> 208; a predictor of 200 or 208 features keeps the plain kernel)
+  auto one_step_tail = [](int H, int HP) { return !HP || !w8::nh_odd(HP) || has_ktail(H, HP); };
+  const bool n1_run = !h->no_n1 && nodes == kResident && acc.mode == 1 && n_slots <= 16 &&  // (mr: plan_kernel, per launch)
+                      one_step_tail(h->ecfg.hidden_nf, hpe) && one_step_tail(h->pcfg.hidden_nf, hpp);
   if (getenv("GAUDI_DEBUG_PLAN"))
-    fprintf(stderr, "[plan] molecules=%d workgroups=%d N=%d node slots=%d S=%d split=%d mr=%d nodes=%d pub_ch=%d pubx=%d lds=%zu\n", B0, B, N,
-            n_slots, M.S, acc.mode, (int)mr_run, (int)nodes, acc.pub_ch, acc.pubx, lds_bytes8(hpe, hpp, n_slots, Dz, M.S, acc.pubx, acc.mode, nodes));
+    fprintf(stderr, "[plan] molecules=%d workgroups=%d N=%d node slots=%d S=%d split=%d mr=%d nodes=%d n1=%d pub_ch=%d pubx=%d lds=%zu\n", B0, B,
+            N, n_slots, M.S, acc.mode, (int)mr_run, (int)nodes, (int)n1_run, acc.pub_ch, acc.pubx,
+            lds_bytes8(hpe, hpp, n_slots, Dz, M.S, acc.pubx, acc.mode, nodes));
   auto up = [&](DevBuf& d, const void* src, size_t bytes) -> hipError_t {
     hipError_t e = d.reserve(bytes);
     if (e != hipSuccess) return e;
@@ -1385,6 +1406,7 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   plan.nodes = nodes;
   // (the FR instantiation: launches on the resident full-ring kernel with two column tiles per node GEMM, launch / plan_kernel)
   plan.fr = !h->no_fr && gn8 == kResident && acc.mode == 1 && n_slots > 16;
+  plan.n1 = n1_run;
   plan.groups = B;
   plan.nslots = n_slots;
   plan.hk = hk;
@@ -1535,6 +1557,7 @@ int gaudi_create(int device, gaudi_handle** out) {
   }
   if (const char* v = getenv("GAUDI_PRED_ROUNDS")) h->pred_rounds = atoi(v) != 0;
   h->no_fr = getenv("GAUDI_NO_FR") != nullptr;
+  h->no_n1 = getenv("GAUDI_NO_N1") != nullptr;
   h->plan.waves = h->variant;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
@@ -1572,6 +1595,11 @@ void gaudi_destroy(gaudi_handle* h) {
 
 const char* gaudi_last_error(const gaudi_handle* h) { return h ? h->err.c_str() : "null handle"; }
 const char* gaudi_last_warning(const gaudi_handle* h) { return h ? h->warn.c_str() : ""; }
+int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n) {
+  if (!h || !buf || n <= 0) return GAUDI_E_INVALID;
+  snprintf(buf, (size_t)n, "%s", h->last_key.c_str());
+  return GAUDI_OK;
+}
 int gaudi_abi_version(void) { return GAUDI_ABI_VERSION; }
 int gaudi_profile_clock(gaudi_handle* h, double* shader_mhz) {
   if (!h || !shader_mhz) return GAUDI_E_INVALID;

@@ -15,12 +15,13 @@ struct KernelKey {
   bool mr;
   int gn;     // node buffers in global memory: 0 none, 1 all of them, 2 all but P / Q (8 waves only)
   bool fr, pg;
+  bool n1;    // 8 waves: node GEMMs compiled for one column tile and one tail k-step (at most 16 node slots)
   int ef;     // edge features of the denoiser's first Linears: 2, or 24 (sin_embedding)
   int hpe, hpp;
   bool vt;
 };
 inline bool operator==(const KernelKey& a, const KernelKey& b) {
-  return a.waves == b.waves && a.sp == b.sp && a.mr == b.mr && a.gn == b.gn && a.fr == b.fr && a.pg == b.pg && a.ef == b.ef &&
+  return a.waves == b.waves && a.sp == b.sp && a.mr == b.mr && a.gn == b.gn && a.fr == b.fr && a.pg == b.pg && a.n1 == b.n1 && a.ef == b.ef &&
          a.hpe == b.hpe && a.hpp == b.hpp && a.vt == b.vt;
 }
 
@@ -37,6 +38,7 @@ constexpr KernelEntry entry() {
   e.key.gn = V::kGN;
   e.key.fr = V::kFR;
   e.key.pg = V::kPG;
+  e.key.n1 = V::kN1;
   e.key.ef = V::kEF;
   e.key.hpe = HPE;
   e.key.hpp = HPP;

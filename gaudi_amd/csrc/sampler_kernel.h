@@ -124,7 +124,7 @@ struct V4T {
   static constexpr bool kGlobalNodes = GN;
   // what the host's kernel table files an instantiation under (kernel_table.h: KernelKey); no device code reads these
   static constexpr int kWaveCount = 4, kSplit = 0, kGN = GN ? 1 : 0, kEF = EF;
-  static constexpr bool kMR = false, kFR = false, kPG = false;
+  static constexpr bool kMR = false, kFR = false, kPG = false, kN1 = false;
   using Graph = gaudi::MolGraph;
   template <int HP> using EdmSmem = gaudi::NetSmem<HP, GN, EF>;
   __device__ __forceinline__ static void set_rows(Graph&, const int*, int, int) {}  // the 4-wave kernels are never packed
@@ -294,7 +294,7 @@ __device__ __attribute__((noinline)) void vt_clip8(const VtDev* vt_, int b_, int
 }
 #ifndef GAUDI_STAMPS
 // GN: the node buffers of the phase live in the workgroup's slice of the global scratch (gnode_), everything else in LDS
-template <int HP, int SP, int GN = 0, bool FL = false>
+template <int HP, int SP, int GN = 0, int FL = 0>
 __device__ __attribute__((noinline)) void edm8_call(EdmDev W_, Graph8Args ga_, float t_val_, float* gnode_ = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const EdmDev W = uni(W_);
@@ -309,7 +309,7 @@ __device__ __attribute__((noinline)) void edm8_call(EdmDev W_, Graph8Args ga_, f
 }
 // the predictor's forward and reverse passes are separate functions too (the reverse pass holds three 52-register
 // operand sets at its peak; allocated together with the forward it spilled twice as much)
-template <int HP, int SP, bool MR, int GN = 0, bool FL = false, bool PG = false>
+template <int HP, int SP, bool MR, int GN = 0, int FL = 0, bool PG = false>
 __device__ __attribute__((noinline)) void pred_fwd8_call(PredDev W_, Graph8Args ga_, float t_val_, float* stash_, float readout_div_,
                                                          float* gnode_ = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -322,7 +322,7 @@ __device__ __attribute__((noinline)) void pred_fwd8_call(PredDev W_, Graph8Args 
   sm.hk = ga.hk ? smem + ga.hk : nullptr;
   w8::pred_forward<HP, SP, MR, GN, FL>(W, mg, sm, L.sZ, uni(t_val_), uni(stash_), uni(readout_div_), (int)threadIdx.x);
 }
-template <int HP, int SP, bool MR, int GN = 0, bool FL = false, bool PG = false>
+template <int HP, int SP, bool MR, int GN = 0, int FL = 0, bool PG = false>
 __device__ __attribute__((noinline)) void pred_bwd8_call(PredDev W_, Graph8Args ga_, float* stash_, float readout_div_, int resume_,
                                                          float* gnode_ = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -345,13 +345,17 @@ __device__ __attribute__((noinline)) void pred_bwd8_call(PredDev W_, Graph8Args 
 // FR: the node GEMMs' split passes and epilogues recompute their lane addresses per call (w8_nodes_f16.h: FL) -- always in the MR
 //     and GN kernels; the resident single-round kernel exists in both forms and the host picks by node slots (gaudi_hip.hip)
 // PG: the predictor keeps ONE node buffer in the workgroup's global scratch (w8_pred.h: PredSmem) -- wide groups on the full ring
-template <int SP, bool MR = false, int GN = 0, bool FR = false, bool PG = false>
+// N1: the resident single-round kernel for workgroups of at most 16 node slots whose tail blocks hold one k-step: its node GEMMs are
+//     compiled for ONE column tile (w8_nodes_f16.h: kNodeOneTile; kern8s1_*.hip).  Same arithmetic in the same order as the plain
+//     kernel; nothing but the node GEMMs' form depends on it
+template <int SP, bool MR = false, int GN = 0, bool FR = false, bool PG = false, bool N1 = false>
 struct V8T {
-  static constexpr bool kFL = MR || GN != 0 || FR;
+  static_assert(!N1 || (!MR && GN == 0 && !FR && !PG), "N1 is a form of the plain resident kernel");
+  static constexpr int kFL = N1 ? w8::kNodeOneTile : (MR || GN != 0 || FR) ? w8::kNodeFresh : w8::kNodePlain;
   static constexpr int kThreads = w8::kThreads;
   static constexpr int kSplit = SP;
   static constexpr int kWaveCount = 8, kGN = GN, kEF = 2;  // (kernel_table.h: KernelKey, with kSplit; host only)
-  static constexpr bool kMR = MR, kFR = FR, kPG = PG;
+  static constexpr bool kMR = MR, kFR = FR, kPG = PG, kN1 = N1;
   using Graph = w8::MolGraph;
   __host__ __device__ static int graph_floats(int N, int S) { return 2 * S + align16(N) + align16((N + 1 + S + 1) / 2); }
   __device__ __forceinline__ static float* load_graph(const KParams& P, int b, float* base, const float* sMask, Graph& mg, int tid, int wave) {

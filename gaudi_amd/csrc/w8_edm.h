@@ -137,7 +137,7 @@ __device__ __forceinline__ void scatter_runs(f4 (&e)[HP / 16], const TileCols& t
 }
 
 // eps_hat[N][D] (LDS) = EGNN_dynamics._forward(t, z[N][D] (LDS))
-template <int HP, int SP = 0, int GN = 0, bool FL = false>
+template <int HP, int SP = 0, int GN = 0, int FL = 0>
 __device__ __forceinline__ void edm_forward(const EdmDev& W, const MolGraph& mg, const NetSmem<HP, SP, GN>& sm, const float* sZ,
                                             float* sEps, float* sMean /* [4] */, float t_val, int tid STAMP_DECL) {
   constexpr int LD = HP + 4;
@@ -272,19 +272,25 @@ __device__ __forceinline__ void edm_forward(const EdmDev& W, const MolGraph& mg,
       }
       __syncthreads();
       STAMP(ST_BARRIER);
-      if constexpr (STG) stage_rows(xs0, sm.h, N * LD, wave, lane);
-      for (int idx = tid; idx < N * (HP / 4); idx += kThreads) {  // agg = (partial 0 + partial 1) / normalization_factor
-        const int n = idx / (HP / 4), f = 4 * (idx % (HP / 4));
-        if constexpr (STG)  // straight into the staged copy (only this GEMM reads agg)
-          *(f4*)(xs1 + n * LD + f) = (*(const f4*)(sm.agg + n * LD + f) + *(const f4*)(sm.agg1 + n * LD + f)) / W.normf;
-        else
-          *(f4*)(sm.agg + n * LD + f) = (*(const f4*)(sm.agg + n * LD + f) + *(const f4*)(sm.agg1 + n * LD + f)) / W.normf;
+      // agg = (partial 0 + partial 1) / normalization_factor.  Only the GEMM below reads it: the resident fp16-pair kernels (SUM)
+      // compute it where that GEMM's split pass loads its rows, behind the barrier above (w8_pred.h: pred_forward)
+      constexpr bool SUM = NH && GN == 0;
+      if constexpr (!SUM) {
+        if constexpr (STG) stage_rows(xs0, sm.h, N * LD, wave, lane);
+        for (int idx = tid; idx < N * (HP / 4); idx += kThreads) {
+          const int n = idx / (HP / 4), f = 4 * (idx % (HP / 4));
+          if constexpr (STG)  // straight into the staged copy
+            *(f4*)(xs1 + n * LD + f) = (*(const f4*)(sm.agg + n * LD + f) + *(const f4*)(sm.agg1 + n * LD + f)) / W.normf;
+          else
+            *(f4*)(sm.agg + n * LD + f) = (*(const f4*)(sm.agg + n * LD + f) + *(const f4*)(sm.agg1 + n * LD + f)) / W.normf;
+        }
+        if constexpr (STG) stage_wait();
+        else __syncthreads();
       }
-      if constexpr (STG) stage_wait();
-      else __syncthreads();
       STAMP(ST_MISC);
-      node_gemm_x<HP, EPI_SILU, true, GN, NH, kAheadOne, kAheadOne, FL>(wb, wbe, G + 3 * PK, sm.h, xs0, !h_kept, G + 4 * PK, sm.agg, xs1, bn1, sm.p, nullptr, nullptr,
-                                              mg.NC, wave, lane, tw, keep ? node_ctx_keep<HP>(hctx(), sm.hk, mg.NC) : hctx(), pf, G + 5 * PK);
+      node_gemm_x<HP, EPI_SILU, true, GN, NH, kAheadOne, kAheadOne, FL, SUM ? 2 : 0>(
+          wb, wbe, G + 3 * PK, sm.h, xs0, !h_kept, G + 4 * PK, sm.agg, xs1, bn1, sm.p, nullptr, nullptr, mg.NC, wave, lane, tw,
+          keep ? node_ctx_keep<HP>(hctx(), sm.hk, mg.NC) : hctx(), pf, G + 5 * PK, nullptr, nullptr, sm.agg1, W.normf);
       STAMP(ST_NODE);
       __syncthreads();
       STAMP(ST_BARRIER);

@@ -49,7 +49,8 @@ namespace w8 {
 
 constexpr float kLoScale = 2048.f;  // 2^11
 #ifndef GAUDI_NODE_ABLATE
-#define GAUDI_NODE_ABLATE 0  // microbenchmark only (timing, wrong results): 1 = no split pass, 2 = no matrix instructions, 4 = no weight loads
+#define GAUDI_NODE_ABLATE 0  // microbenchmark only (timing, wrong results): 1 = no split pass, 2 = no matrix instructions, 4 = no weight loads,
+                             // 8 = waves without a second output tile run a one-tile body (tools/node_gemm_h_microbench.hip; node_gemm_h: NU)
 #endif
 constexpr int kAblateH = GAUDI_NODE_ABLATE;
 // microbenchmark only (-DGAUDI_NODE_STAMPS=1): cycle sums of the parts of a node GEMM, per wave (s_memtime waits for lgkmcnt(0): shares, not
@@ -138,11 +139,32 @@ struct SplitRowH {
   f4 x;
   uint32_t mx;
 };
-template <int HP>
-__device__ __forceinline__ SplitRowH split_row_load(const float* X, int n, int lane) {
+// Where the split pass takes its rows from: one array, or the sum of two (the two partial sums of the edge aggregation, which only
+// the node MLP's first GEMM reads -- w8_pred.h, w8_edm.h: the separate "agg = partial 0 + partial 1" pass and its barrier are this
+// load), DIV: divided by d (the denoiser's normalization_factor: a division, as the pass it replaces).
+struct RowsOne {
+  const float* x;
+  __device__ __forceinline__ f4 load(int off) const { return *(const f4*)(x + off); }
+};
+template <bool DIV>
+struct RowsSum {
+  const float *a, *b;
+  float d;
+  __device__ __forceinline__ f4 load(int off) const {
+    const f4 s = *(const f4*)(a + off) + *(const f4*)(b + off);
+    return DIV ? s / d : s;
+  }
+};
+__device__ __forceinline__ RowsOne rows_of(const float* x) { return RowsOne{x}; }
+__device__ __forceinline__ RowsOne rows_of(const RowsOne& r) { return r; }
+__device__ __forceinline__ RowsOne rows_of(decltype(nullptr)) { return RowsOne{nullptr}; }  // (a GEMM without that source)
+template <bool DIV>
+__device__ __forceinline__ RowsSum<DIV> rows_of(const RowsSum<DIV>& r) { return r; }
+template <int HP, class SRC>
+__device__ __forceinline__ SplitRowH split_row_load(const SRC& X, int n, int lane) {
   constexpr int LD = HP + 4;
   SplitRowH r;
-  r.x = lane < HP / 4 ? *(const f4*)(X + n * LD + 4 * lane) : splat(0.f);
+  r.x = lane < HP / 4 ? X.load(n * LD + 4 * lane) : splat(0.f);
   // (absbits takes the element BY VALUE: __builtin_bit_cast applied to an ext-vector element expression reads element 0
   // whatever the index -- hipcc 7.2; found as rows whose largest entry was not in a lane's first slot getting the wrong scale)
   r.mx = umax(umax(absbits(r.x[0]), absbits(r.x[1])), umax(absbits(r.x[2]), absbits(r.x[3])));
@@ -175,8 +197,9 @@ __device__ __forceinline__ void split_row_store(const SplitBufH& sb, const f4 x,
   }
   if (lane == 0) sb.scale(HP)[ct * 16 + c] = inv;
 }
-template <int HP>
-__device__ __forceinline__ void split_rows_h(const SplitBufH& sb, const float* X, int N, int wave, int lane) {
+template <int HP, class SRC>
+__device__ __forceinline__ void split_rows_h(const SplitBufH& sb, const SRC& X_, int N, int wave, int lane) {
+  const auto X = rows_of(X_);
   for (int n = wave; n < N; n += 2 * kWaves) {
     const int n2 = n + kWaves < N ? n + kWaves : n;  // (a second copy of the same row when there is no partner: same stores)
     SplitRowH a = split_row_load<HP>(X, n, lane), b = split_row_load<HP>(X, n2, lane);
@@ -207,6 +230,12 @@ __device__ __forceinline__ void lds_barrier() {
 // buffer_load issue), the split pass and the epilogue leave that pipe idle, so loads moved there cost nothing.
 #ifndef GAUDI_NODE_LATE
 #define GAUDI_NODE_LATE 0
+#endif
+// The fp32 tail steps of a source (odd tile counts) ahead of its K loop instead of in the fold behind it: they need the bias, the tail
+// weights (loaded in the prologue) and the split copy, not the loop -- y then reaches the fold complete.  Same order of operations per
+// output element (bias, tail steps, descaled chunk sums).  Measured: DESIGN section 8, round 9.
+#ifndef GAUDI_NODE_TAIL_EARLY
+#define GAUDI_NODE_TAIL_EARLY 0
 #endif
 template <int HP>
 struct NodeGeoH {
@@ -242,10 +271,10 @@ struct TileLanesH {
       vo[u] = (on && wave + kWaves * u < NodeGeoH<HP>::T) ? lane * 16 + (wave + kWaves * u) * 2048 : kOOBBytes;
   }
 };
-template <int HP>
+template <int HP, int NU = NodeGeoH<HP>::NTW>
 __device__ __forceinline__ void nh_load(NodeSetH<NodeGeoH<HP>::NTW>& s, const WBuf& wh, int chunk_off, const TileLanesH<HP>& tl) {
 #pragma unroll
-  for (int u = 0; u < NodeGeoH<HP>::NTW; ++u) {
+  for (int u = 0; u < NU; ++u) {
     s.p[u][0] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(wh.r, tl.vo[u], chunk_off * 4, GAUDI_NODE_LOAD_AUX));
     s.p[u][1] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(wh.r, tl.vo[u] + 1024, chunk_off * 4, GAUDI_NODE_LOAD_AUX));
   }
@@ -264,6 +293,15 @@ __device__ __forceinline__ void node_prefetch_h(NodePFH<HP>& pf, const WBuf& wh,
   });
 }
 
+// FL, the form of a kernel's node GEMMs (sampler_kernel.h: V8T::kFL)
+constexpr int kNodePlain = 0;    // lane addresses of the split passes and epilogues hoisted out of the layer loops
+constexpr int kNodeFresh = 1;    // ... recomputed per call (node_gemm_x below)
+constexpr int kNodeOneTile = 2;  // kNodePlain for workgroups of at most 16 node slots: ONE column tile and, at a width with a tail
+                                 // block, ONE tail k-step (H % 16 == 4) are compile-time facts -- the host guarantees both
+// TAIL of node_gemm_h: how many k-steps of the fp32 tail block hold weights
+constexpr int kTailRuntime = 0;  // NodeCtxH::ktail says: one or four
+constexpr int kTailOne = 1;      // one (H % 16 == 4): steps 1-3 are neither loaded nor compiled
+
 // what a call needs beside the fp32 form's arguments
 struct NodeCtxH {
   float winv;       // 2^-s_w: descale of the network's node matrices
@@ -280,17 +318,23 @@ struct NodeCtxH {
 //   (pf.s[0 .. min(PIN, D))); POUT: chunks of nextW this call loads ahead.
 // The caller guarantees that nobody still reads the split regions when the call starts (a barrier since their last use) and
 // places a barrier between this call's stores to sY and their readers, as for the fp32 form.
-template <int HP, int EPI, bool TWO, int MAXNT, int PIN = kAheadOne, int POUT = kAheadOne, bool FL = false>
-__device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float* sXa, bool do_split_a, int Wb, const float* sXb,
+// sXb: the second source's rows, a pointer or a row source (RowsOne / RowsSum above).
+// NU (microbenchmark only, GAUDI_NODE_ABLATE & 8): the output tiles this body loads and multiplies, 0 = the geometry's.
+template <int HP, int EPI, bool TWO, int MAXNT, int PIN = kAheadOne, int POUT = kAheadOne, int FL = kNodePlain, int TAIL = kTailRuntime,
+          int NU = 0, class XB = const float*>
+__device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float* sXa, bool do_split_a, int Wb, const XB& sXb,
                                             const float* sBias, float* sY, const float* sRes, const float* sMask, int N, int wave,
                                             int lane, const NodeCtxH& cx, NodePFH<HP>& pf, int nextW = -1, float* gPre = nullptr,
                                             uint32_t* sMaxOut = nullptr /* LDS [N], zeroed: max |y| bits of every node's row */,
                                             NodeStampH* ns = nullptr) {
   (void)ns;
   using G = NodeGeoH<HP>;
-  constexpr int T = G::T, LD = HP + 4, NTW = G::NTW, nc = G::nc, D = G::D;
+  constexpr int T = G::T, LD = HP + 4, NTW = NU > 0 ? NU : G::NTW, nc = G::nc, D = G::D;
   constexpr int kIn = PIN < D ? PIN : D, kOut = POUT < D ? POUT : D;
   constexpr int kLate = nc < D ? 0 : (GAUDI_NODE_LATE < kOut ? GAUDI_NODE_LATE : kOut);  // (matrices of fewer chunks than sets: all in the loop)
+  constexpr int TQ = TAIL == kTailOne ? 1 : 4;                 // tail k-steps that exist in this instantiation
+  const bool ktail = TAIL == kTailOne ? true : cx.ktail;
+  constexpr bool kFresh = FL == kNodeFresh;
   const int c = lane & 15, g = lane >> 4;
   // column tiles of this call (wave-uniform; the code below branches on it around matrix instructions and LDS traffic only)
   const int nt = (MAXNT < 2 || N <= 16) ? 1 : (MAXNT < 3 || N <= 32) ? 2 : 3;
@@ -304,17 +348,17 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
   // chunks that did not travel ahead of the call
   static_for<D>([&](auto d_tag) {
     constexpr int d = decltype(d_tag)::value;
-    if constexpr (d >= kIn) nh_load<HP>(pf.s[d], wh, 2 * Wa + d * nh_chunk_floats(HP), tl);
+    if constexpr (d >= kIn) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wa + d * nh_chunk_floats(HP), tl);
   });
   // tail weights (odd tile counts): k-step q of the wave's tiles; steps past the first are loaded only when they hold weights
-  float ta[NTW][4], tb[NTW][4];
+  float ta[NTW][TQ], tb[NTW][TQ];
   if constexpr (G::odd) {
 #pragma unroll
     for (int u = 0; u < NTW; ++u) {
       const int t = wave + kWaves * u < T ? wave + kWaves * u : 0;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int ln = ((q == 0 || !cx.ktail) && wave + kWaves * u < T) ? lane : kOOBLane;
+      for (int q = 0; q < TQ; ++q) {
+        const int ln = ((q == 0 || !ktail) && wave + kWaves * u < T) ? lane : kOOBLane;
         ta[u][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wh.r, ln * 4, (2 * Wa + nh_tail_off(HP) + t * 256 + q * 64) * 4, 0));
         if constexpr (TWO)
           tb[u][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wh.r, ln * 4, (2 * Wb + nh_tail_off(HP) + t * 256 + q * 64) * 4, 0));
@@ -325,8 +369,8 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
   // forty integer instructions -- instead of being hoisted out of the layer loop and spilled; the K loop's offsets stay hoisted.
   NSTAMP(0);
   if (!(kAblateH & 1)) {
-    const int ls = FL ? fresh(lane) : lane;
-    if (do_split_a) split_rows_h<HP>(sa, sXa, N, wave, ls);
+    const int ls = kFresh ? fresh(lane) : lane;
+    if (do_split_a) split_rows_h<HP>(sa, rows_of(sXa), N, wave, ls);
     if (TWO && !seq) split_rows_h<HP>(sb, sXb, N, wave, ls);
     NSTAMP(1);
     if (do_split_a || (TWO && !seq)) lds_barrier();
@@ -351,7 +395,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
     return BH{*(const u4*)q, *(const u4*)(q + 256)};
   };
   // the three piece products of one column tile against one chunk
-  auto mm = [&](const NodeSetH<NTW>& s, const BH& b, int j) {
+  auto mm = [&](const NodeSetH<G::NTW>& s, const BH& b, int j) {
     if (kAblateH & 2) {  // (keep the operands alive)
       asm volatile("" ::"v"(s.p[0][0]), "v"(s.p[0][1]), "v"(s.p[NTW - 1][0]), "v"(s.p[NTW - 1][1]), "v"(b.h), "v"(b.l));
       return;
@@ -363,22 +407,36 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
 #pragma unroll
     for (int u = 0; u < NTW; ++u) acc1[j][u] = mfma_h(s.p[u][1], b.h, acc1[j][u]);
   };
+  // the tail's fp32 steps of column tile j: inputs 16 (T-1) + 4 q + g on lane group g, unscaled operands
+  auto tail_steps = [&](const SplitBufH& s_, const float (&tw)[NTW][TQ], auto j_tag) {
+    constexpr int j = decltype(j_tag)::value;
+    if constexpr (G::odd) {
+      const float* xt = s_.tail(HP) + j * 256 + g * 16 + c;  // [input k = g + 4 q][column c]
+#pragma unroll
+      for (int u = 0; u < NTW; ++u) y[j][u] = mfma1(tw[u][0], xt[0], y[j][u]);
+      if constexpr (TQ > 1) {
+        if (!ktail) {
+#pragma unroll
+          for (int q = 1; q < TQ; ++q)
+#pragma unroll
+            for (int u = 0; u < NTW; ++u) y[j][u] = mfma1(tw[u][q], xt[64 * q], y[j][u]);
+        }
+      }
+    }
+  };
+  constexpr bool kTailEarly = GAUDI_NODE_TAIL_EARLY != 0;
+  auto tail_early = [&](const SplitBufH& s_, const float (&tw)[NTW][TQ]) {
+    if constexpr (kTailEarly && G::odd)
+      static_for<MAXNT>([&](auto j_tag) {
+        if (decltype(j_tag)::value < nt) tail_steps(s_, tw, j_tag);
+      });
+  };
   // descale and fold the accumulators of one source into y
-  auto fold = [&](const SplitBufH& s_, const float (&tw)[NTW][4]) {
+  auto fold = [&](const SplitBufH& s_, const float (&tw)[NTW][TQ]) {
     static_for<MAXNT>([&](auto j_tag) {
       constexpr int j = decltype(j_tag)::value;
       if (j < nt) {
-        if constexpr (G::odd) {  // the tail's fp32 steps: inputs 16 (T-1) + 4 q + g on lane group g, unscaled operands
-          const float* xt = s_.tail(HP) + j * 256 + g * 16 + c;  // [input k = g + 4 q][column c]
-#pragma unroll
-          for (int u = 0; u < NTW; ++u) y[j][u] = mfma1(tw[u][0], xt[0], y[j][u]);
-          if (!cx.ktail) {
-#pragma unroll
-            for (int q = 1; q < 4; ++q)
-#pragma unroll
-              for (int u = 0; u < NTW; ++u) y[j][u] = mfma1(tw[u][q], xt[64 * q], y[j][u]);
-          }
-        }
+        if constexpr (!kTailEarly) tail_steps(s_, tw, j_tag);
         const float sc = s_.scale(HP)[j * 16 + c] * cx.winv;
 #pragma unroll
         for (int u = 0; u < NTW; ++u) {
@@ -414,9 +472,9 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!(kAblateH & 4)) {
-        if constexpr (i + D < nc) nh_load<HP>(pf.s[d], wh, 2 * Wcur + (i + D) * nh_chunk_floats(HP), tl);
-        else if constexpr (!last_src) nh_load<HP>(pf.s[d], wh, 2 * Wb + d * nh_chunk_floats(HP), tl);
-        else if constexpr (d < kOut - kLate) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
+        if constexpr (i + D < nc) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wcur + (i + D) * nh_chunk_floats(HP), tl);
+        else if constexpr (!last_src) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wb + d * nh_chunk_floats(HP), tl);
+        else if constexpr (d < kOut - kLate) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       }
       __builtin_amdgcn_sched_barrier(0);
       bcur = bnext;
@@ -427,7 +485,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
     constexpr int d = decltype(d_tag)::value;
     if constexpr (d >= kOut - kLate && d < kOut) {
       __builtin_amdgcn_sched_barrier(0);
-      if (!(kAblateH & 4)) nh_load<HP>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
+      if (!(kAblateH & 4)) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -438,9 +496,10 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
   // while it streams.  Microbenchmark -0.3 ... -1.9 % per GEMM at one column tile (profiles/r06b_node_gemm_priority.txt); product C3
   // 206.3 -> 208.1 mol/s.  With TWO column tiles the microbenchmark gains more (-3.7 %) and the product LOSES (C4 245.0 -> 242.2,
   // pairs -0.2 %): only the kernels that run one column tile (not FL) take the step.  Priority for waves 0-3 instead: nothing.
-  if constexpr (!FL)
+  if constexpr (!kFresh)
     if ((GAUDI_NODE_PRIO == 1 && wave >= kWaves / 2) || (GAUDI_NODE_PRIO == 2 && wave < kWaves / 2)) __builtin_amdgcn_s_setprio(1);
 #endif
+  tail_early(sa, ta);
   source(std::integral_constant<int, 0>{}, sa);
   NSTAMP(4);
   if constexpr (!TWO) late(std::integral_constant<int, kOut - kLate>{});
@@ -449,9 +508,10 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
   if constexpr (TWO) {
     if (seq) {
       lds_barrier();  // (every wave is done with the first source's copy; the weight loads in flight stay in flight)
-      split_rows_h<HP>(sb, sXb, N, wave, FL ? fresh(lane) : lane);
+      split_rows_h<HP>(sb, sXb, N, wave, kFresh ? fresh(lane) : lane);
       lds_barrier();
     }
+    tail_early(sb, tb);
     source(std::integral_constant<int, 1>{}, sb);
     late(std::integral_constant<int, kOut - kLate>{});
     fold(sb, tb);
@@ -460,9 +520,9 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
     if constexpr (decltype(d_tag)::value > kOut - kLate) late(d_tag);
   });
 #if GAUDI_NODE_PRIO
-  if constexpr (!FL) __builtin_amdgcn_s_setprio(0);
+  if constexpr (!kFresh) __builtin_amdgcn_s_setprio(0);
 #endif
-  const int le = FL ? fresh(lane) : lane, ce = le & 15, ge = le >> 4;
+  const int le = kFresh ? fresh(lane) : lane, ce = le & 15, ge = le >> 4;
   static_for<MAXNT>([&](auto j_tag) {
     constexpr int j = decltype(j_tag)::value;
     if (j < nt) {
@@ -473,7 +533,7 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
         f4 yy = y[j][u];
         if (t < T && nd < N) {
           float* dst = sY + nd * LD + 16 * t + 4 * ge;
-          const bool pad = G::odd && cx.ktail && t == T - 1 && ge > 0;  // rows 4 .. 15 of the last tile of an H % 16 == 4 width
+          const bool pad = G::odd && ktail && t == T - 1 && ge > 0;  // rows 4 .. 15 of the last tile of an H % 16 == 4 width
           if (pad) yy = splat(0.f);
           if (gPre != nullptr) nstash_store((f4*)(gPre + nd * HP + 16 * t + 4 * ge), yy);  // stash: write once, read once
           // the row maxima the edge GEMMs' column scales are bounded with (w8_split.h): one LDS atomic per lane and tile
@@ -532,14 +592,24 @@ __device__ __forceinline__ void node_prefetch_x(PF& pf, const WBuf& wb, const WB
 // 1024 in pairs +2.2 %, but C3 (11 nodes, one column tile: half the epilogue work per reload) -0.4 % -- the recomputation costs
 // what the reloads did.  So FL is on in the kernels that take large molecules (MR, GN, and the FR instantiation of the resident
 // kernel that the host picks for more than 16 node slots) and off in the one C2 / C3 run on.
-template <int HP, int EPI, bool TWO, int GN, bool NH, int PIN, int POUT, bool FL = false, class PF>
+// FL = kNodeOneTile: the instantiation the host picks for at most 16 node slots (one column tile, one tail k-step: see above).
+// XBS: the second source is Xb + Xb1 (1), (Xb + Xb1) / xb_div (2) -- fp16-pair GEMMs whose rows are not staged only (RowsSum).
+template <int HP, int EPI, bool TWO, int GN, bool NH, int PIN, int POUT, int FL = kNodePlain, int XBS = 0, class PF>
 __device__ __forceinline__ void node_gemm_x(const WBuf& wb, const WBuf& wbe, int Wa, const float* Xa, const float* XaS, bool split_a, int Wb,
                                             const float* Xb, const float* XbS, const float* sBias, float* sY, const float* sRes,
                                             const float* sMask, int N, int wave, int lane, bool tw, const NodeCtxH& cx, PF& pf,
-                                            int nextW = -1, float* gPre = nullptr, uint32_t* sMaxOut = nullptr) {
+                                            int nextW = -1, float* gPre = nullptr, uint32_t* sMaxOut = nullptr,
+                                            const float* Xb1 = nullptr, float xb_div = 1.f) {
+  static_assert(XBS == 0 || (NH && GN == 0 && TWO), "summed second sources: the fp16-pair form of the resident kernels");
   if constexpr (NH) {
-    node_gemm_h<HP, EPI, TWO, GN ? 3 : 2, PIN, POUT, FL>(wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW, gPre,
-                                                         sMaxOut);
+    constexpr int MAXNT = GN ? 3 : FL == kNodeOneTile ? 1 : 2;
+    constexpr int TAIL = FL == kNodeOneTile && nh_odd(HP) ? kTailOne : kTailRuntime;
+    if constexpr (XBS == 0)
+      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL>(wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW,
+                                                            gPre, sMaxOut);
+    else
+      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL>(wbe, Wa, Xa, split_a, Wb, RowsSum<XBS == 2>{Xb, Xb1, xb_div}, sBias, sY, sRes, sMask, N,
+                                                            wave, lane, cx, pf, nextW, gPre, sMaxOut);
   } else if constexpr (GN != 0) {
     node_gemm_n<HP, EPI, true, 3>(wb, Wa, XaS, Wb, XbS, sBias, sY, sRes, sMask, N, wave, lane, tw, &pf, nextW, gPre);
   } else {

@@ -95,7 +95,7 @@ __host__ __device__ inline int pub_chunk_tiles(int S, long long avail_floats, in
 // MR: the kernel takes graphs of more than one round of eight edge tiles (more than 128 slots).  A separate instantiation: the
 // round loops (and the second copy of the reverse chain that parks du in the stash) cost the single-round kernels 2-4 % when
 // they live in the same function (hipcc's register allocation of the out-of-line phases changes), measured on C3.
-template <int HP, int SP = 0, bool MR = false, int GN = 0, bool FL = false, class SM = PredSmem<HP, SP, GN>>
+template <int HP, int SP = 0, bool MR = false, int GN = 0, int FL = 0, class SM = PredSmem<HP, SP, GN>>
 __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& mg, const SM& sm, const float* sZ,
                                              float t_val, float* stash, float readout_div, int tid STAMP_DECL) {
   constexpr int LD = HP + 4;
@@ -263,19 +263,25 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
     }
     __syncthreads();
     STAMP(ST_BARRIER);
-    if constexpr (STG) stage_rows(xs0, h, N * LD, wave, lane);
-    for (int idx = tid; idx < N * (HP / 4); idx += kThreads) {  // agg = partial 0 + partial 1
-      const int n = idx / (HP / 4), f = 4 * (idx % (HP / 4));
-      if constexpr (STG)  // straight into the staged copy (only this GEMM reads agg)
-        *(f4*)(xs1 + n * LD + f) = *(const f4*)(agg + n * LD + f) + *(const f4*)(agg1 + n * LD + f);
-      else
-        *(f4*)(agg + n * LD + f) = *(const f4*)(agg + n * LD + f) + *(const f4*)(agg1 + n * LD + f);
+    // agg = partial 0 + partial 1.  Only the GEMM below reads it: the resident fp16-pair kernels (SUM) add the partials where that
+    // GEMM's split pass loads its rows, behind the barrier above -- no pass of their own, no second barrier
+    constexpr bool SUM = NH && GN == 0;
+    if constexpr (!SUM) {
+      if constexpr (STG) stage_rows(xs0, h, N * LD, wave, lane);
+      for (int idx = tid; idx < N * (HP / 4); idx += kThreads) {
+        const int n = idx / (HP / 4), f = 4 * (idx % (HP / 4));
+        if constexpr (STG)  // straight into the staged copy
+          *(f4*)(xs1 + n * LD + f) = *(const f4*)(agg + n * LD + f) + *(const f4*)(agg1 + n * LD + f);
+        else
+          *(f4*)(agg + n * LD + f) = *(const f4*)(agg + n * LD + f) + *(const f4*)(agg1 + n * LD + f);
+      }
+      if constexpr (STG) stage_wait();
+      else __syncthreads();
     }
-    if constexpr (STG) stage_wait();
-    else __syncthreads();
     STAMP(ST_MISC);
-    node_gemm_x<HP, EPI_SILU, true, GN, NH, kAheadOne, kAheadOne, FL>(wb, wbe, Lw.Wn1h, h, xs0, !keep, Lw.Wn1a, agg, xs1, Lw.bn1, p, nullptr, nullptr, mg.NC, wave, lane,
-                                            tw, keep ? node_ctx_keep<HP>(hctx(), sm.hk, mg.NC) : hctx(), pf, Lw.Wn2, st + 2 * N * HP /* npre -> stash */);
+    node_gemm_x<HP, EPI_SILU, true, GN, NH, kAheadOne, kAheadOne, FL, SUM ? 1 : 0>(
+        wb, wbe, Lw.Wn1h, h, xs0, !keep, Lw.Wn1a, agg, xs1, Lw.bn1, p, nullptr, nullptr, mg.NC, wave, lane, tw,
+        keep ? node_ctx_keep<HP>(hctx(), sm.hk, mg.NC) : hctx(), pf, Lw.Wn2, st + 2 * N * HP /* npre -> stash */, nullptr, agg1);
     STAMP(ST_NODE);
     __syncthreads();
     STAMP(ST_BARRIER);
@@ -318,7 +324,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
 //                          B4 = b4: npre (stash) -> dnpre -> dQ
 // pub_ch = 16-feature tiles of du published per chunk into [b0 | b1 | pub] (row = 16 pub_ch + 4 floats per slot)
 // ---------------------------------------------------------------------------------------------
-template <int HP, int SP = 0, bool MR = false, int GN = 0, bool FL = false, class SM = PredSmem<HP, SP, GN>>
+template <int HP, int SP = 0, bool MR = false, int GN = 0, int FL = 0, class SM = PredSmem<HP, SP, GN>>
 __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& mg, const SM& sm, const float* stash,
                                               float* sGrad, float readout_div, int pub_ch, int tid STAMP_DECL, const float* sZin = nullptr) {
   constexpr int LD = HP + 4;

@@ -171,6 +171,16 @@ class Engine:
         self._check(fn(self.h, C.byref(v)), "gaudi_profile_clock")
         return float(v.value)
 
+    def last_kernel_key(self) -> str:
+        """The kernel-table key of the kernel the most recent launch ran, e.g. 'waves=8 SP=1 ... N1=1 ... VT=0' ('' before the
+        first launch, or an older A/B library without the entry point)."""
+        fn = getattr(self.lib, "gaudi_last_kernel_key", None)
+        if fn is None or not fn.argtypes:
+            return ""
+        buf = C.create_string_buffer(256)
+        self._check(fn(self.h, buf, len(buf)), "gaudi_last_kernel_key")
+        return buf.value.decode()
+
     def keep_h(self) -> int:
         """Floats of LDS the most recent call gave to a kept split copy of h (0: none)."""
         fn = getattr(self.lib, "gaudi_last_keep_h", None)

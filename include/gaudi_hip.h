@@ -81,6 +81,10 @@ const char* gaudi_last_error(const gaudi_handle* h);
  * cannot carry (an infinite weight, a matrix far below the others), whose calls therefore run the fp32-instruction kernels at
  * about 0.55 x the speed.  gaudi_amd.engine turns it into a Python warning at load time and into diag["edge_math_fallback"]. */
 const char* gaudi_last_warning(const gaudi_handle* h);
+/* The kernel the most recent launch of the handle ran, as its kernel-table key ("waves=8 SP=1 MR=0 GN=0 FR=0 PG=0 N1=1 EF=2 HPE=192
+ * HPP=208 VT=0": csrc/kernel_table.h), NUL-terminated and cut to n bytes; "" before the first launch.  For tests and tooling: which
+ * instantiation a plan picked (GAUDI_NO_FR / GAUDI_NO_N1 at gaudi_create keep the resident full-ring kernel on its plain form). */
+int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
 /* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3 -- change no existing

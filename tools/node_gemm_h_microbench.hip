@@ -15,10 +15,13 @@ using namespace gaudi;
 #define GAUDI_MB_AHEAD w8::kAheadAll  // chunks that travel ahead of a call; w8::kAheadOne: what most call sites of the kernels use
 #endif
 #ifndef GAUDI_MB_FL
-#define GAUDI_MB_FL false  // true: the FL form (lane addresses recomputed per call: the MR / GN / FR kernels)
+#define GAUDI_MB_FL 0  // 1: the FL form (lane addresses recomputed per call: the MR / GN / FR kernels); 2 = 0 here (w8::kNodeOneTile)
+#endif
+#ifndef GAUDI_MB_TAIL
+#define GAUDI_MB_TAIL w8::kTailRuntime  // w8::kTailOne: one tail k-step compiled in (the N1 kernels; timings only -- the numerics' tail = 0 cases need four)
 #endif
 #ifndef GAUDI_MB_MAXNT
-#define GAUDI_MB_MAXNT 3  // column tiles per pass the fp16 form is instantiated for (2: the resident kernels; N = 40 runs are skipped)
+#define GAUDI_MB_MAXNT 3  // column tiles per pass the fp16 form is instantiated for (2: the resident kernels; N = 40 runs are skipped; 1: the N1 kernels)
 #endif
 
 template <int HP, int V>
@@ -43,11 +46,20 @@ struct Sel<HP, 3> {
                                               w8::NodeStampH* ns = nullptr) {
     const int nct = N <= 16 ? 1 : N <= 32 ? 2 : 3;
     w8::NodeCtxH cx{winv, split + 96, seq ? split + 96 : split + 96 + w8::nh_split_floats(HP, nct), tw, split};
-    if (Wb >= 0)
-      w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
+    // GAUDI_NODE_ABLATE & 8 (timings only): a wave without a second output tile (13 tiles: waves 5-7; 12: waves 4-7) runs a body
+    // with ONE tile -- no second-tile loads (all lanes out of range in the shipped form) and no second-tile matrix instructions
+    if ((GAUDI_NODE_ABLATE & 8) && HP / 16 > 8 && wave + 8 >= HP / 16) {
+      if (Wb >= 0)
+        w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL, 1>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx,
+                                                                                                          *pf, nextW, nullptr, nullptr, ns);
+      else
+        w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL, 1>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane,
+                                                                                                           cx, *pf, nextW, nullptr, nullptr, ns);
+    } else if (Wb >= 0)
+      w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
                                                                                     nullptr, nullptr, ns);
     else
-      w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
+      w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
                                                                                      nullptr, nullptr, ns);
   }
 };
@@ -332,7 +344,8 @@ void timing() {
 }
 
 int main(int argc, char**) {
-  printf("depth %d, column tiles <= %d, ablation %d\n", GAUDI_NODE_DEPTH, GAUDI_MB_MAXNT, GAUDI_NODE_ABLATE);
+  printf("depth %d, column tiles <= %d, tail %s, ablation %d\n", GAUDI_NODE_DEPTH, GAUDI_MB_MAXNT,
+         GAUDI_MB_TAIL == w8::kTailOne ? "one step compiled in" : "run time", GAUDI_NODE_ABLATE);
   if (argc > 1) {  // any argument: the fp16 form's timings only
     timing<3>();
     return 0;
