@@ -53,6 +53,17 @@ class AtomTables(C.Structure):
                 ("c_elem", C.c_int32), ("h_bond", C.c_double)]
 
 
+class PerceptionTables(C.Structure):
+    """include/gaudi_hip.h: gaudi_perception_tables."""
+    _fields_ = [("n_elems", C.c_int32), ("cov_radius", C.c_double * 8), ("h_elem", C.c_int32), ("c_elem", C.c_int32),
+                ("b_elem", C.c_int32), ("n_types", C.c_int32), ("ring_size", C.c_int32 * 16), ("ring_elem", (C.c_int32 * 6) * 16),
+                ("no_orientation", C.c_int32 * 16), ("db_type", C.c_int32), ("dhdb_type", C.c_int32)]
+
+
+RINGS_MAX_ATOMS, RINGS_MAX_HEAVY, RINGS_MAX_RINGS = 384, 192, 32  # include/gaudi_hip.h: GAUDI_RINGS_MAX_*
+RINGS_USE_H = 1
+RINGS_OK, RINGS_NO_RINGS, RINGS_BAD_TYPE, RINGS_NOT_A_BASIS, RINGS_OVERFLOW = 0, 1, 2, 3, 4
+
 ATOMS_MAX_ATOMS = 384  # include/gaudi_hip.h: GAUDI_ATOMS_MAX_ATOMS / GAUDI_ATOMS_MAX_BONDS
 ATOMS_MAX_BONDS = 384
 ATOMS_PLACE_H, ATOMS_FINGERPRINT = 1, 2
@@ -103,6 +114,11 @@ EXPORTS = {
     "gaudi_rings_to_atoms": (C.c_int, [C.c_void_p, C.POINTER(RingTables), C.POINTER(AtomTables), C.c_int, C.c_int, FP, IP, IP,
                                        C.c_int, C.c_int, C.c_int, IP, IP, DP, DP, IP, IP, IP, C.POINTER(C.c_uint64)]),
     "gaudi_atoms_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_atoms_to_rings": (C.c_int, [C.c_void_p, C.POINTER(PerceptionTables), C.c_int, C.c_int, DP, IP, IP, C.c_int, C.c_double,
+                                       C.c_int, IP, IP, IP, IP, IP, DP, IP, DP, C.POINTER(C.c_uint8)]),
+    "gaudi_rings_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_host_atoms_to_rings": (C.c_int, [C.POINTER(PerceptionTables), C.c_int, C.c_int, DP, IP, IP, C.c_int, C.c_double,
+                                            C.c_int, IP, IP, IP, IP, IP, DP, IP, DP, C.POINTER(C.c_uint8)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -172,6 +188,7 @@ _NLL_EXPORTS = ("gaudi_edm_nll", "gaudi_predictor_loss_grad", "gaudi_predictor_g
 _GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")  # ... and the time-grid chains
 _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fused value targets
 _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
+_RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and the way back, atoms -> graph of rings
 _KEY_EXPORTS = ("gaudi_last_kernel_key",)  # ... and the name of the kernel a launch ran
 
 _lib = None
@@ -200,7 +217,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -209,6 +226,38 @@ def load_library() -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def rings_outputs(B: int, max_rings: int) -> dict:
+    """The nine output arrays of gaudi_atoms_to_rings / gaudi_host_atoms_to_rings, in argument order."""
+    M = int(max_rings)
+    return dict(status=np.zeros(B, np.int32), n_rings=np.zeros(B, np.int32), ring_size=np.zeros((B, M), np.int32),
+                ring_atoms=np.full((B, M, 6), -1, np.int32), ring_type=np.zeros((B, M), np.int32),
+                centre=np.zeros((B, M, 3), np.float64), n_orient=np.zeros((B, M), np.int32),
+                orient=np.zeros((B, M, 2, 3), np.float64), adj=np.zeros((B, M, M), np.uint8))
+
+
+def rings_args(xyz, elem, n_atoms, flags, covalency_factor, max_rings, out):
+    """The arguments both entry points share after the tables."""
+    assert xyz.dtype == np.float64 and elem.dtype == np.int32 and n_atoms.dtype == np.int32
+    assert xyz.flags["C_CONTIGUOUS"] and elem.flags["C_CONTIGUOUS"] and n_atoms.flags["C_CONTIGUOUS"]
+    B, A = xyz.shape[0], xyz.shape[1]
+    assert xyz.shape == (B, A, 3) and elem.shape == (B, A) and n_atoms.shape == (B,)
+    ip = lambda a: a.ctypes.data_as(IP)
+    dp = lambda a: a.ctypes.data_as(DP)
+    return (B, A, dp(xyz), ip(elem), ip(n_atoms), int(flags), float(covalency_factor), int(max_rings), ip(out["status"]),
+            ip(out["n_rings"]), ip(out["ring_size"]), ip(out["ring_atoms"]), ip(out["ring_type"]), dp(out["centre"]),
+            ip(out["n_orient"]), dp(out["orient"]), out["adj"].ctypes.data_as(C.POINTER(C.c_uint8)))
+
+
+def host_atoms_to_rings(tables, xyz, elem, n_atoms, flags=0, covalency_factor=1.3, max_rings=RINGS_MAX_RINGS) -> dict:
+    """gaudi_host_atoms_to_rings (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = rings_outputs(xyz.shape[0], max_rings)
+    rc = lib.gaudi_host_atoms_to_rings(C.byref(tables), *rings_args(xyz, elem, n_atoms, flags, covalency_factor, max_rings, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_atoms_to_rings failed ({rc})")
+    return out
 
 
 def fptr(a: np.ndarray | None):

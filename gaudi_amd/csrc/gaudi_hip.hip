@@ -109,6 +109,7 @@ struct gaudi_handle {
       d_pred, d_tw, d_stash, d_chain, d_sx, d_stype, d_sn, d_sflags, d_sdist, d_sadj, d_saux, d_stab, d_as, d_ncols, d_soff,
       d_sidx, d_gnode, d_rowmap, d_compmol, d_ncomp, d_clock, d_gcoef, d_gidx, d_zt;  // d_gcoef / d_gidx / d_zt: time-grid chains
   DevBuf d_atoms[9];  // gaudi_rings_to_atoms (atoms.inc): its outputs and its tables
+  DevBuf d_rings[13];  // gaudi_atoms_to_rings (rings.inc): its three inputs, its tables and its nine outputs
   DevBuf d_vtpar, d_vttrace, d_vtdev;  // value targets: per-molecule parameter rows, the guidance trace, the VtDev that names them
   // Value-target call in flight (gaudi_sample_target / gaudi_step_target set it around sample_impl / run_chain; nullptr otherwise):
   // run_chain stages the parameter rows of ITS molecules (request index = b0 + k), the window flags and the trace, and keeps
@@ -218,7 +219,7 @@ struct gaudi_handle {
       ms = 0.0;
       n = 0;
     }
-  } prof_log, stab_log, atoms_log;
+  } prof_log, stab_log, atoms_log, rings_log;
   long long prof_steps = 0;
 #ifdef GAUDI_STAMPS
   DevBuf d_stamps;
@@ -1574,6 +1575,7 @@ void gaudi_destroy(gaudi_handle* h) {
   h->prof_log.reset(true);
   h->stab_log.reset(true);
   h->atoms_log.reset(true);
+  h->rings_log.reset(true);
   DevBuf* bufs[] = {&h->edm_w, &h->pred_w, &h->coef_d, &h->edm_w4, &h->pred_w4, &h->edm_ws, &h->pred_ws, &h->d_mask, &h->d_order, &h->d_edges, &h->d_emask, &h->d_npairs,
                     &h->d_seg, &h->d_zin, &h->d_zout, &h->d_t, &h->d_x, &h->d_h, &h->d_noise, &h->d_nan, &h->d_dpred,
                     &h->d_pred, &h->d_tw, &h->d_stash, &h->d_chain, &h->d_sx, &h->d_stype, &h->d_sn,
@@ -1581,6 +1583,7 @@ void gaudi_destroy(gaudi_handle* h) {
                     &h->d_gnode, &h->d_rowmap, &h->d_compmol, &h->d_ncomp, &h->d_gcoef, &h->d_gidx, &h->d_zt, &h->d_vtpar, &h->d_vttrace, &h->d_vtdev};
   for (DevBuf* b : bufs) b->release();
   for (DevBuf& b : h->d_atoms) b.release();
+  for (DevBuf& b : h->d_rings) b.release();
   pt_release(h);
   et_release(h);
   h->p_pred.release();
@@ -2930,6 +2933,7 @@ int gaudi_profile_reset(gaudi_handle* h, int enable) {
   h->prof_log.reset(false);
   h->stab_log.reset(false);
   h->atoms_log.reset(false);
+  h->rings_log.reset(false);
   h->prof_steps = 0;
   h->prof = enable != 0;
   return GAUDI_OK;
@@ -2964,5 +2968,6 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 #include "pred_train_host.inc"
 #include "stability.inc"
 #include "atoms.inc"
+#include "rings.inc"
 #include "nll_host.inc"
 #include "edm_train_host.inc"

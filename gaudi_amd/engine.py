@@ -758,6 +758,22 @@ class Engine:
         self._check(rc, "gaudi_rings_to_atoms")
         return out
 
+    def rings_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_atoms_to_rings since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_rings_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_rings_profile_get")
+        return n.value, ms.value
+
+    def atoms_to_rings(self, tables, xyz, elem, n_atoms, flags=0, covalency_factor=1.3, max_rings=_lib.RINGS_MAX_RINGS):
+        """gaudi_atoms_to_rings on packed arrays (xyz [B,A,3] float64, elem [B,A] int32, n_atoms [B] int32) -> dict of the raw
+        output arrays; gaudi_amd.goa2gor.atoms_to_rings is the interface on top."""
+        out = _lib.rings_outputs(xyz.shape[0], max_rings)
+        rc = self.lib.gaudi_atoms_to_rings(self.h, C.byref(tables), *_lib.rings_args(xyz, elem, n_atoms, flags, covalency_factor,
+                                                                                     max_rings, out))
+        self._check(rc, "gaudi_atoms_to_rings")
+        return out
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

@@ -87,7 +87,7 @@ const char* gaudi_last_warning(const gaudi_handle* h);
 int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3 -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -429,6 +429,59 @@ int gaudi_rings_to_atoms(gaudi_handle* h, const gaudi_ring_tables* tables, const
 /* Number of gaudi_rings_to_atoms launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_atoms_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Graph of atoms -> graph of rings: the inverse of gaudi_rings_to_atoms, for B molecules in one launch. ----
+ * What data/aromatic_dataloader.py:131-152 (AromaticDataset.get_rings) computes per molecule in Python: bonds from covalent radii
+ * (utils/molgraph.py:37-80), the rings, their types, centres and orientation candidates (utils/ring_graph.py:12-93) and the
+ * ring-ring adjacency (:120-128).  Constants for one dataset: */
+#define GAUDI_RINGS_MAX_ATOMS 384  /* atoms of one molecule: everything gaudi_rings_to_atoms can emit fits */
+#define GAUDI_RINGS_MAX_HEAVY 192  /* non-hydrogen atoms */
+#define GAUDI_RINGS_MAX_RINGS 32
+typedef struct {
+  int32_t n_elems;                 /* len(ATOMS_LIST[dataset]) <= 8                                                    */
+  double cov_radius[8];            /* covalent radius of each element (utils/const.py), Angstrom                       */
+  int32_t h_elem, c_elem, b_elem;  /* ATOMS_LIST[dataset].index("H") / ("C") / ("B"); b_elem = -1 where there is no B  */
+  int32_t n_types;                 /* len(RINGS_LIST[dataset]) <= 16                                                   */
+  int32_t ring_size[16];           /* ring atoms of the type: 4, 5 or 6; 0 = not a ring (".")                          */
+  int32_t ring_elem[16][6];        /* its elements (RINGS_DICT) as indices into ATOMS_LIST[dataset], in any order       */
+  int32_t no_orientation[16];      /* 1: NO_ORIENTATION_RINGS -- the orientation candidate is the centre itself         */
+  int32_t db_type, dhdb_type;      /* the two types that share CCBCCB, told apart by the H on B; -1 / -1 where absent   */
+} gaudi_perception_tables;
+
+#define GAUDI_RINGS_USE_H 1        /* flag: hydrogens count when Db / DhDb is decided (skip_hydrogen=False); default: they
+                                      take no part at all (the dataset path, skip_hydrogen=True), and CCBCCB is Db      */
+/* status_out codes: 0 = perceived; otherwise the molecule has n_rings = 0. */
+#define GAUDI_RINGS_OK 0
+#define GAUDI_RINGS_NO_RINGS 1     /* no heavy atom, or a heavy-atom graph without a cycle                                        */
+#define GAUDI_RINGS_BAD_TYPE 2     /* a ring whose element multiset is no ring type of the dataset (NotImplementedError / ValueError) */
+#define GAUDI_RINGS_NOT_A_BASIS 3  /* the chordless cycles of 4..6 atoms are not THE minimum cycle basis: the reference's answer
+                                      depends on networkx's tie-breaking or holds a ring it cannot type                           */
+#define GAUDI_RINGS_OVERFLOW 4     /* NOT a reference error: more than 384 atoms, 192 heavy atoms or max_rings rings              */
+
+/* xyz [B][A][3] float64, elem [B][A] (indices into ATOMS_LIST[dataset]), n_atoms [B] in 0..A.  One 64-lane wave per molecule:
+ *  - heavy atoms i < j are bonded iff sqrt(dx^2 + dy^2 + dz^2) <= (r_i + r_j) * covalency_factor, in float64 without contraction;
+ *    the adjacency is kept as bit rows, so a heavy atom may have any number of neighbours;
+ *  - the rings are the chordless cycles of 4 to 6 heavy atoms.  There must be no triangle, they must number E - V + C
+ *    (C = components) and be independent over GF(2); then every minimum cycle basis consists of exactly these cycles, and networkx.minimum_cycle_basis returns them as
+ *    a set.  Otherwise GAUDI_RINGS_NOT_A_BASIS;
+ *  - rings are ordered ascending by their sorted tuple of atom indices (the reference's order is networkx's);
+ *  - type: the first type of RINGS_LIST[dataset] with the ring's element multiset; CCBCCB is Db, and DhDb only with
+ *    GAUDI_RINGS_USE_H when a B atom of the ring has an H within (r_B + r_H) * covalency_factor.  (The reference looks at the
+ *    first B in networkx's cycle order only.)
+ * Outputs, rows of max_rings <= GAUDI_RINGS_MAX_RINGS entries per molecule, zero beyond n_rings:
+ *   status_out [B], n_rings_out [B], ring_size_out [B][max_rings], ring_type_out [B][max_rings];
+ *   ring_atoms_out [B][max_rings][6]: atom indices ascending, padded with -1 (all -1 beyond n_rings);
+ *   centre_out [B][max_rings][3]: the float64 mean of the ring atoms, summed in ascending atom index;
+ *   n_orient_out [B][max_rings], orient_out [B][max_rings][2][3]: the centre for a NO_ORIENTATION type, otherwise the
+ *     coordinates of the ring's non-carbon atoms in ascending index (at most 2);
+ *   adj_out [B][max_rings][max_rings]: 1 where two different rings share an atom (get_rings_adj).
+ * A molecule that fails never disturbs the others of the batch. */
+int gaudi_atoms_to_rings(gaudi_handle* h, const gaudi_perception_tables* tables, int B, int A, const double* xyz,
+                         const int32_t* elem, const int32_t* n_atoms, int flags, double covalency_factor, int max_rings,
+                         int32_t* status_out, int32_t* n_rings_out, int32_t* ring_size_out, int32_t* ring_atoms_out,
+                         int32_t* ring_type_out, double* centre_out, int32_t* n_orient_out, double* orient_out, uint8_t* adj_out);
+/* Number of gaudi_atoms_to_rings launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
+int gaudi_rings_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -440,6 +493,12 @@ int gaudi_host_schedule(int T, float noise_power /* 0 = cosine */, float noise_p
  * a [n][3][3] (the lower triangles are read) -> e_out [n][3][3], e_out[q][c][k] = component c of the eigenvector of the k-th
  * smallest eigenvalue, with the signs numpy.linalg.eigh (LAPACK dsyevd, 'L') returns. */
 int gaudi_host_eigh3(int n, const double* a, double* e_out);
+/* gaudi_atoms_to_rings without a handle: the same source text (csrc/rings.inc: perceive_rings) compiled for the host and run
+ * serially, one molecule after the other.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_atoms_to_rings(const gaudi_perception_tables* tables, int B, int A, const double* xyz, const int32_t* elem,
+                              const int32_t* n_atoms, int flags, double covalency_factor, int max_rings, int32_t* status_out,
+                              int32_t* n_rings_out, int32_t* ring_size_out, int32_t* ring_atoms_out, int32_t* ring_type_out,
+                              double* centre_out, int32_t* n_orient_out, double* orient_out, uint8_t* adj_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),

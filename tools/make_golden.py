@@ -2055,6 +2055,219 @@ def g30_gor2goa():
          twin_x=TX, twin_types=TTY, twin_iso_class=np.array(tcls, np.int32))
 
 
+def _g31_hexes(centres, r=1.40):
+    """Carbon skeleton of fused regular hexagons (pointy top) around the given 2-D centres: shared corners once."""
+    pts = []
+    for cx, cy in centres:
+        for k in range(6):
+            p = (cx + r * np.cos(np.pi / 6 + k * np.pi / 3), cy + r * np.sin(np.pi / 6 + k * np.pi / 3))
+            if not any(abs(p[0] - q[0]) + abs(p[1] - q[1]) < 1e-6 for q in pts):
+                pts.append(p)
+    return np.array(pts)
+
+
+def g31_goa2gor():
+    """Graph of atoms -> graph of rings: the reference's own get_connectivity_matrix / get_rings / get_rings_adj (through xyz files
+    and load_xyz) and AromaticDataset.get_all on the atoms g30's molecules were built into, plus hand-written specials.
+
+    Inputs: every non-raising molecule of g30, its reference atoms lifted to 3-D (z = 0), template H (parked at the origin) dropped,
+    under its own seeded rotation and translation, coordinates rounded to float32 values (stored as float32: the size limit of a
+    committed fixture; the reference reads them back exactly from `repr`-precision xyz files).  Recorded per molecule: the inputs,
+    `threw`, `expect` (specials: the status the kernel must give, else -1), the rings in ascending order of their sorted atom tuples
+    (`g30_index`: the g30 molecule it was built from, else -1; atom sets, types, float64 centres, the float32 x of get_rings, orientation candidates as atom indices -- the reference returns
+    the atoms' own coordinates, asserted here; -1 = the centre), the ring adjacency, `basis_ok` (networkx's minimum cycle basis
+    equals the set of chordless cycles of 4..6 atoms and their number is E - V + C) and `margin` (smallest |distance - cutoff| over
+    heavy pairs).  For 8 hetero and 4 cata molecules: the tensors of AromaticDataset.get_all with normalize=True.
+    Tie filter: margin < 1e-9 is dropped, at most 10 %.  Prints the rate of the reference's get_rings path on this CPU."""
+    import random
+    import tempfile
+    import time
+    import networkx as nx
+    import pandas as pd
+    from data import aromatic_dataloader as adl
+    from data.mol import load_xyz
+    from utils.const import __COV_RADII__
+    from utils.molgraph import get_connectivity_matrix, get_edges
+    from utils.ring_graph import get_rings, get_rings_adj
+    g30 = np.load(os.path.join(OUT, "g30_gor2goa.npz"))
+    rng = np.random.default_rng(3100)
+    cands = []  # (dataset, symbols, xyz float64 of float32 values, use_h, expect)
+
+    def place(xy_or_xyz):
+        p = np.asarray(xy_or_xyz, np.float64)
+        if p.shape[1] == 2:
+            p = np.concatenate([p, np.zeros((len(p), 1))], 1)
+        return ((p @ _rand_rot(rng)) + rng.uniform(-4, 4, 3)).astype(np.float32).astype(np.float64)
+
+    for m in range(len(g30["n"])):
+        if g30["threw"][m]:
+            continue
+        ds = "hetro" if g30["hetro"][m] else "cata"
+        a0, a1 = g30["atom_off"][m], g30["atom_off"][m + 1]
+        ty, xy = g30["ref_types"][a0:a1], g30["ref_atoms"][a0:a1]
+        keep = ty != adl.ATOMS_LIST[ds].index("H")
+        cands.append((ds, [adl.ATOMS_LIST[ds][t] for t in ty[keep]], place(xy[keep]), False, -1))
+    g30_of = [m for m in range(len(g30["n"])) if not g30["threw"][m]]
+    n_g30 = len(cands)
+    OK, NO_RINGS, BAD_TYPE, NOT_A_BASIS, OVERFLOW = range(5)
+    d = 1.40 * np.sqrt(3.0)
+    ring = lambda n, r, ph=0.0: np.array([[r * np.cos(ph + 2 * np.pi * k / n), r * np.sin(ph + 2 * np.pi * k / n)] for k in range(n)])
+    hexa = ring(6, 1.40)
+    cata_sp = lambda pts, expect, sym=None: cands.append(("cata", sym or ["C"] * len(pts), place(pts), False, expect))
+    cata_sp(hexa, OK)                                                                       # benzene
+    cata_sp(np.concatenate([hexa, ring(6, 2.49)]), OK, ["C"] * 6 + ["H"] * 6)               # benzene with its hydrogens
+    cands.append(("hetro", ["C"] * 4, place(ring(4, 1.03)), False, OK))                     # a single Cbd ring
+    db = ["C", "C", "B", "C", "C", "B"]
+    hc = ring(6, 2.49)[[0, 1, 3, 4]]
+    cands.append(("hetro", db + ["H"] * 4, place(np.concatenate([hexa, hc])), True, OK))    # Db: H on the carbons only
+    cands.append(("hetro", db + ["H"] * 6, place(np.concatenate([hexa, hc, ring(6, 2.59)[[2, 5]]])), True, OK))  # DhDb: H on both B
+    cata_sp(_g31_hexes([(0, 0), (d, 0), (d / 2, 1.5 * 1.40), (d / 2, -1.5 * 1.40)]), OK)    # pyrene: three rings meet at an atom
+    cata_sp(np.concatenate([hexa, _g31_hexes([(10, 0), (10 + d, 0)])]), OK)                 # two molecules in one record
+    cata_sp([[1.21 * k, 0.7 * (k % 2)] for k in range(5)], NO_RINGS)                        # a chain
+    cands.append(("hetro", ["C"] * 5, place(ring(5, 1.2)), False, BAD_TYPE))                # an all-carbon five-ring
+    cata_sp(ring(7, 1.613), NOT_A_BASIS)                                                    # a 7-ring
+    cata_sp(_g31_hexes([(d * k, 0) for k in range(32)]), OK)                                # the capacity edge
+    cata_sp(_g31_hexes([(d * k, 0) for k in range(33)]), OVERFLOW)                          # one ring beyond it
+
+    def reference(ds, sym, xyz, use_h, tmp, name):
+        path = os.path.join(tmp, name + ".xyz")
+        with open(path, "w") as f:
+            f.write(f"{len(sym)}\n\n")
+            for s_, p in zip(sym, xyz.tolist()):
+                f.write(f"{s_} {p[0]!r} {p[1]!r} {p[2]!r}\n")
+        mol = load_xyz(path)
+        assert all(a.x == p[0] and a.y == p[1] and a.z == p[2] for a, p in zip(mol.atoms, xyz.tolist()))
+        con = get_connectivity_matrix(mol.atoms, skip_hydrogen=not use_h)
+        g = nx.Graph(get_edges(con))
+        heavy = [i for i, s_ in enumerate(sym) if s_ != "H"]
+        gh = nx.Graph()
+        gh.add_nodes_from(heavy)
+        gh.add_edges_from((i, j) for i, j in get_edges(con) if sym[i] != "H" and sym[j] != "H")
+        basis = {frozenset(c) for c in nx.minimum_cycle_basis(gh)}
+        short = {frozenset(c) for c in nx.chordless_cycles(gh, length_bound=6) if len(c) >= 4}
+        cyclo = gh.number_of_edges() - gh.number_of_nodes() + nx.number_connected_components(gh)
+        basis_ok = basis == short and len(short) == cyclo
+        margin = np.inf
+        for a in range(len(heavy)):
+            for b_ in range(a + 1, len(heavy)):
+                i, j = heavy[a], heavy[b_]
+                cut = (__COV_RADII__[sym[i]] + __COV_RADII__[sym[j]]) * 1.3
+                margin = min(margin, abs(float(np.sqrt(((xyz[i] - xyz[j]) ** 2).sum())) - cut))
+        rec = dict(basis_ok=basis_ok, margin=margin, threw=False, rings=[])
+        try:
+            knots = get_rings(mol.atoms, g)
+            adj = get_rings_adj(knots).numpy()
+            x32 = torch.tensor([k.get_coord() for k in knots], dtype=adl.DTYPE).numpy().reshape(-1, 3)
+            types = [adl.RINGS_LIST[ds].index(k.cycle_type) for k in knots]
+        except Exception:
+            rec["threw"] = True
+            return rec
+        order = sorted(range(len(knots)), key=lambda r: tuple(sorted(a.index for a in knots[r].atoms)))
+        for r in order:
+            k = knots[r]
+            idx = sorted(a.index for a in k.atoms)
+            oi = []
+            for o in k.orientation:
+                hit = [i for i in idx if [xyz[i][0], xyz[i][1], xyz[i][2]] == list(o)]
+                if hit:
+                    assert len(hit) == 1 and sym[hit[0]] != "C"
+                    oi.append(hit[0])
+                else:
+                    assert list(o) == k.get_coord()
+                    oi.append(-1)
+            rec["rings"].append(dict(atoms=idx, type=types[r], centre=k.get_coord(), x32=x32[r], orient=oi))
+        rec["adj"] = adj[np.ix_(order, order)].astype(np.uint8)
+        return rec
+
+    kept, n_drop = [], 0
+    with tempfile.TemporaryDirectory() as tmp:
+        t_ref, n_ref = 0.0, 0
+        for m, (ds, sym, xyz, use_h, expect) in enumerate(cands):
+            rec = reference(ds, sym, xyz, use_h, tmp, f"m{m}")
+            if rec["margin"] < 1e-9:
+                if expect >= 0:
+                    raise RuntimeError("a special molecule of g31 sits on a tie: move it")
+                n_drop += 1
+                continue
+            if m < n_g30:  # the rate of the reference's path (get_mol + get_rings + get_rings_adj), file already written
+                t0 = time.perf_counter()
+                try:
+                    mol = load_xyz(os.path.join(tmp, f"m{m}.xyz"))
+                    kn = get_rings(mol.atoms, nx.Graph(get_edges(get_connectivity_matrix(mol.atoms, skip_hydrogen=True))))
+                    get_rings_adj(kn)
+                except Exception:
+                    pass
+                t_ref += time.perf_counter() - t0
+                n_ref += 1
+            rec.update(ds=ds, sym=sym, xyz=xyz, use_h=use_h, expect=expect, name=f"m{m}", g30=g30_of[m] if m < n_g30 else -1)
+            kept.append(rec)
+        print(f"g31: dropped {n_drop} of {len(cands)} candidates on ties; cap {len(cands) // 10}")
+        assert n_drop * 10 <= len(cands), "tie filter dropped more than 10 %"
+        print(f"g31: reference get_rings path on this CPU: {n_ref / t_ref:.1f} molecules/s over {n_ref} molecules")
+        good = [r for r in kept if r["basis_ok"] and not r["threw"] and r["expect"] <= 0 and r["rings"]]
+        n_ok = sum(r["basis_ok"] and not r["threw"] for r in kept)
+        n_ok_h = sum(r["basis_ok"] and not r["threw"] and r["ds"] == "hetro" for r in kept)
+        n_nb = sum(not r["basis_ok"] for r in kept)
+        print(f"g31: {len(kept)} molecules kept, {n_ok} with basis_ok ({n_ok_h} hetero), {n_nb} without, "
+              f"{sum(r['threw'] for r in kept)} raise, smallest margin {min(r['margin'] for r in kept):.2e}")
+        assert n_ok >= 100 and n_ok_h >= 40 and n_nb >= 5
+
+        # AromaticDataset.get_all on a subset, normalize=True, two targets
+        out = {}
+        for ds, want, MN in (("hetro", 8, 10), ("cata", 4, 11)):
+            sub = [r for r in good if r["ds"] == ds and not r["use_h"] and 2 <= len(r["rings"]) <= MN]
+            sub = sub[:: max(1, len(sub) // want)][:want]
+            assert len(sub) == want
+            tg = np.random.default_rng(3101).normal(2.0, 1.5, (want, 2)).astype(np.float32)
+            df = pd.DataFrame(dict(molecule=[r["name"] for r in sub], n_rings=[len(r["rings"]) for r in sub], gap=tg[:, 0], ip=tg[:, 1]))
+
+            class A:
+                pass
+            args = A()
+            args.rings_graph, args.normalize, args.max_nodes, args.dataset, args.target_features = True, True, MN, ds, "gap,ip"
+            args.sample_rate, args.df_train, args.df_val = 1, df, df
+            old = adl.get_paths
+            adl.get_paths = lambda a: (None, tmp)
+            try:
+                dset = adl.AromaticDataset(args, "train")
+                random.seed(31)
+                rows = [dset[i] for i in range(want)]
+            finally:
+                adl.get_paths = old
+            out[ds] = dict(idx=np.array([kept.index(r) for r in sub], np.int32), max_nodes=MN, targets=tg,
+                           mean=dset.mean.numpy(), std=dset.std.numpy(),
+                           x=np.stack([r[0].numpy() for r in rows]).astype(np.float32), node_mask=np.stack([r[1].numpy() for r in rows]).astype(np.float32),
+                           edge_mask=np.stack([r[2].numpy() for r in rows]).astype(np.float32),
+                           node_features=np.stack([r[3].numpy() for r in rows]).astype(np.float32), y=np.stack([r[4].numpy() for r in rows]).astype(np.float32))
+
+    aoff = np.concatenate([[0], np.cumsum([len(r["sym"]) for r in kept])]).astype(np.int32)
+    roff = np.concatenate([[0], np.cumsum([len(r["rings"]) for r in kept])]).astype(np.int32)
+    joff = np.concatenate([[0], np.cumsum([len(r["rings"]) ** 2 for r in kept])]).astype(np.int32)
+    rings = [q for r in kept for q in r["rings"]]
+    ra = np.full((len(rings), 6), -1, np.int16)
+    ro = np.full((len(rings), 2), -2, np.int16)  # -2: no such candidate, -1: the centre
+    for i, q in enumerate(rings):
+        ra[i, :len(q["atoms"])] = q["atoms"]
+        assert 1 <= len(q["orient"]) <= 2
+        ro[i, :len(q["orient"])] = q["orient"]
+    arrs = dict(
+        hetro=np.array([r["ds"] == "hetro" for r in kept]), use_h=np.array([r["use_h"] for r in kept]),
+        expect=np.array([r["expect"] for r in kept], np.int8), g30_index=np.array([r["g30"] for r in kept], np.int16), threw=np.array([r["threw"] for r in kept]),
+        basis_ok=np.array([r["basis_ok"] for r in kept]), margin=np.array([r["margin"] for r in kept], np.float32),
+        atom_off=aoff, xyz=np.concatenate([r["xyz"] for r in kept]).astype(np.float32),
+        elem=np.concatenate([[adl.ATOMS_LIST[r["ds"]].index(s_) for s_ in r["sym"]] for r in kept]).astype(np.int8),
+        ring_off=roff, ring_atoms=ra, ring_type=np.array([q["type"] for q in rings], np.int8),
+        centre=np.array([q["centre"] for q in rings], np.float64), x32=np.array([q["x32"] for q in rings], np.float32),
+        orient=ro, adj_off=joff, adj=np.concatenate([r["adj"].reshape(-1) for r in kept if r["rings"]]).astype(np.uint8),
+        ref_rate=np.array(n_ref / t_ref))
+    for ds, o in out.items():
+        for k, v in o.items():
+            arrs[f"ga_{ds}_{k}"] = np.asarray(v)
+    save("g31_goa2gor", **arrs)
+    size, cap = os.path.getsize(os.path.join(OUT, "g31_goa2gor.npz")), os.path.getsize(os.path.join(OUT, "g30_gor2goa.npz"))
+    assert size <= cap, f"g31 is {size} bytes, g30 {cap}"
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -2080,8 +2293,9 @@ def g8_checkpoint_roundtrip():
 
 if __name__ == "__main__":
     fns = dict(g1=g1_schedule, g2=g2_masks, g3=g3_phi, g4=g4_predictor, g5=g5_steps, g6=g6_decode,
-               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target, g30=g30_gor2goa)
+               g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target, g30=g30_gor2goa, g31=g31_goa2gor)
     fns["g30_gor2goa"] = g30_gor2goa  # (also under its full name)
-    which = sys.argv[1:] or [k for k in fns if k != "g30_gor2goa"]
+    fns["g31_goa2gor"] = g31_goa2gor
+    which = sys.argv[1:] or [k for k in fns if k not in ("g30_gor2goa", "g31_goa2gor")]
     for w in which:
         fns[w]()

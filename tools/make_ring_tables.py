@@ -19,6 +19,7 @@ utils/ring_graph.py:9, data/aromatic_dataloader.py:26-30), keyed by ring symbol:
     goa.no_orientation        ring types turned towards a fused ring instead of an orientation node
     goa.extra_angle[sym]      what gor2goa adds to that angle;   goa.template_h[sym]: ring atoms that carry a template H
     goa.atoms[dataset]        ATOMS_LIST;   goa.h_bond: X-H distance used when hydrogens are placed (ours, not the reference's)
+    goa.cov_radii[element]    covalent radii (utils/const.py) of the elements of ATOMS_LIST: bond perception of atoms -> rings
 """
 import json
 import os
@@ -38,6 +39,7 @@ from data import gor2goa as G  # noqa: E402
 from data.aromatic_dataloader import ATOMS_LIST, RINGS_LIST  # noqa: E402
 from data.ring import RINGS_DICT  # noqa: E402
 from utils.ring_graph import NO_ORIENTATION_RINGS  # noqa: E402
+from utils.const import __COV_RADII__  # noqa: E402
 from utils import helpers as H  # noqa: E402
 
 out = dict(rings={}, dist_lo={}, dist_hi={}, a3={}, a4={}, n_nodes={}, min_dist={})
@@ -71,6 +73,7 @@ out["goa"] = dict(
     template_h={"Bl": [4], "Pl": [4], "DhDb": [2, 5]},
     atoms={ds: list(ATOMS_LIST[ds]) for ds in ("cata", "peri", "hetro")},
     h_bond=1.09,
+    cov_radii={e: float(__COV_RADII__[e]) for e in ATOMS_LIST["hetro"]},
 )
 path = os.path.join(ROOT, "gaudi_amd", "data", "ring_tables.json")
 with open(path, "w") as f:
