@@ -60,6 +60,12 @@ class PerceptionTables(C.Structure):
                 ("no_orientation", C.c_int32 * 16), ("db_type", C.c_int32), ("dhdb_type", C.c_int32)]
 
 
+class ValenceTables(C.Structure):
+    """include/gaudi_hip.h: gaudi_valence_tables."""
+    _fields_ = [("n_elems", C.c_int32), ("n_options", (C.c_int32 * 5) * 8), ("option", (((C.c_int32 * 2) * 2) * 5) * 8),
+                ("h_elem", C.c_int32), ("c_elem", C.c_int32)]
+
+
 RINGS_MAX_ATOMS, RINGS_MAX_HEAVY, RINGS_MAX_RINGS = 384, 192, 32  # include/gaudi_hip.h: GAUDI_RINGS_MAX_*
 RINGS_USE_H = 1
 RINGS_OK, RINGS_NO_RINGS, RINGS_BAD_TYPE, RINGS_NOT_A_BASIS, RINGS_OVERFLOW = 0, 1, 2, 3, 4
@@ -67,6 +73,10 @@ RINGS_OK, RINGS_NO_RINGS, RINGS_BAD_TYPE, RINGS_NOT_A_BASIS, RINGS_OVERFLOW = 0,
 ATOMS_MAX_ATOMS = 384  # include/gaudi_hip.h: GAUDI_ATOMS_MAX_ATOMS / GAUDI_ATOMS_MAX_BONDS
 ATOMS_MAX_BONDS = 384
 ATOMS_PLACE_H, ATOMS_FINGERPRINT = 1, 2
+
+BONDS_MAX_ATOMS, BONDS_MAX_HEAVY, BONDS_MAX_BONDS, BONDS_MAX_CHARGED = 384, 192, 384, 4  # include/gaudi_hip.h: GAUDI_BONDS_*
+(BONDS_OK, BONDS_NO_STRUCTURE, BONDS_CAPPED, BONDS_NOT_CONNECTED, BONDS_BAD_VALENCE, BONDS_BAD_INPUT, BONDS_OVERFLOW,
+ BONDS_EMPTY, BONDS_GAVE_UP) = range(9)
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
@@ -119,6 +129,11 @@ EXPORTS = {
     "gaudi_rings_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_host_atoms_to_rings": (C.c_int, [C.POINTER(PerceptionTables), C.c_int, C.c_int, DP, IP, IP, C.c_int, C.c_double,
                                             C.c_int, IP, IP, IP, IP, IP, DP, IP, DP, C.POINTER(C.c_uint8)]),
+    "gaudi_bond_orders": (C.c_int, [C.c_void_p, C.POINTER(ValenceTables), C.c_int, C.c_int, C.c_int, IP, IP, IP, IP,
+                                    C.POINTER(C.c_uint8), C.POINTER(C.c_int8), IP, IP]),
+    "gaudi_bonds_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_host_bond_orders": (C.c_int, [C.POINTER(ValenceTables), C.c_int, C.c_int, C.c_int, IP, IP, IP, IP,
+                                         C.POINTER(C.c_uint8), C.POINTER(C.c_int8), IP, IP]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -189,6 +204,7 @@ _GRID_EXPORTS = ("gaudi_sample_grid", "gaudi_step_pair", "gaudi_sample_cb_grid")
 _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fused value targets
 _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
 _RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and the way back, atoms -> graph of rings
+_BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bond orders / formal charges
 _KEY_EXPORTS = ("gaudi_last_kernel_key",)  # ... and the name of the kernel a launch ran
 
 _lib = None
@@ -217,7 +233,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -257,6 +273,33 @@ def host_atoms_to_rings(tables, xyz, elem, n_atoms, flags=0, covalency_factor=1.
     rc = lib.gaudi_host_atoms_to_rings(C.byref(tables), *rings_args(xyz, elem, n_atoms, flags, covalency_factor, max_rings, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_atoms_to_rings failed ({rc})")
+    return out
+
+
+def bonds_outputs(B: int, A: int, M: int) -> dict:
+    """The four output arrays of gaudi_bond_orders / gaudi_host_bond_orders, in argument order."""
+    return dict(order=np.zeros((B, M), np.uint8), charge=np.zeros((B, A), np.int8), n_charged=np.zeros(B, np.int32),
+                status=np.zeros(B, np.int32))
+
+
+def bonds_args(elem, n_atoms, bonds, n_bonds, out):
+    """The arguments both entry points share after the tables."""
+    for a in (elem, n_atoms, bonds, n_bonds):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    ip = lambda a: a.ctypes.data_as(IP)
+    return (B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), out["order"].ctypes.data_as(C.POINTER(C.c_uint8)),
+            out["charge"].ctypes.data_as(C.POINTER(C.c_int8)), ip(out["n_charged"]), ip(out["status"]))
+
+
+def host_bond_orders(tables, elem, n_atoms, bonds, n_bonds) -> dict:
+    """gaudi_host_bond_orders (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = bonds_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_bond_orders(C.byref(tables), *bonds_args(elem, n_atoms, bonds, n_bonds, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_bond_orders failed ({rc})")
     return out
 
 

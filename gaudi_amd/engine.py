@@ -774,6 +774,22 @@ class Engine:
         self._check(rc, "gaudi_atoms_to_rings")
         return out
 
+    def bonds_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_bond_orders since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_bonds_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_bonds_profile_get")
+        return n.value, ms.value
+
+    def bond_orders(self, tables, elem, n_atoms, bonds, n_bonds):
+        """gaudi_bond_orders on packed arrays (elem [B,A], n_atoms [B], bonds [B,M,2], n_bonds [B], all int32) -> dict of the raw
+        output arrays (order [B,M] uint8, charge [B,A] int8, n_charged [B], status [B]); gaudi_amd.gor2goa.bond_orders is the
+        interface on top."""
+        out = _lib.bonds_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_bond_orders(self.h, C.byref(tables), *_lib.bonds_args(elem, n_atoms, bonds, n_bonds, out))
+        self._check(rc, "gaudi_bond_orders")
+        return out
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

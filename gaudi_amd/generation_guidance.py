@@ -1,9 +1,10 @@
 """Host mirror of generation_guidance.py: predict / get_target_function_values / design.  The reference filters the
 designed molecules with RDKit validity (eval_stability, generation_guidance.py:69-80); RDKit is not a dependency here, so
 the filter is the graph-of-rings stability check of eval_validity.py on the GPU (gaudi_amd.analyze), and plots are replaced
-by the returned dict.  The geometric half of that step exists: with ``with_atoms=True`` the designed molecules also come
-back as graphs of atoms (gaudi_amd.gor2goa, hydrogens placed) with fingerprints and ``mol_unique``; only the RDKit half
-(sanitising, InChI) is missing."""
+by the returned dict.  With ``with_atoms=True`` the designed molecules also come back as graphs of atoms (gaudi_amd.gor2goa,
+hydrogens placed) with fingerprints and ``mol_unique``, and with ``valence_check=True`` on top of it with the valence check the
+reference makes through xyz2mol (bond orders and formal charges per molecule, ``mol_valid``, ``valid``, ``best_valid``); RDKit
+itself (its sanitiser, InChI) is still missing."""
 from __future__ import annotations
 
 from time import time
@@ -51,11 +52,16 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
     return stability_dict, x[ok], one_hot[ok], node_mask[ok], edge_mask.view(bs, n, n)[ok].view(-1, 1)
 
 
-def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False):
+def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
+           valence_check=False):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
-    placed) and add ``atoms`` (one record per molecule), ``fingerprints`` and ``mol_unique`` to the dict."""
+    placed) and add ``atoms`` (one record per molecule), ``fingerprints`` and ``mol_unique`` to the dict.  valence_check (with
+    with_atoms): every record also carries its bond orders and formal charges (gaudi_amd.gor2goa.bond_orders), and the dict gains
+    ``mol_valid`` (built with a valence-checked structure / all), ``valid`` (one bool per molecule) and ``best_valid`` (the
+    ranking restricted to the valid molecules, as ``best_stable`` is to the stable ones).  The set of keys with_atoms alone
+    returns is kept as it was."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
@@ -65,11 +71,11 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-                     with_atoms)
+                     with_atoms, valence_check)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
-                 n_steps=None, with_atoms=False):
+                 n_steps=None, with_atoms=False, valence_check=False):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -127,14 +133,14 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     for j, (t, mult) in enumerate(settings):
         lo, hi = j * bs, (j + 1) * bs
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
-                      em[lo:hi].reshape(-1, 1), seconds, with_atoms)
+                      em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
 
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
-           prop_dist=None, with_atoms=False):
+           prop_dist=None, with_atoms=False, valence_check=False):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought."""
@@ -150,26 +156,31 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     seconds = time() - start_time
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
-                    seconds, with_atoms)
+                    seconds, with_atoms, valence_check)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     return out
 
 
-def _atoms(x, one_hot, node_mask, dataset, engine):
-    """The graph of atoms of every molecule (hydrogens placed, fingerprints): what the reference's eval_stability gets from
-    gor2goa + RDKit (generation_guidance.py:69-80), as far as it goes without RDKit."""
+def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False):
+    """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
+    the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
+    RDKit."""
     from .gor2goa import rings_to_atoms
     atom_type = one_hot.argmax(2)
     keep = [node_mask[i, :, 0].bool() for i in range(x.shape[0])]
     recs = rings_to_atoms([(x[i][keep[i]], atom_type[i][keep[i]]) for i in range(x.shape[0])], dataset, place_hydrogens=True,
-                          fingerprint=True, engine=engine)
+                          fingerprint=True, engine=engine, bond_orders=valence_check)
     keys = [r["fingerprint"] for r in recs]
     built = [k for r, k in zip(recs, keys) if r["status"] == 0]
-    return dict(atoms=recs, fingerprints=keys, mol_unique=len(set(built)) / float(len(built)) if built else 0.0)
+    out = dict(atoms=recs, fingerprints=keys, mol_unique=len(set(built)) / float(len(built)) if built else 0.0)
+    if valence_check:
+        out["valid"] = np.array([r["status"] == 0 and r["kekule_status"] == 0 for r in recs], dtype=bool)
+        out["mol_valid"] = float(out["valid"].mean())
+    return out
 
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-              with_atoms=False):
+              with_atoms=False, valence_check=False):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     _check(x, node_mask)
     stability_dict, _, _, _, _ = eval_stability(x, one_hot, node_mask, edge_mask, dataset=args.dataset,
@@ -188,8 +199,11 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
     out = dict(stability=stability_dict, best_stable=order[stable[order]], x=x, one_hot=one_hot, node_mask=node_mask, edge_mask=edge_mask, target_function_values=_like_ref(tvals),
                pred=_like_ref(pred), best=order, seconds=seconds, molecules_per_second=x.shape[0] / seconds)
     if with_atoms:
-        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine))
+        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
+        if valence_check:
+            out["best_valid"] = order[out["valid"][order]]
+            print(f"{out['mol_valid']=:.2%} out of {x.shape[0]}")
     return out
 
 

@@ -5,20 +5,32 @@ batched form: every molecule of a call is converted in ONE kernel launch (one wa
 placement and an optional 64-bit fingerprint of the heavy-atom graph.  ``write_xyz`` / ``write_molfile`` are host code.  The
 constants (ring templates, RINGS_DICT, ATOMS_LIST, ...) ship as data in ``gaudi_amd/data/ring_tables.json`` under "goa".
 
-What is NOT here: the RDKit half of the reference (build_molecule_aromatic, rdkit_valid, InChI: gor2goa.py:264-324).  "Built"
-means gor2goa did not raise -- not that RDKit would sanitise the molecule; the fingerprint stands in for the InChI string when
-molecules are counted, and equal fingerprints do not prove that two molecules are isomorphic.  There is no CPU implementation
-behind these functions: without the HIP library they raise GaudiError."""
+``bond_orders`` (and ``rings_to_atoms(..., bond_orders=True)``) is the valence check the reference gets from xyz2mol.AC2BO inside
+rdkit_valid (gor2goa.py:298-324): bond orders 1 / 2 and formal charges from elements and connectivity alone, on the device
+(gaudi_bond_orders, one wavefront per molecule); the rule is stated in DESIGN.md section 8h.  "Built" means gor2goa did not raise;
+"valid" means built and ``kekule_status == 0``.
+
+What is NOT here: RDKit itself -- its sanitiser after AC2BO, ResonanceMolSupplier's single-structure condition (AC2mol) and InChI
+(gor2goa.py:264-324).  The fingerprint stands in for the InChI string when molecules are counted, and equal fingerprints do not
+prove that two molecules are isomorphic.  There is no CPU implementation behind these functions: without the HIP library they
+raise GaudiError."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import ATOMS_FINGERPRINT, ATOMS_MAX_ATOMS, ATOMS_MAX_BONDS, ATOMS_PLACE_H, AtomTables, GaudiError
+from ._lib import (ATOMS_FINGERPRINT, ATOMS_MAX_ATOMS, ATOMS_MAX_BONDS, ATOMS_PLACE_H, BONDS_EMPTY, AtomTables, GaudiError,
+                   ValenceTables)
 from .analyze import _engine, _key, _np, _pack, c_tables, ring_tables
 
 STATUS_NAMES = {0: "built", 1: "a ring without a fused neighbour in a multi-ring molecule",
                 2: "the orientation type or a type outside the table among the rings", 3: "no rings",
                 4: "more atoms, bonds or fused pairs than the kernel holds"}
+KEKULE_STATUS_NAMES = {0: "a structure with at most 4 charged atoms", 1: "no structure with up to 6 charged atoms",
+                       2: "no structure within 4 charged atoms, but one with 5 or 6",
+                       3: "the bond graph is not connected", 4: "an atom whose bonds exceed every allowed valence",
+                       5: "a bond index outside the atom list, a repeated bond or an element outside the table",
+                       6: "more than 384 atoms, 192 heavy atoms or 384 bonds", 7: "no atoms (not built)",
+                       8: "undecided: the subset search gave up (more than 25 atoms with two options; may depend on the numbering)"}
 
 
 def atoms_list(dataset: str):
@@ -57,6 +69,53 @@ def c_atom_tables(dataset: str) -> AtomTables:
     return t
 
 
+def c_valence_tables(dataset: str) -> ValenceTables:
+    """gaudi_valence_tables for one dataset: the "valence" section of ring_tables.json in the order of ATOMS_LIST[dataset]."""
+    atoms = atoms_list(dataset)
+    V = ring_tables()["valence"]
+    t = ValenceTables()
+    t.n_elems = len(atoms)
+    for e, sym in enumerate(atoms):
+        for d, opts in enumerate(V["options"][sym]):
+            t.n_options[e][d] = len(opts)
+            for k, (added, charge) in enumerate(opts):
+                t.option[e][d][k][0], t.option[e][d][k][1] = added, charge
+    t.h_elem, t.c_elem = atoms.index("H"), atoms.index("C")
+    return t
+
+
+def bond_orders(molecules, dataset="cata", engine=None):
+    """Bond orders and formal charges for a batch in one launch.  ``molecules``: a list of records from rings_to_atoms or of
+    ``(atom_types [n], bonds [m,2])`` pairs, with or without placed hydrogens (a carbon with two bonds counts the H the reference
+    would add).  Returns one dict per molecule:
+      kekule_status  0 = a structure was found (KEKULE_STATUS_NAMES); otherwise the arrays below are zero
+      orders         [m] 1 or 2 per bond;  charges: [n] formal charge per atom;  n_charged: atoms with a nonzero charge -- the
+                     fewest any structure of the molecule has (0: a neutral Kekule structure)
+    A record whose ``status != 0`` (not built) yields kekule_status 7 (EMPTY).  kekule_status 8 (GAVE_UP) is no verdict: the
+    bounded subset search ran out (possible only with more than 25 atoms that have two options), a structure may exist, and
+    another atom numbering may find it -- every other status and n_charged do not depend on the numbering."""
+    mols = []
+    for mol in molecules:
+        if isinstance(mol, dict):
+            built = mol["status"] == 0
+            mol = (mol["atom_types"], mol["bonds"]) if built else ((), ())
+        mols.append((np.asarray(_np(mol[0]), np.int32).reshape(-1), np.asarray(_np(mol[1]), np.int32).reshape(-1, 2)))
+    if not mols:
+        return []
+    B = len(mols)
+    A, M = max(1, max(len(t) for t, _ in mols)), max(1, max(len(b) for _, b in mols))
+    elem, bonds = np.zeros((B, A), np.int32), np.zeros((B, M, 2), np.int32)
+    na, nb = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for i, (t, b) in enumerate(mols):
+        elem[i, :len(t)], bonds[i, :len(b)], na[i], nb[i] = t, b, len(t), len(b)
+    raw = _engine(engine).bond_orders(c_valence_tables(dataset), elem, na, bonds, nb)
+    return [dict(kekule_status=int(raw["status"][i]), orders=raw["order"][i, :nb[i]].astype(np.int64),
+                 charges=raw["charge"][i, :na[i]].astype(np.int64), n_charged=int(raw["n_charged"][i])) for i in range(B)]
+
+
+_bond_orders = bond_orders  # (rings_to_atoms has a parameter of that name)
+
+
 def _is_packed(molecules) -> bool:
     """(x [B,N,3], ring_type [B,N], n_nodes [B]) rather than a list of (positions, ring_type) pairs: three entries that are
     arrays (not pairs themselves) of 3, 2 and 1 dimensions."""
@@ -65,7 +124,7 @@ def _is_packed(molecules) -> bool:
     return [np.ndim(_np(m)) for m in molecules] == [3, 2, 1]
 
 
-def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None):
+def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -77,7 +136,8 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
       atom_types   [n] indices into ATOMS_LIST[dataset];  bonds: [m,2], each pair i <= j, the list sorted
       fingerprint  int (0 unless asked for): equal for isomorphic heavy-atom graphs; equal keys do NOT prove isomorphism
     place_hydrogens: template H's leave the origin and every carbon with two heavy neighbours gets an H (appended after all other
-    atoms in ascending parent index), 1.09 A out on the bisector in the molecular plane -- a complete structure."""
+    atoms in ascending parent index), 1.09 A out on the bisector in the molecular plane -- a complete structure.
+    bond_orders: a second launch (gaudi_bond_orders) adds kekule_status, orders, charges and n_charged to every record."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -103,6 +163,9 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
         out.append(dict(status=int(raw["status"][b]), atoms=raw["xy"][b, :na].copy(), atoms3d=raw["xyz"][b, :na].copy(),
                         atom_types=raw["atom_type"][b, :na].astype(np.int64), bonds=raw["bonds"][b, :nb].astype(np.int64),
                         fingerprint=int(raw["fingerprint"][b])))
+    if bond_orders:
+        for rec, extra in zip(out, _bond_orders(out, dataset, engine=eng)):
+            rec.update(extra)
     return out
 
 
@@ -146,9 +209,10 @@ def write_xyz(path_or_file, atoms3d, atom_types, dataset="cata", comment=""):
             f.close()
 
 
-def write_molfile(path_or_file, atoms3d, atom_types, bonds, dataset="cata", comment=""):
+def write_molfile(path_or_file, atoms3d, atom_types, bonds, dataset="cata", comment="", orders=None, charges=None):
     """V2000 molfile of one molecule: bond type 4 (aromatic) between heavy atoms, 1 (single) to hydrogen -- the bond orders
-    build_molecule_aromatic gives them (data/gor2goa.py:282-286)."""
+    build_molecule_aromatic gives them (data/gor2goa.py:282-286).  With ``orders`` (one per bond, from bond_orders) the bond types
+    are those, 1 / 2: a Kekule structure; ``charges`` (one per atom) become ``M  CHG`` lines, 8 entries each."""
     xyz = np.asarray(_np(atoms3d), np.float64)
     if xyz.ndim != 2 or xyz.shape[1] not in (2, 3) or len(xyz) != len(atom_types):
         raise GaudiError(f"write_molfile: {xyz.shape} coordinates for {len(atom_types)} atoms")
@@ -160,15 +224,28 @@ def write_molfile(path_or_file, atoms3d, atom_types, bonds, dataset="cata", comm
     if len(bonds) and (bonds.min() < 0 or bonds.max() >= len(xyz)):
         raise GaudiError("write_molfile: bond index outside the atom list")
     sym = _symbols(atom_types, dataset)
+    if orders is not None:
+        orders = np.asarray(_np(orders), np.int64).reshape(-1)
+        if len(orders) != len(bonds) or (len(orders) and (orders.min() < 1 or orders.max() > 3)):
+            raise GaudiError(f"write_molfile: {len(orders)} bond orders in 1..3 wanted for {len(bonds)} bonds")
+    charged = []
+    if charges is not None:
+        charges = np.asarray(_np(charges), np.int64).reshape(-1)
+        if len(charges) != len(xyz):
+            raise GaudiError(f"write_molfile: {len(charges)} charges for {len(xyz)} atoms")
+        charged = [(a + 1, int(q)) for a, q in enumerate(charges) if q]
     f, close = _open(path_or_file)
     try:
         f.write(f"{str(comment).splitlines()[0] if comment else ''}\n  gaudi_amd\n\n")
         f.write(f"{len(xyz):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000\n")
         for s, p in zip(sym, xyz):
             f.write(f"{p[0]:10.4f}{p[1]:10.4f}{p[2]:10.4f} {s:<3s} 0  0  0  0  0  0  0  0  0  0  0  0\n")
-        for i, j in bonds:
-            order = 1 if "H" in (sym[i], sym[j]) else 4
+        for k, (i, j) in enumerate(bonds):
+            order = int(orders[k]) if orders is not None else 1 if "H" in (sym[i], sym[j]) else 4
             f.write(f"{i + 1:3d}{j + 1:3d}{order:3d}  0\n")
+        for k in range(0, len(charged), 8):
+            row = charged[k:k + 8]
+            f.write(f"M  CHG{len(row):3d}" + "".join(f"{a:4d}{q:4d}" for a, q in row) + "\n")
         f.write("M  END\n")
     finally:
         if close:

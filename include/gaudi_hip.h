@@ -87,7 +87,7 @@ const char* gaudi_last_warning(const gaudi_handle* h);
 int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -482,6 +482,52 @@ int gaudi_atoms_to_rings(gaudi_handle* h, const gaudi_perception_tables* tables,
 /* Number of gaudi_atoms_to_rings launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_rings_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Bond orders and formal charges of a graph of atoms, for B molecules in one launch. ----
+ * What the reference asks of xyz2mol.AC2BO inside rdkit_valid (data/gor2goa.py:298-324, data/xyz2mol.py:538-634), as a rule of
+ * this library's own (the reference's answer depends on the atom numbering): an atom's sigma degree d is its number of bonds,
+ * one more for a carbon with exactly two (the H build_molecule_aromatic adds); its options are the (added bonds, formal charge)
+ * pairs of its (element, d) below; a molecule is valid when its bond graph is connected, every atom has an option, and one option
+ * per atom can be chosen such that the charges sum to zero and the atoms that add a bond have a perfect matching among themselves
+ * -- the double bonds.  Returned: such a structure with the fewest charged atoms. */
+#define GAUDI_BONDS_MAX_ATOMS 384  /* as GAUDI_RINGS_MAX_ATOMS / _MAX_HEAVY: everything gaudi_rings_to_atoms emits fits */
+#define GAUDI_BONDS_MAX_HEAVY 192
+#define GAUDI_BONDS_MAX_BONDS 384
+#define GAUDI_BONDS_MAX_CHARGED 4     /* a returned structure has at most this many charged atoms */
+#define GAUDI_BONDS_SEARCH_CHARGED 6  /* ... and whether one exists at all is searched up to this many */
+typedef struct {
+  int32_t n_elems;                 /* len(ATOMS_LIST[dataset]) <= 8                                                       */
+  int32_t n_options[8][5];         /* options of (element, sigma degree 0..4): 0, 1 or 2; a degree above 4 has none      */
+  int32_t option[8][5][2][2];      /* (added bonds 0 / 1, formal charge); of two, the first is neutral, the second charged */
+  int32_t h_elem, c_elem;          /* ATOMS_LIST[dataset].index("H") / .index("C")                                      */
+} gaudi_valence_tables;
+/* status_out codes; anything but OK leaves the molecule's orders, charges and n_charged zero. */
+#define GAUDI_BONDS_OK 0
+#define GAUDI_BONDS_NO_STRUCTURE 1   /* no choice of options works with up to GAUDI_BONDS_SEARCH_CHARGED charged atoms (a proof
+                                        that none exists whenever fewer than 7 atoms can carry a charge at all)                 */
+#define GAUDI_BONDS_CAPPED 2         /* none within GAUDI_BONDS_MAX_CHARGED, but one with 5 or 6 charged atoms exists             */
+#define GAUDI_BONDS_NOT_CONNECTED 3
+#define GAUDI_BONDS_BAD_VALENCE 4    /* an atom without an option, e.g. a carbon with five bonds                               */
+#define GAUDI_BONDS_BAD_INPUT 5      /* a bond index outside 0..n_atoms-1, a bond from an atom to itself or listed twice, an
+                                        element outside the table                                                              */
+#define GAUDI_BONDS_OVERFLOW 6       /* more than 384 atoms, 192 non-hydrogen atoms or 384 bonds                               */
+#define GAUDI_BONDS_EMPTY 7          /* n_atoms = 0: what a molecule gaudi_rings_to_atoms did not build looks like             */
+#define GAUDI_BONDS_GAVE_UP 8        /* undecided: one subset size of the atoms with two options would have taken more than 16 384
+                                        subsets (pruned ones included).  A structure within the cap may exist, and this status --
+                                        unlike every other, and unlike n_charged -- can depend on the atom numbering: another
+                                        numbering may reach a structure first.  It cannot occur within the cap with at most 25
+                                        two-option atoms (sizes 1..4 are then at most 15 275 subsets); with 26 it can           */
+/* elem [B][A] (indices into ATOMS_LIST[dataset]), n_atoms [B] in 0..A, bonds [B][M][2], n_bonds [B] in 0..M, as
+ * gaudi_rings_to_atoms returns them, with or without placed hydrogens.  One 64-lane wave per molecule, integer arithmetic only.
+ * order_out [B][M]: 1 or 2 for every listed bond; charge_out [B][A]; n_charged_out [B] = atoms with a nonzero charge;
+ * status_out [B].  Which of several structures with equally few charges comes back is a function of the molecule's own arrays
+ * (never of its place in the batch), and bit for bit what gaudi_host_bond_orders returns.  A molecule that fails never disturbs
+ * the others of the batch. */
+int gaudi_bond_orders(gaudi_handle* h, const gaudi_valence_tables* tables, int B, int A, int M, const int32_t* elem,
+                      const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, uint8_t* order_out,
+                      int8_t* charge_out, int32_t* n_charged_out, int32_t* status_out);
+/* Number of gaudi_bond_orders launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
+int gaudi_bonds_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -499,6 +545,11 @@ int gaudi_host_atoms_to_rings(const gaudi_perception_tables* tables, int B, int 
                               const int32_t* n_atoms, int flags, double covalency_factor, int max_rings, int32_t* status_out,
                               int32_t* n_rings_out, int32_t* ring_size_out, int32_t* ring_atoms_out, int32_t* ring_type_out,
                               double* centre_out, int32_t* n_orient_out, double* orient_out, uint8_t* adj_out);
+/* gaudi_bond_orders without a handle: the same source text (csrc/bonds.inc: assign_bond_orders) compiled for the host and run
+ * serially.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_bond_orders(const gaudi_valence_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                           const int32_t* bonds, const int32_t* n_bonds, uint8_t* order_out, int8_t* charge_out,
+                           int32_t* n_charged_out, int32_t* status_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),

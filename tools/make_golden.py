@@ -2268,6 +2268,191 @@ def g31_goa2gor():
     assert size <= cap, f"g31 is {size} bytes, g30 {cap}"
 
 
+def _g32_h_rule(types, bonds, C, H):
+    """build_molecule_aromatic's hydrogens (data/gor2goa.py:288-293): one H on every carbon with exactly two bonds, appended."""
+    types = [int(t) for t in types]
+    bonds = [(int(a), int(b)) for a, b in bonds]
+    deg = np.zeros(len(types), int)
+    for a, b in bonds:
+        deg[a] += 1
+        deg[b] += 1
+    for a in range(len(deg)):
+        if types[a] == C and deg[a] == 2:
+            bonds.append((a, len(types)))
+            types.append(H)
+    return np.array(types, np.int64), np.array(bonds, np.int64).reshape(-1, 2)
+
+
+def _g32_acene(k, C):
+    """Carbon skeleton of a linear acene of k rings: 4 k + 2 atoms, 5 k + 1 bonds."""
+    top = list(range(0, 2 * k + 1))
+    bot = list(range(2 * k + 1, 4 * k + 2))
+    bonds = [(top[i], top[i + 1]) for i in range(2 * k)] + [(bot[i], bot[i + 1]) for i in range(2 * k)]
+    bonds += [(top[2 * i], bot[2 * i]) for i in range(k + 1)]
+    return [C] * (4 * k + 2), bonds
+
+
+def g32_bond_orders():
+    """Bond orders and formal charges from connectivity (data/xyz2mol.py:538-634, AC2BO, as rdkit_valid calls it: charge 0).
+    Candidates: every built molecule of g30 with build_molecule_aromatic's H rule applied; for each hetero one of at most 40 atoms
+    six mutants with 1-3 heavy atoms re-elemented among C, B, N, O, S; specials built at the atom level.  Elements are indices
+    into ATOMS_LIST["hetro"] for every molecule (ATOMS_LIST["cata"] is its prefix).  Stored per molecule: elements, bonds,
+    ref_ran (the reference can take the input at all), ref_valid (AC2BO under the identity: every atom's bond-order sum is one of
+    its allowed valences and the formal charges sum to zero, sys.exit = invalid; and the bond graph is connected, rdkit_valid's
+    fragment condition), ref_stable (the identity and two seeded relabellings agree), ref_cumulated (some labelling's VALID
+    structure gives an atom two or more added bonds), min_charged (exhaustive search over the options table below with networkx
+    maximum-cardinality matching, up to 6 charged atoms, -1: none), odd_cycle (the selected subgraph of the first minimum
+    solution is not bipartite), special (the status a special is there for, -1 otherwise), g30 (index into g30, -1 otherwise).
+    The options table: per (element, sigma degree 0..4) the (added bonds, charge) pairs of every allowed valence v >= degree
+    with v - degree <= 1, from the reference's valence lists and charge function, the neutral one first."""
+    import itertools
+    import time
+    import networkx as nx
+    from data import xyz2mol as X
+    from data.aromatic_dataloader import ATOMS_LIST
+    names = list(ATOMS_LIST["hetro"])
+    assert list(ATOMS_LIST["cata"]) == names[:2]
+    H, C = names.index("H"), names.index("C")
+    Z = [X.int_atom(e) for e in names]
+    table = [[sorted(([v - d, int(X.get_atomic_charge(z, X.atomic_valence_electrons[z], v))] for v in X.atomic_valence[z] if 0 <= v - d <= 1),
+                     key=lambda o: (abs(o[1]), o[0])) for d in range(5)] for z in Z]
+    g30 = np.load(os.path.join(OUT, "g30_gor2goa.npz"))
+    rng = np.random.default_rng(3200)
+
+    def ref_choices(types, bonds):
+        deg = np.bincount(bonds.reshape(-1), minlength=len(types))
+        return sum(len([v for v in X.atomic_valence[Z[t]] if v >= d]) >= 2 for t, d in zip(types, deg))
+
+    def ref_verdict(types, bonds, perm):
+        n = len(types)
+        AC = np.zeros((n, n), int)
+        for a, b in bonds:
+            AC[perm[a], perm[b]] = AC[perm[b], perm[a]] = 1
+        atoms = [0] * n
+        for a in range(n):
+            atoms[perm[a]] = Z[types[a]]
+        try:
+            BO, _ = X.AC2BO(AC, atoms, 0)
+        except SystemExit:
+            return False, False
+        val = BO.sum(1)
+        ok = all(int(v) in X.atomic_valence[z] for v, z in zip(val, atoms))
+        q = sum(X.get_atomic_charge(z, X.atomic_valence_electrons[z], int(v)) for v, z in zip(val, atoms))
+        valid = bool(ok and q == 0)
+        return valid, valid and bool((BO - AC).sum(1).max() >= 2)
+
+    def own_search(types, bonds):
+        n = len(types)
+        g = nx.Graph()
+        g.add_nodes_from(range(n))
+        g.add_edges_from((int(a), int(b)) for a, b in bonds)
+        if n == 0 or not nx.is_connected(g):
+            return -1, False
+        deg = np.bincount(bonds.reshape(-1), minlength=n) if len(bonds) else np.zeros(n, int)
+        opts = [table[t][d] if d < 5 else [] for t, d in zip(types, deg)]
+        if any(not o for o in opts):
+            return -1, False
+        flex = [a for a in range(n) if len(opts[a]) == 2]
+        base_q = sum(o[0][1] for o in opts)
+        forced = sum(o[0][1] != 0 for o in opts)
+        for t in range(0, 7 - forced):
+            for sub in itertools.combinations(flex, t):
+                if base_q + sum(opts[a][1][1] for a in sub) != 0:
+                    continue
+                S = [a for a in range(n) if opts[a][1 if a in sub else 0][0] == 1]
+                if len(S) % 2:
+                    continue
+                h = g.subgraph(S)
+                if 2 * len(nx.max_weight_matching(h, maxcardinality=True)) == len(S):
+                    return forced + t, not nx.is_bipartite(h)
+        return -1, False
+
+    cands = []  # (types, bonds, kind, special status, g30 index)
+    built = [m for m in range(len(g30["n"])) if not g30["threw"][m]]
+    n_skipped = n_mut = 0
+    for m in built:
+        ty = g30["ref_types"][g30["atom_off"][m]:g30["atom_off"][m + 1]].astype(np.int64)
+        bo = g30["ref_bonds"][g30["bond_off"][m]:g30["bond_off"][m + 1]].astype(np.int64)
+        cands.append((*_g32_h_rule(ty, bo, C, H), 0, -1, m))
+        if not g30["hetro"][m] or len(cands[-1][0]) > 40:
+            continue
+        heavy = np.flatnonzero(ty != H)
+        for _ in range(6):  # (three leave no molecule that needs two charge pairs)
+            n_mut += 1
+            t2 = ty.copy()
+            for a in rng.choice(heavy, size=int(rng.integers(1, 4)), replace=False):
+                t2[a] = names.index("CBNOS"[int(rng.integers(5))])
+            t2, b2 = _g32_h_rule(t2, bo, C, H)
+            if ref_choices(t2, b2) > 9:
+                n_skipped += 1
+                continue
+            cands.append((t2, b2, 1, -1, -1))
+    print(f"g32: {n_skipped} of {n_mut} mutants skipped (more than 9 atoms with a choice of valence); cap 12 %")
+    assert n_skipped * 100 <= 12 * n_mut
+    ring6 = [(i, (i + 1) % 6) for i in range(6)]
+    sp = lambda t, b, st=-1, h=True: cands.append((*(_g32_h_rule(t, b, C, H) if h else (np.array(t, np.int64), np.array(b, np.int64).reshape(-1, 2))), 2, st, -1))
+    sp([C] * 6, ring6, 0)                                                   # benzene
+    sp(*_g32_acene(16, C), 0)                                               # 66 carbons: more heavy atoms than lanes
+    sp(*_g32_acene(47, C), 0)                                               # 190 carbons: the capacity edge
+    sp(*_g32_acene(48, C), 6)                                               # 194: OVERFLOW
+    t47, b47 = _g32_acene(47, C)
+    t47[1] = names.index("O")                                               # a CH carbon -> O: an odd remainder
+    sp(t47, b47, 1)
+    sp([C] * 12, ring6 + [(6 + i, 6 + j) for i, j in ring6], 3)             # two benzenes, not connected
+    sp([C] + [H] * 5, [(0, k) for k in range(1, 6)], 4, h=False)            # a carbon with five bonds
+    sp([C] * 6 + [H] * 6, ring6[:5] + [(5, 12)] + [(k, 6 + k) for k in range(6)], 5, h=False)  # a bond index equal to n_atoms
+    sp([], [], 7, h=False)                                                  # an empty molecule
+
+    recs = []
+    t0 = time.time()
+    for types, bonds, kind, special, gi in cands:
+        n = len(types)
+        ran = special not in (5, 6, 7)
+        rec = dict(types=types, bonds=bonds, kind=kind, special=special, g30=gi, ran=ran, valid=False, stable=True, cumulated=False,
+                   minq=-1, odd=False)
+        if ran:
+            g = nx.Graph()
+            g.add_nodes_from(range(n))
+            g.add_edges_from((int(a), int(b)) for a, b in bonds)
+            verdicts = [ref_verdict(types, bonds, p) for p in [np.arange(n), rng.permutation(n), rng.permutation(n)]]
+            rec["valid"] = verdicts[0][0] and nx.is_connected(g)
+            rec["stable"] = len({v for v, _ in verdicts}) == 1
+            rec["cumulated"] = any(c for _, c in verdicts)
+            rec["minq"], rec["odd"] = own_search(types, bonds)
+        recs.append(rec)
+    print(f"g32: reference and search over {len(recs)} molecules in {time.time() - t0:.0f} s")
+    for kind, label in ((0, "g30"), (1, "mutants")):
+        sel = [r for r in recs if r["kind"] == kind]
+        exc = sum((not r["stable"]) or r["cumulated"] for r in sel)
+        print(f"g32: {label}: {len(sel)} kept, {exc} outside the verdict comparison (unstable or cumulated)")
+    exc = sum((not r["stable"]) or r["cumulated"] or not r["ran"] for r in recs)
+    print(f"g32: {exc} of {len(recs)} molecules outside the verdict comparison; cap 5 %")
+    assert exc * 100 <= 5 * len(recs)
+    counts = {k: sum(r["minq"] == k for r in recs) for k in range(-1, 7)}
+    n_odd = sum(r["odd"] for r in recs)
+    print(f"g32: min_charged counts {counts} (-1 includes the specials without a structure), odd_cycle {n_odd}")
+    agree = sum((0 <= r["minq"] <= 4) == r["valid"] for r in recs if r["stable"] and not r["cumulated"] and r["ran"])
+    print(f"g32: the rule agrees with the reference's verdict on {agree} of {len(recs) - exc} compared molecules")
+    assert counts[0] >= 100 and counts[2] >= 10 and counts[4] >= 1 and counts[-1] >= 50 and n_odd >= 10
+    aoff = np.concatenate([[0], np.cumsum([len(r["types"]) for r in recs])]).astype(np.int64)
+    boff = np.concatenate([[0], np.cumsum([len(r["bonds"]) for r in recs])]).astype(np.int64)
+    tn = np.array([[len(table[e][d]) for d in range(5)] for e in range(len(names))], np.int8)
+    to = np.zeros((len(names), 5, 2, 2), np.int8)
+    for e in range(len(names)):
+        for d in range(5):
+            for k, o in enumerate(table[e][d]):
+                to[e, d, k] = o
+    col = lambda key, dt: np.array([r[key] for r in recs], dt)
+    save("g32_bond_orders", elem=np.concatenate([r["types"] for r in recs]).astype(np.int8),
+         bonds=np.concatenate([r["bonds"] for r in recs]).astype(np.int16), atom_off=aoff, bond_off=boff,
+         kind=col("kind", np.int8), special=col("special", np.int8), g30=col("g30", np.int32), ref_ran=col("ran", bool),
+         ref_valid=col("valid", bool), ref_stable=col("stable", bool), ref_cumulated=col("cumulated", bool),
+         min_charged=col("minq", np.int8), odd_cycle=col("odd", bool), table_n=tn, table_opt=to,
+         elements=np.array(json.dumps(names)))
+    size, cap = os.path.getsize(os.path.join(OUT, "g32_bond_orders.npz")), os.path.getsize(os.path.join(OUT, "g30_gor2goa.npz"))
+    assert size <= cap, f"g32 is {size} bytes, g30 {cap}"
+
+
 def g8_checkpoint_roundtrip():
     """The reference's own loader must accept checkpoints written by gaudi_amd.synth.write_checkpoint
     (args.txt + model.pt, with and without the ``module.`` prefix).  Stores nothing but a marker."""
@@ -2296,6 +2481,7 @@ if __name__ == "__main__":
                g7=g7_end_to_end, g8=g8_checkpoint_roundtrip, g9=g9_sample_chain, g10=g10_nonlinear_target, g11=g11_stability, g12=g12_ring_count_sampler, g13=g13_noised_predictor, g14=g14_long_chains, g15=g15_nan_scrub, g16=g16_fix_noise, g17=g17_nan_in_edge_gemm_matrix, g18=g18_large_molecules, g19=g19_amplified_default_steps, g20=g20_cosine_and_mean, g21=g21_direct_z_target, g22=g22_sin_embedding, g23=g23_attention_tanh_flags, g24=g24_scalar_hyperparameters, g25=g25_nll, g26=g26_pred_grad, g27=g27_edm_grad, g27t=g27_edm_train, g28=g28_grid, g29=g29_value_target, g30=g30_gor2goa, g31=g31_goa2gor)
     fns["g30_gor2goa"] = g30_gor2goa  # (also under its full name)
     fns["g31_goa2gor"] = g31_goa2gor
-    which = sys.argv[1:] or [k for k in fns if k not in ("g30_gor2goa", "g31_goa2gor")]
+    fns["g32"] = fns["g32_bond_orders"] = g32_bond_orders
+    which = sys.argv[1:] or [k for k in fns if k not in ("g30_gor2goa", "g31_goa2gor", "g32_bond_orders")]
     for w in which:
         fns[w]()

@@ -20,6 +20,12 @@ utils/ring_graph.py:9, data/aromatic_dataloader.py:26-30), keyed by ring symbol:
     goa.extra_angle[sym]      what gor2goa adds to that angle;   goa.template_h[sym]: ring atoms that carry a template H
     goa.atoms[dataset]        ATOMS_LIST;   goa.h_bond: X-H distance used when hydrogens are placed (ours, not the reference's)
     goa.cov_radii[element]    covalent radii (utils/const.py) of the elements of ATOMS_LIST: bond perception of atoms -> rings
+
+and the valence options of the bond-order assignment (gaudi_bond_orders), from the allowed valences and the charge function of
+data/xyz2mol.py:136-164,312-326:
+
+    valence.options[element]  per sigma degree 0..4 the list of [added bonds, formal charge] for every allowed valence v >= degree
+                              with v - degree <= 1 (the rule is ours: DESIGN.md section 8h), the neutral option first
 """
 import json
 import os
@@ -36,6 +42,7 @@ for m in ["rdkit", "rdkit.Chem", "rdkit.Chem.Draw", "rdkit.Chem.rdmolops", "rdki
 import math  # noqa: E402
 
 from data import gor2goa as G  # noqa: E402
+from data import xyz2mol as X  # noqa: E402
 from data.aromatic_dataloader import ATOMS_LIST, RINGS_LIST  # noqa: E402
 from data.ring import RINGS_DICT  # noqa: E402
 from utils.ring_graph import NO_ORIENTATION_RINGS  # noqa: E402
@@ -75,6 +82,16 @@ out["goa"] = dict(
     h_bond=1.09,
     cov_radii={e: float(__COV_RADII__[e]) for e in ATOMS_LIST["hetro"]},
 )
+
+
+def valence_options(sym, degree):
+    z = X.int_atom(sym)
+    opts = [[v - degree, int(X.get_atomic_charge(z, X.atomic_valence_electrons[z], v))] for v in X.atomic_valence[z]
+            if 0 <= v - degree <= 1]
+    return sorted(opts, key=lambda o: (abs(o[1]), o[0]))
+
+
+out["valence"] = dict(degrees=5, options={e: [valence_options(e, d) for d in range(5)] for e in ATOMS_LIST["hetro"]})
 path = os.path.join(ROOT, "gaudi_amd", "data", "ring_tables.json")
 with open(path, "w") as f:
     json.dump(out, f, indent=1)
