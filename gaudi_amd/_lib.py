@@ -162,6 +162,8 @@ EXPORTS = {
     "gaudi_set_plan_hint": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "gaudi_last_warning": (C.c_char_p, [C.c_void_p]),
     "gaudi_last_kernel_key": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "gaudi_kernel_key_log": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "gaudi_host_kernel_keys": (C.c_int, [C.c_char_p, C.c_int]),
     "gaudi_abi_version": (C.c_int, []),
     "gaudi_last_family_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "gaudi_profile_clock": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -205,7 +207,7 @@ _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fu
 _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
 _RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and the way back, atoms -> graph of rings
 _BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bond orders / formal charges
-_KEY_EXPORTS = ("gaudi_last_kernel_key",)  # ... and the name of the kernel a launch ran
+_KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
 
@@ -242,6 +244,21 @@ def load_library() -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def key_lines(fn, *head) -> list:
+    """The lines of a key list (gaudi_host_kernel_keys / gaudi_kernel_key_log: a call with no buffer sizes it)."""
+    need = fn(*head, None, 0)
+    if need < 0:
+        raise GaudiError(f"{fn.__name__} failed ({need})")
+    buf = C.create_string_buffer(need)
+    fn(*head, buf, need)
+    return buf.value.decode().splitlines()
+
+
+def registered_kernel_keys() -> list:
+    """The key of every entry of the kernel table (csrc/kernel_table.h), sorted.  Needs no device."""
+    return key_lines(load_library().gaudi_host_kernel_keys)
 
 
 def rings_outputs(B: int, max_rings: int) -> dict:

@@ -100,7 +100,8 @@ struct NetSmem {
 
 // SinusoidsEmbeddingNew (egnn_new.py:378-391): x -> sqrt(x + 1e-8) * f_k, (sin | cos), f_k = 2 pi 4^k / 15 (k = 0..5) in the fp32
 // values torch builds (oracle/gaudi_oracle.py: sin_frequencies; tests/golden/g22 holds the reference's tensor).  Accurate sinf / cosf:
-// the highest frequency multiplies sqrt(r) by 429.
+// the highest frequency multiplies sqrt(r) by 429.  This fp32 form is the reference's own arithmetic and what the training kernels
+// (kernt_edm_train.hip) call; the sampler deliberately deviates from both and takes the double form below.
 __device__ __forceinline__ void sin_features(float x, float* out /* [12] */) {
   constexpr float kFreq[6] = {4.1887903e-01f, 1.6755161e+00f, 6.7020645e+00f, 2.6808258e+01f, 1.0723303e+02f, 4.2893213e+02f};
   const float sx = sqrtf(x + 1e-8f);
@@ -109,6 +110,22 @@ __device__ __forceinline__ void sin_features(float x, float* out /* [12] */) {
     const float e = sx * kFreq[k];
     out[k] = sinf(e);
     out[6 + k] = cosf(e);
+  }
+}
+
+// The same from the squared distance in double, for the sampler: fp32 rounds r and the product sqrt(r) * 429 by about 1e-4 rad of
+// phase each, which a network with large coordinate heads turns into 1e-3 of phi (against the float64 evaluation; the reference in
+// fp32 is as far off).  The fp32 coordinates are exact inputs: their differences, r, the square root, the product with the (fp32)
+// frequency and the reduction to [-pi, pi] are done in double, sinf / cosf see the reduced argument.
+__device__ __forceinline__ void sin_features(double x, float* out /* [12] */) {
+  constexpr float kFreq[6] = {4.1887903e-01f, 1.6755161e+00f, 6.7020645e+00f, 2.6808258e+01f, 1.0723303e+02f, 4.2893213e+02f};
+  const double sx = sqrt(x + 1e-8);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double e = sx * (double)kFreq[k];
+    const float rem = (float)fma(-rint(e * 0.15915494309189535), 6.283185307179586, e);
+    out[k] = sinf(rem);
+    out[6 + k] = cosf(rem);
   }
 }
 
@@ -133,7 +150,10 @@ __device__ __forceinline__ void compute_geo(const SM& sm, const MolGraph& mg, fl
     }
     if constexpr (SM::kEF > 2) {  // edge_attr = [sin_embedding(r) | sin_embedding(d0)] (egnn_new.py:217-219, 302-303)
       float* ft = sm.feat + (size_t)(wave * mg.EW + slot) * SM::kEF + (write_d0 ? SM::kEF / 2 : 0);
-      sin_features(r, ft);
+      const double ex = (double)sm.x[4 * i + 0] - (double)sm.x[4 * j + 0];
+      const double ey = (double)sm.x[4 * i + 1] - (double)sm.x[4 * j + 1];
+      const double ez = (double)sm.x[4 * i + 2] - (double)sm.x[4 * j + 2];
+      sin_features(ex * ex + ey * ey + ez * ez, ft);
     }
   }
 }

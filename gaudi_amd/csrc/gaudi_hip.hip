@@ -131,6 +131,7 @@ struct gaudi_handle {
   bool no_fr = false;         // GAUDI_NO_FR=1: never the FR instantiation of the resident full-ring kernel (kern8s2_*.hip)
   bool no_n1 = false;         // GAUDI_NO_N1=1: never the N1 instantiation of the resident full-ring kernel (kern8s1_*.hip)
   std::string last_key;       // key_name of the kernel the most recent launch ran (gaudi_last_kernel_key)
+  std::vector<std::string> key_log;  // the distinct key_names launched since gaudi_create, in first-launch order (gaudi_kernel_key_log)
   bool wide_full = true;      // GAUDI_WIDE_FULL=0: wide groups that do not fit the full ring run on the half ring (round 5)
   bool gn8_pq = true;         // GAUDI_GN8_PQ=0: never the P / Q-in-LDS form (kern8gp_*.hip)
   bool gn8 = true;            // GAUDI_GN8=0: molecules beyond the LDS limit go to the 4-wave V4G kernels, as in round 3
@@ -1025,6 +1026,7 @@ static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long
 #endif
   HIPCHECK(h, hipGetLastError());
   h->last_key = key_name(key);
+  if (std::find(h->key_log.begin(), h->key_log.end(), h->last_key) == h->key_log.end()) h->key_log.push_back(h->last_key);
   if (h->prof) {
     HIPCHECK(h, h->prof_log.end(h->stream, ev));
     h->prof_steps += steps;
@@ -1605,6 +1607,25 @@ int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n) {
   if (!h || !buf || n <= 0) return GAUDI_E_INVALID;
   snprintf(buf, (size_t)n, "%s", h->last_key.c_str());
   return GAUDI_OK;
+}
+// names, one per line, cut to n bytes (NUL-terminated); returns the bytes the whole text needs, its NUL included
+static int copy_lines(const std::vector<std::string>& names, char* buf, int n) {
+  std::string all;
+  for (const std::string& s : names) all += s + "\n";
+  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", all.c_str());
+  return (int)all.size() + 1;
+}
+int gaudi_host_kernel_keys(char* buf, int n) {
+  if (n < 0) return GAUDI_E_INVALID;
+  std::vector<std::string> names;
+  for (const KernelTable* t = g_kernel_tables; t; t = t->next)
+    for (int i = 0; i < t->n; ++i) names.push_back(key_name(t->entries[i].key));
+  std::sort(names.begin(), names.end());  // (the tables link in load order, which means nothing)
+  return copy_lines(names, buf, n);
+}
+int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n) {
+  if (!h || n < 0) return GAUDI_E_INVALID;
+  return copy_lines(h->key_log, buf, n);
 }
 int gaudi_abi_version(void) { return GAUDI_ABI_VERSION; }
 int gaudi_profile_clock(gaudi_handle* h, double* shader_mhz) {

@@ -181,6 +181,14 @@ class Engine:
         self._check(fn(self.h, buf, len(buf)), "gaudi_last_kernel_key")
         return buf.value.decode()
 
+    def kernel_keys_launched(self) -> list:
+        """The distinct kernel-table keys this engine has launched since it was made, in first-launch order (a call may be two
+        launches: the 4-wave global-node-buffer kernels, a sin_embedding width without a fused kernel)."""
+        fn = getattr(self.lib, "gaudi_kernel_key_log", None)
+        if fn is None or not fn.argtypes:  # (an older A/B library)
+            return []
+        return _lib.key_lines(fn, self.h)
+
     def keep_h(self) -> int:
         """Floats of LDS the most recent call gave to a kept split copy of h (0: none)."""
         fn = getattr(self.lib, "gaudi_last_keep_h", None)

@@ -85,9 +85,17 @@ const char* gaudi_last_warning(const gaudi_handle* h);
  * HPP=208 VT=0": csrc/kernel_table.h), NUL-terminated and cut to n bytes; "" before the first launch.  For tests and tooling: which
  * instantiation a plan picked (GAUDI_NO_FR / GAUDI_NO_N1 at gaudi_create keep the resident full-ring kernel on its plain form). */
 int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n);
+/* Every distinct key the handle has launched since gaudi_create, in first-launch order, one per line (each line ends in '\n'),
+ * NUL-terminated and cut to n bytes.  gaudi_last_kernel_key names one launch; a call that makes two (a guided step on the 4-wave
+ * global-node-buffer kernels, a sin_embedding width without a fused entry) shows both here.  Returns the bytes the whole text needs
+ * (its NUL included), so (h, NULL, 0) sizes the buffer; GAUDI_E_INVALID for a null handle or n < 0. */
+int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
+/* The key of every entry the library's kernel table holds (csrc/kernel_table.h), sorted, in the same form and with the same
+ * return value.  Needs no device: tests/test_kernel_census_cpu.py holds the list against the cases of tests/kernel_census.py. */
+int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);

@@ -20,6 +20,36 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
 
 
+def test_kernel_key_lists_are_declared_bound_and_sized_by_the_caller():
+    """gaudi_host_kernel_keys / gaudi_kernel_key_log: declared in the header, bound with the prototype the header gives, and the
+    device-free one follows its protocol -- the return value is the room the whole text needs, a short buffer is cut and
+    NUL-terminated, the Python wrapper returns the sorted distinct keys."""
+    import ctypes as C
+    from gaudi_amd import _lib, build
+    build.build()
+    lib = _lib.load_library()
+    header = open(os.path.join(ROOT, "include", "gaudi_hip.h")).read()
+    assert re.search(r"int gaudi_kernel_key_log\(const gaudi_handle\* h, char\* buf, int n\);", header)
+    assert re.search(r"int gaudi_host_kernel_keys\(char\* buf, int n\);", header)
+    assert "#define GAUDI_ABI_VERSION 7" in header and _lib.ABI_VERSION == 7
+    assert _lib.EXPORTS["gaudi_kernel_key_log"] == (C.c_int, [C.c_void_p, C.c_char_p, C.c_int])
+    assert _lib.EXPORTS["gaudi_host_kernel_keys"] == (C.c_int, [C.c_char_p, C.c_int])
+    assert {"gaudi_kernel_key_log", "gaudi_host_kernel_keys"} <= set(_lib._KEY_EXPORTS)
+    need = lib.gaudi_host_kernel_keys(None, 0)
+    assert need > 1
+    buf = C.create_string_buffer(need)
+    assert lib.gaudi_host_kernel_keys(buf, need) == need
+    text = buf.value.decode()
+    assert len(text) == need - 1 and text.endswith("\n")
+    short = C.create_string_buffer(b"x" * 40, 40)
+    assert lib.gaudi_host_kernel_keys(short, 20) == need
+    assert short.raw[19:20] == b"\0" and short.raw[:19] == text.encode()[:19] and short.raw[20:] == b"x" * 20
+    assert lib.gaudi_host_kernel_keys(buf, -1) < 0 and lib.gaudi_kernel_key_log(None, buf, need) < 0
+    keys = _lib.registered_kernel_keys()
+    assert keys == text.splitlines() == sorted(set(keys)) and len(keys) > 100
+    assert "waves=8 SP=1 MR=0 GN=0 FR=0 PG=0 N1=1 EF=2 HPE=192 HPP=208 VT=0" in keys  # (the header's example of a key)
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
