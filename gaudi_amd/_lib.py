@@ -78,6 +78,10 @@ BONDS_MAX_ATOMS, BONDS_MAX_HEAVY, BONDS_MAX_BONDS, BONDS_MAX_CHARGED = 384, 192,
 (BONDS_OK, BONDS_NO_STRUCTURE, BONDS_CAPPED, BONDS_NOT_CONNECTED, BONDS_BAD_VALENCE, BONDS_BAD_INPUT, BONDS_OVERFLOW,
  BONDS_EMPTY, BONDS_GAVE_UP) = range(9)
 
+# include/gaudi_hip.h: GAUDI_CANON_*
+CANON_MAX_ATOMS, CANON_MAX_HEAVY, CANON_MAX_BONDS, CANON_MAX_DEGREE, CANON_MAX_NODES, CANON_MAX_DEPTH = 384, 192, 384, 8, 4096, 16
+CANON_OK, CANON_GAVE_UP, CANON_BAD_INPUT, CANON_OVERFLOW, CANON_EMPTY = range(5)
+
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
 DP = C.POINTER(C.c_double)
@@ -134,6 +138,11 @@ EXPORTS = {
     "gaudi_bonds_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_host_bond_orders": (C.c_int, [C.POINTER(ValenceTables), C.c_int, C.c_int, C.c_int, IP, IP, IP, IP,
                                          C.POINTER(C.c_uint8), C.POINTER(C.c_int8), IP, IP]),
+    "gaudi_canonical_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP,
+                                        C.POINTER(C.c_uint8), IP, C.POINTER(C.c_uint16), IP, IP]),
+    "gaudi_canon_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_host_canonical_order": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP,
+                                             C.POINTER(C.c_uint8), IP, C.POINTER(C.c_uint16), IP, IP]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -207,6 +216,7 @@ _TARGET_EXPORTS = ("gaudi_sample_target", "gaudi_step_target")  # ... and the fu
 _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and the graph-of-atoms conversion
 _RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and the way back, atoms -> graph of rings
 _BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bond orders / formal charges
+_CANON_EXPORTS = ("gaudi_canonical_order", "gaudi_canon_profile_get")  # ... and the canonical numbering
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -235,7 +245,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -317,6 +327,35 @@ def host_bond_orders(tables, elem, n_atoms, bonds, n_bonds) -> dict:
     rc = lib.gaudi_host_bond_orders(C.byref(tables), *bonds_args(elem, n_atoms, bonds, n_bonds, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_bond_orders failed ({rc})")
+    return out
+
+
+def canon_outputs(B: int, A: int, M: int) -> dict:
+    """The seven output arrays of gaudi_canonical_order / gaudi_host_canonical_order, in argument order."""
+    return dict(rank=np.zeros((B, A), np.int32), n_heavy=np.zeros(B, np.int32), label=np.zeros((B, A), np.uint8),
+                n_hbonds=np.zeros(B, np.int32), cbonds=np.zeros((B, M, 2), np.uint16), nodes=np.zeros(B, np.int32),
+                status=np.zeros(B, np.int32))
+
+
+def canon_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, out):
+    """The arguments both entry points share."""
+    for a in (elem, n_atoms, bonds, n_bonds):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    ip = lambda a: a.ctypes.data_as(IP)
+    return (int(n_elems), int(h_elem), int(c_elem), B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), ip(out["rank"]),
+            ip(out["n_heavy"]), out["label"].ctypes.data_as(C.POINTER(C.c_uint8)), ip(out["n_hbonds"]),
+            out["cbonds"].ctypes.data_as(C.POINTER(C.c_uint16)), ip(out["nodes"]), ip(out["status"]))
+
+
+def host_canonical_order(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds) -> dict:
+    """gaudi_host_canonical_order (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = canon_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_canonical_order(*canon_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_canonical_order failed ({rc})")
     return out
 
 

@@ -166,13 +166,14 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
     return dist, adj
 
 
-def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False):
+def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
+                                exact=False, train_keys=None):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
     What differs from the reference, plainly: there is no RDKit here.  ``mol_built`` is the fraction for which gor2goa did not
     raise, and molecules are told apart by the 64-bit fingerprint of their heavy-atom graph, not by InChI: equal keys do not
-    prove that two molecules are the same.  The reference's ``mol_valid`` has a counterpart only with ``valence_check=True``.
+    prove that two molecules are the same (``exact=True`` below replaces the fingerprint by an exact key).  The reference's ``mol_valid`` has a counterpart only with ``valence_check=True``.
 
     -> (dict, built_list): ``mol_built``; ``mol_unique`` = distinct keys / built molecules (0.0 when none was built);
     ``molecule_built_bool``; ``fingerprints`` (one int per molecule, 0 where not built); ``mol_novel`` = built molecules whose
@@ -180,23 +181,43 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
 
     valence_check: a second launch (gaudi_bond_orders) assigns bond orders and formal charges from connectivity, the step the
     reference takes through xyz2mol.AC2BO inside rdkit_valid (DESIGN.md section 8h has the rule; RDKit's sanitiser, the
-    single-resonance-structure condition and InChI are still not there).  The dict gains ``mol_valid`` = molecules that are built
+    single-resonance-structure condition and InChI strings are still not there).  The dict gains ``mol_valid`` = molecules that are built
     and have a structure / all molecules, ``molecule_valid_bool``, ``mol_unique_valid`` = distinct keys / valid molecules,
-    ``mol_novel_valid`` (with ``train_fingerprints``), and the second return value becomes the VALID molecules."""
+    ``mol_novel_valid`` (with ``train_fingerprints``), and the second return value becomes the VALID molecules.
+
+    exact: a further launch (gaudi_canonical_order) numbers every built molecule canonically, and molecules
+    are told apart by ``canon_key`` -- equal keys <=> isomorphic graphs of atoms, what the reference's InChI comparison decides.
+    A built molecule without a key (the bounded search gave up) falls back to ``("fp", fingerprint)``.  ``mol_unique*`` count
+    these keys, ``mol_novel*`` compare them with ``train_keys`` (a collection of ``bytes``; ``train_fingerprints`` is not used),
+    and the dict gains ``canon_keys`` (one per molecule, None where not built), ``mol_undecided`` = built molecules without a
+    key / built molecules and, with ``valence_check``, ``smiles`` (one string or None per molecule)."""
     from .gor2goa import rings_to_atoms
     # (the keyword only when asked for: a rings_to_atoms stand-in with the earlier signature, as tests/test_gor2goa_cpu.py passes, keeps working)
     extra = {"bond_orders": True} if valence_check else {}
+    if exact:
+        extra["canonical"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
     built = [r["status"] == 0 for r in recs]
     keys = [r["fingerprint"] if ok else 0 for r, ok in zip(recs, built)]
+    fingerprints = keys
+    if exact:
+        keys = [None if not ok else r["canon_key"] if r["canon_key"] is not None else ("fp", r["fingerprint"])
+                for r, ok in zip(recs, built)]
     built_keys = [k for k, ok in zip(keys, built) if ok]
     n_built = len(built_keys)
     d = {"mol_built": n_built / float(len(recs)),
          "mol_unique": len(set(built_keys)) / float(n_built) if n_built else 0.0,
-         "molecule_built_bool": built, "fingerprints": keys}
+         "molecule_built_bool": built, "fingerprints": fingerprints}
     train = None if train_fingerprints is None else {int(k) for k in train_fingerprints}
+    if exact:
+        train = None if train_keys is None else {bytes(k) for k in train_keys}
+        d["canon_keys"] = keys
+        d["mol_undecided"] = sum(isinstance(k, tuple) for k in built_keys) / float(n_built) if n_built else 0.0
+        if valence_check:
+            from .gor2goa import smiles
+            d["smiles"] = [smiles(r, dataset) if ok else None for r, ok in zip(recs, built)]
     if train is not None:
         d["mol_novel"] = sum(k not in train for k in built_keys) / float(n_built) if n_built else 0.0
     keep = built

@@ -798,6 +798,22 @@ class Engine:
         self._check(rc, "gaudi_bond_orders")
         return out
 
+    def canon_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_canonical_order since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_canon_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_canon_profile_get")
+        return n.value, ms.value
+
+    def canonical_order(self, n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds):
+        """gaudi_canonical_order on packed arrays (as bond_orders takes them) -> dict of the raw output arrays (rank [B,A] int32,
+        n_heavy [B], label [B,A] uint8, n_hbonds [B], cbonds [B,M,2] uint16, nodes [B], status [B]);
+        gaudi_amd.gor2goa.canonical is the interface on top."""
+        out = _lib.canon_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_canonical_order(self.h, *_lib.canon_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, out))
+        self._check(rc, "gaudi_canonical_order")
+        return out
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

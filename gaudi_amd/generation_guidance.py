@@ -53,7 +53,7 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 
 
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
-           valence_check=False):
+           valence_check=False, exact=False):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -61,7 +61,9 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     with_atoms): every record also carries its bond orders and formal charges (gaudi_amd.gor2goa.bond_orders), and the dict gains
     ``mol_valid`` (built with a valence-checked structure / all), ``valid`` (one bool per molecule) and ``best_valid`` (the
     ranking restricted to the valid molecules, as ``best_stable`` is to the stable ones).  The set of keys with_atoms alone
-    returns is kept as it was."""
+    returns is kept as it was.  exact (with with_atoms): every record is numbered canonically (gaudi_amd.gor2goa.canonical),
+    ``mol_unique`` counts ``canon_keys`` (added: one per molecule, None where not built, ``("fp", fingerprint)`` where the
+    search gave up) instead of fingerprints, and with valence_check the dict gains ``smiles``."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
@@ -71,7 +73,7 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-                     with_atoms, valence_check)
+                     with_atoms, valence_check, exact)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
@@ -161,7 +163,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     return out
 
 
-def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False):
+def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -169,10 +171,18 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False):
     atom_type = one_hot.argmax(2)
     keep = [node_mask[i, :, 0].bool() for i in range(x.shape[0])]
     recs = rings_to_atoms([(x[i][keep[i]], atom_type[i][keep[i]]) for i in range(x.shape[0])], dataset, place_hydrogens=True,
-                          fingerprint=True, engine=engine, bond_orders=valence_check)
+                          fingerprint=True, engine=engine, bond_orders=valence_check, **({"canonical": True} if exact else {}))
     keys = [r["fingerprint"] for r in recs]
-    built = [k for r, k in zip(recs, keys) if r["status"] == 0]
+    ids = keys
+    if exact:
+        ids = [None if r["status"] else r["canon_key"] if r["canon_key"] is not None else ("fp", r["fingerprint"]) for r in recs]
+    built = [k for r, k in zip(recs, ids) if r["status"] == 0]
     out = dict(atoms=recs, fingerprints=keys, mol_unique=len(set(built)) / float(len(built)) if built else 0.0)
+    if exact:
+        out["canon_keys"] = ids
+        if valence_check:
+            from .gor2goa import smiles
+            out["smiles"] = [smiles(r, dataset) for r in recs]
     if valence_check:
         out["valid"] = np.array([r["status"] == 0 and r["kekule_status"] == 0 for r in recs], dtype=bool)
         out["mol_valid"] = float(out["valid"].mean())
@@ -180,7 +190,7 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False):
 
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-              with_atoms=False, valence_check=False):
+              with_atoms=False, valence_check=False, exact=False):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     _check(x, node_mask)
     stability_dict, _, _, _, _ = eval_stability(x, one_hot, node_mask, edge_mask, dataset=args.dataset,
@@ -199,7 +209,7 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
     out = dict(stability=stability_dict, best_stable=order[stable[order]], x=x, one_hot=one_hot, node_mask=node_mask, edge_mask=edge_mask, target_function_values=_like_ref(tvals),
                pred=_like_ref(pred), best=order, seconds=seconds, molecules_per_second=x.shape[0] / seconds)
     if with_atoms:
-        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check))
+        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

@@ -10,16 +10,20 @@ rdkit_valid (gor2goa.py:298-324): bond orders 1 / 2 and formal charges from elem
 (gaudi_bond_orders, one wavefront per molecule); the rule is stated in DESIGN.md section 8h.  "Built" means gor2goa did not raise;
 "valid" means built and ``kekule_status == 0``.
 
+``canonical`` (and ``rings_to_atoms(..., canonical=True)``) numbers the heavy atoms canonically on the device
+(gaudi_canonical_order, one wavefront per molecule): ``canon_key`` is equal for two molecules if and only
+if their graphs of atoms are isomorphic, which is what the reference uses the InChI string for when it counts molecules.
+``canonical_molecule`` rebuilds the molecule in that numbering, and ``smiles`` / ``write_smiles`` write it as Kekule SMILES.
+
 What is NOT here: RDKit itself -- its sanitiser after AC2BO, ResonanceMolSupplier's single-structure condition (AC2mol) and InChI
-(gor2goa.py:264-324).  The fingerprint stands in for the InChI string when molecules are counted, and equal fingerprints do not
-prove that two molecules are isomorphic.  There is no CPU implementation behind these functions: without the HIP library they
-raise GaudiError."""
+strings (gor2goa.py:264-324).  The fingerprint is a hash: equal fingerprints do not prove that two molecules are isomorphic; equal
+``canon_key`` values do.  There is no CPU implementation behind these functions: without the HIP library they raise GaudiError."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (ATOMS_FINGERPRINT, ATOMS_MAX_ATOMS, ATOMS_MAX_BONDS, ATOMS_PLACE_H, BONDS_EMPTY, AtomTables, GaudiError,
-                   ValenceTables)
+from ._lib import (ATOMS_FINGERPRINT, ATOMS_MAX_ATOMS, ATOMS_MAX_BONDS, ATOMS_PLACE_H, BONDS_EMPTY, CANON_GAVE_UP, CANON_OK,
+                   AtomTables, GaudiError, ValenceTables)
 from .analyze import _engine, _key, _np, _pack, c_tables, ring_tables
 
 STATUS_NAMES = {0: "built", 1: "a ring without a fused neighbour in a multi-ring molecule",
@@ -31,6 +35,9 @@ KEKULE_STATUS_NAMES = {0: "a structure with at most 4 charged atoms", 1: "no str
                        5: "a bond index outside the atom list, a repeated bond or an element outside the table",
                        6: "more than 384 atoms, 192 heavy atoms or 384 bonds", 7: "no atoms (not built)",
                        8: "undecided: the subset search gave up (more than 25 atoms with two options; may depend on the numbering)"}
+CANON_STATUS_NAMES = {0: "canonical", 1: "gave up (more than 4096 search-tree nodes or 16 levels): a valid numbering, not canonical",
+                      2: "a bond index outside the atom list, a repeated bond or an element outside the table",
+                      3: "more than 384 atoms, 192 heavy atoms or 384 bonds, or an atom with more than 8 bonds", 4: "no atoms (not built)"}
 
 
 def atoms_list(dataset: str):
@@ -84,6 +91,23 @@ def c_valence_tables(dataset: str) -> ValenceTables:
     return t
 
 
+def _pack_atoms(molecules):
+    """Records or (atom_types, bonds) pairs -> elem [B,A], n_atoms [B], bonds [B,M,2], n_bonds [B] (int32, zero padded)."""
+    mols = []
+    for mol in molecules:
+        if isinstance(mol, dict):
+            built = mol["status"] == 0
+            mol = (mol["atom_types"], mol["bonds"]) if built else ((), ())
+        mols.append((np.asarray(_np(mol[0]), np.int32).reshape(-1), np.asarray(_np(mol[1]), np.int32).reshape(-1, 2)))
+    B = len(mols)
+    A, M = max(1, max(len(t) for t, _ in mols)), max(1, max(len(b) for _, b in mols))
+    elem, bonds = np.zeros((B, A), np.int32), np.zeros((B, M, 2), np.int32)
+    na, nb = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for i, (t, b) in enumerate(mols):
+        elem[i, :len(t)], bonds[i, :len(b)], na[i], nb[i] = t, b, len(t), len(b)
+    return elem, na, bonds, nb
+
+
 def bond_orders(molecules, dataset="cata", engine=None):
     """Bond orders and formal charges for a batch in one launch.  ``molecules``: a list of records from rings_to_atoms or of
     ``(atom_types [n], bonds [m,2])`` pairs, with or without placed hydrogens (a carbon with two bonds counts the H the reference
@@ -94,20 +118,11 @@ def bond_orders(molecules, dataset="cata", engine=None):
     A record whose ``status != 0`` (not built) yields kekule_status 7 (EMPTY).  kekule_status 8 (GAVE_UP) is no verdict: the
     bounded subset search ran out (possible only with more than 25 atoms that have two options), a structure may exist, and
     another atom numbering may find it -- every other status and n_charged do not depend on the numbering."""
-    mols = []
-    for mol in molecules:
-        if isinstance(mol, dict):
-            built = mol["status"] == 0
-            mol = (mol["atom_types"], mol["bonds"]) if built else ((), ())
-        mols.append((np.asarray(_np(mol[0]), np.int32).reshape(-1), np.asarray(_np(mol[1]), np.int32).reshape(-1, 2)))
-    if not mols:
+    molecules = list(molecules)
+    if not molecules:
         return []
-    B = len(mols)
-    A, M = max(1, max(len(t) for t, _ in mols)), max(1, max(len(b) for _, b in mols))
-    elem, bonds = np.zeros((B, A), np.int32), np.zeros((B, M, 2), np.int32)
-    na, nb = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    for i, (t, b) in enumerate(mols):
-        elem[i, :len(t)], bonds[i, :len(b)], na[i], nb[i] = t, b, len(t), len(b)
+    elem, na, bonds, nb = _pack_atoms(molecules)
+    B = len(na)
     raw = _engine(engine).bond_orders(c_valence_tables(dataset), elem, na, bonds, nb)
     return [dict(kekule_status=int(raw["status"][i]), orders=raw["order"][i, :nb[i]].astype(np.int64),
                  charges=raw["charge"][i, :na[i]].astype(np.int64), n_charged=int(raw["n_charged"][i])) for i in range(B)]
@@ -124,7 +139,8 @@ def _is_packed(molecules) -> bool:
     return [np.ndim(_np(m)) for m in molecules] == [3, 2, 1]
 
 
-def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False):
+def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
+                   canonical=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -137,7 +153,11 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
       fingerprint  int (0 unless asked for): equal for isomorphic heavy-atom graphs; equal keys do NOT prove isomorphism
     place_hydrogens: template H's leave the origin and every carbon with two heavy neighbours gets an H (appended after all other
     atoms in ascending parent index), 1.09 A out on the bisector in the molecular plane -- a complete structure.
-    bond_orders: a second launch (gaudi_bond_orders) adds kekule_status, orders, charges and n_charged to every record."""
+    bond_orders: a second launch (gaudi_bond_orders) adds kekule_status, orders, charges and n_charged to every record.
+    canonical: a launch of gaudi_canonical_order adds canon_status, canon_rank, canon_key and canon_nodes (see ``canonical``);
+    with bond_orders one further gaudi_bond_orders launch, on canonical_molecule's arrays, adds canon_kekule_status,
+    canon_orders, canon_charges and canon_n_charged: the structure of the molecule in its canonical numbering, the same for
+    every numbering of the input (empty / EMPTY for a molecule without a numbering).  The other keys are left as they are."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -166,6 +186,14 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     if bond_orders:
         for rec, extra in zip(out, _bond_orders(out, dataset, engine=eng)):
             rec.update(extra)
+    if canonical:
+        extras, codes = _canonical_raw(out, dataset, eng)
+        for rec, extra in zip(out, extras):
+            rec.update(extra)
+        if bond_orders:
+            mols = [_molecule_from_code(c, dataset) if c is not None else ((), ()) for c in codes]
+            for rec, extra in zip(out, _bond_orders(mols, dataset, engine=eng)):
+                rec.update({"canon_" + k: v for k, v in extra.items()})
     return out
 
 
@@ -250,3 +278,175 @@ def write_molfile(path_or_file, atoms3d, atom_types, bonds, dataset="cata", comm
     finally:
         if close:
             f.close()
+
+
+def canon_code(raw, i) -> bytes:
+    """The code of molecule i of a raw gaudi_canonical_order result: n_heavy (int32), the labels in rank order (uint8 each,
+    element * 8 + H count), the heavy-atom bonds as sorted (lo, hi) rank pairs (uint16 each), little-endian."""
+    H, E = int(raw["n_heavy"][i]), int(raw["n_hbonds"][i])
+    return np.array([H], "<i4").tobytes() + raw["label"][i, :H].tobytes() + raw["cbonds"][i, :E].astype("<u2").tobytes()
+
+
+def _canonical_raw(molecules, dataset, engine):
+    """-> (per-molecule dicts of canonical(), codes): the code of every molecule that has a numbering (OK or GAVE_UP), else None."""
+    atoms = atoms_list(dataset)
+    elem, na, bonds, nb = _pack_atoms(molecules)
+    raw = _engine(engine).canonical_order(len(atoms), atoms.index("H"), atoms.index("C"), elem, na, bonds, nb)
+    out, codes = [], []
+    for i in range(len(na)):
+        st = int(raw["status"][i])
+        code = canon_code(raw, i) if st in (CANON_OK, CANON_GAVE_UP) else None
+        codes.append(code)
+        out.append(dict(canon_status=st, canon_rank=raw["rank"][i, :na[i]].astype(np.int64), canon_key=code if st == CANON_OK else None,
+                        canon_nodes=int(raw["nodes"][i])))
+    return out, codes
+
+
+def canonical(molecules, dataset="cata", engine=None):
+    """Canonical numbering of the heavy atoms for a batch in one launch.  ``molecules``: as bond_orders takes them.  Returns one
+    dict per molecule:
+      canon_status  0 = canonical (CANON_STATUS_NAMES); 1 = gave up: canon_rank is a valid numbering, but may differ under
+                    renumbering (more than 4096 search-tree nodes: several identical disconnected pieces); above 1 the input was
+                    refused and canon_rank is zero
+      canon_rank    [n] the canonical index of every heavy atom, -1 for hydrogens
+      canon_key     bytes (canon_code: n_heavy, the (element, H count) labels in rank order, the heavy-atom bonds as sorted rank
+                    pairs), or None unless canon_status == 0.  Equal keys <=> isomorphic graphs of atoms, hydrogens placed or not
+      canon_nodes   search-tree nodes spent"""
+    molecules = list(molecules)
+    return _canonical_raw(molecules, dataset, engine)[0] if molecules else []
+
+
+def _molecule_from_code(code: bytes, dataset):
+    atoms = atoms_list(dataset)
+    H = int(np.frombuffer(code[:4], "<i4")[0])
+    label = np.frombuffer(code[4:4 + H], np.uint8).astype(np.int64)
+    heavy = np.frombuffer(code[4 + H:], "<u2").astype(np.int64).reshape(-1, 2)
+    n_h = label & 7
+    parents = np.repeat(np.arange(H, dtype=np.int64), n_h)
+    types = np.concatenate([label >> 3, np.full(len(parents), atoms.index("H"), np.int64)])
+    bonds = np.concatenate([heavy, np.stack([parents, H + np.arange(len(parents), dtype=np.int64)], 1)]).reshape(-1, 2)
+    return types, bonds[np.lexsort((bonds[:, 1], bonds[:, 0]))]
+
+
+def canonical_molecule(record_or_pair, dataset="cata", engine=None):
+    """The molecule in its canonical numbering -> (atom_types [n], bonds [m,2]): the heavy atoms in rank order, then every
+    hydrogen -- the listed ones and the one a carbon with two bonds implies -- in ascending parent rank; bonds as i <= j pairs,
+    the list sorted.  Isomorphic inputs give identical arrays, so bond_orders on them is a function of the molecule and not of
+    its numbering (unless either stage gave up).  A record that carries ``canon_key`` is decoded on the host; anything else takes
+    one gaudi_canonical_order launch.  Raises GaudiError for a molecule without a numbering."""
+    if isinstance(record_or_pair, dict) and record_or_pair.get("canon_key") is not None:
+        return _molecule_from_code(record_or_pair["canon_key"], dataset)
+    out, codes = _canonical_raw([record_or_pair], dataset, engine)
+    if codes[0] is None:
+        raise GaudiError(f"canonical_molecule: {CANON_STATUS_NAMES.get(out[0]['canon_status'], out[0]['canon_status'])}")
+    return _molecule_from_code(codes[0], dataset)
+
+
+_SMILES_VALENCES = {"B": (3,), "C": (4,), "N": (3, 5), "O": (2,), "S": (2, 4, 6)}
+
+
+def _smiles_atom(sym, n_h, charge, order_sum):
+    """Bare inside the organic subset when neutral and the H count is the implied one, else a bracket atom."""
+    if charge == 0 and sym in _SMILES_VALENCES:
+        fit = [v for v in _SMILES_VALENCES[sym] if v >= order_sum]
+        if n_h == (fit[0] - order_sum if fit else 0):
+            return sym
+    q = "" if charge == 0 else ("+" if charge > 0 else "-") + (str(abs(charge)) if abs(charge) > 1 else "")
+    return "[" + sym + ("" if n_h == 0 else "H" if n_h == 1 else f"H{n_h}") + q + "]"
+
+
+def smiles(record, dataset="cata"):
+    """Kekule SMILES of a record from rings_to_atoms(..., canonical=True, bond_orders=True), or None unless
+    ``canon_status == 0 and canon_kekule_status == 0``.  Host formatting, as write_molfile.  The string is a function of the
+    molecule: components joined by ".", each started at its lowest canonical rank; depth first, neighbours in ascending rank, all
+    but the last child in parentheses; the other bonds are ring closures with the lowest number free when the earlier atom is
+    written (a number closed at an atom is free again from the next atom on; 10..99 as %nn); "=" before the child atom or the
+    closing digit, single bonds never written; upper-case symbols; an atom is bare (B C N O S) when it is neutral and its H count
+    is the one the organic subset implies for the sum of its written bond orders, else bracketed."""
+    if record.get("canon_status") != CANON_OK or record.get("canon_kekule_status") != 0 or record.get("canon_key") is None:
+        return None
+    names = atoms_list(dataset)
+    types, bonds = _molecule_from_code(record["canon_key"], dataset)
+    orders, charges = np.asarray(record["canon_orders"], np.int64), np.asarray(record["canon_charges"], np.int64)
+    h_type = names.index("H")
+    H = int((types != h_type).sum())
+    if charges[H:].any():
+        raise GaudiError("smiles: a charged hydrogen")
+    adj = [dict() for _ in range(H)]
+    n_h = np.zeros(H, np.int64)
+    for (i, j), o in zip(bonds, orders):
+        if j >= H:
+            n_h[i] += 1
+        else:
+            adj[i][int(j)] = int(o)
+            adj[j][int(i)] = int(o)
+    order, children, closes, opens = {}, [[] for _ in range(H)], [[] for _ in range(H)], [[] for _ in range(H)]
+    roots = []
+    for root in range(H):
+        if root in order:
+            continue
+        roots.append(root)
+        order[root] = len(order)
+        stack = [(root, -1, iter(sorted(adj[root])))]
+        while stack:
+            a, parent, it = stack[-1]
+            for nb in it:
+                if nb == parent:
+                    continue
+                if nb not in order:
+                    order[nb] = len(order)
+                    children[a].append(nb)
+                    stack.append((nb, a, iter(sorted(adj[nb]))))
+                    break
+                if order[nb] < order[a]:
+                    closes[a].append(nb)
+                    opens[nb].append(a)
+            else:
+                stack.pop()
+    used, number = set(), {}
+
+    def digit(k):
+        return str(k) if k < 10 else f"%{k}"
+
+    def emit(a, parent):
+        out = ["=" if parent >= 0 and adj[a][parent] == 2 else "",
+               _smiles_atom(names[int(types[a])], int(n_h[a]), int(charges[a]), sum(adj[a].values()))]
+        for d in opens[a]:
+            k = next(k for k in range(1, 101) if k not in used)
+            if k > 99:
+                raise GaudiError("smiles: more than 99 ring closures open at once")
+            used.add(k)
+            number[(a, d)] = k
+        for nb in closes[a]:
+            out.append(("=" if adj[a][nb] == 2 else "") + digit(number[(nb, a)]))
+        out += [digit(number[(a, d)]) for d in opens[a]]
+        for nb in closes[a]:
+            used.discard(number.pop((nb, a)))
+        for i, c in enumerate(children[a]):
+            text = emit(c, a)
+            out.append(text if i == len(children[a]) - 1 else "(" + text + ")")
+        return "".join(out)
+
+    import sys
+    limit = sys.getrecursionlimit()
+    if limit < 3 * H + 100:
+        sys.setrecursionlimit(3 * H + 100)
+    try:
+        return ".".join(emit(r, -1) for r in roots)
+    finally:
+        sys.setrecursionlimit(limit)
+
+
+def write_smiles(path_or_file, records, dataset="cata"):
+    """One line per record: its SMILES, or an empty line where smiles() gives None.  -> the number of strings written."""
+    f, close = _open(path_or_file)
+    n = 0
+    try:
+        for rec in records:
+            text = smiles(rec, dataset)
+            n += text is not None
+            f.write((text or "") + "\n")
+    finally:
+        if close:
+            f.close()
+    return n

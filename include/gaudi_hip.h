@@ -95,7 +95,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -536,6 +536,44 @@ int gaudi_bond_orders(gaudi_handle* h, const gaudi_valence_tables* tables, int B
 /* Number of gaudi_bond_orders launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_bonds_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Canonical numbering of a graph of atoms, for B molecules in one launch. ----
+ * The identity of a built molecule that does not depend on its atom numbering (what the reference takes from the InChI string,
+ * analyze/analyze.py:180-231).  The labelled graph: vertices = the non-hydrogen atoms; vertex label = element * 8 + H count, the
+ * H count being the listed H neighbours plus one for a carbon with exactly two bonds (the H build_molecule_aromatic adds), so a
+ * molecule has the same graph with and without placed hydrogens; edges = the bonds between non-hydrogen atoms, unlabelled (bond
+ * orders and formal charges belong to one resonance structure, not to the molecule).  The code of a numbering is n_heavy, the
+ * labels in rank order and the edges as sorted (lo, hi) pairs of ranks; the canonical numbering is the one with the
+ * lexicographically smallest code over the leaves of an individualisation-refinement search (csrc/canon.inc, DESIGN.md section
+ * 8i).  Two molecules get equal codes if and only if their labelled graphs are isomorphic. */
+#define GAUDI_CANON_MAX_ATOMS 384   /* as GAUDI_BONDS_MAX_*: everything gaudi_rings_to_atoms emits fits */
+#define GAUDI_CANON_MAX_HEAVY 192
+#define GAUDI_CANON_MAX_BONDS 384
+#define GAUDI_CANON_MAX_DEGREE 8    /* bonds of one atom */
+#define GAUDI_CANON_MAX_NODES 4096  /* search-tree nodes per molecule; one node = one refinement to an equitable colouring */
+#define GAUDI_CANON_MAX_DEPTH 16    /* individualisations on one path of the tree */
+/* status_out codes; BAD_INPUT, OVERFLOW and EMPTY leave every output of the molecule zero. */
+#define GAUDI_CANON_OK 0
+#define GAUDI_CANON_GAVE_UP 1    /* the tree has more than GAUDI_CANON_MAX_NODES nodes or a path deeper than GAUDI_CANON_MAX_DEPTH
+                                    (many identical disconnected pieces: three benzenes need 16 903 nodes).  The outputs are a
+                                    valid numbering and its code, but NOT canonical: they may differ under renumbering */
+#define GAUDI_CANON_BAD_INPUT 2  /* as GAUDI_BONDS_BAD_INPUT: a bond index outside 0..n_atoms-1, a bond from an atom to itself or
+                                    listed twice, an element outside 0..n_elems-1                                            */
+#define GAUDI_CANON_OVERFLOW 3   /* more than 384 atoms, 192 non-hydrogen atoms or 384 bonds; an atom with more than 8 bonds or a
+                                    non-hydrogen atom with more than 7 hydrogens                                             */
+#define GAUDI_CANON_EMPTY 4      /* n_atoms = 0: what a molecule gaudi_rings_to_atoms did not build looks like                */
+/* Inputs as gaudi_bond_orders takes them; n_elems = len(ATOMS_LIST[dataset]) <= 8, h_elem / c_elem = the indices of H and C.
+ * One 64-lane wave per molecule, integer arithmetic only, one launch.  rank_out [B][A]: the canonical index of a non-hydrogen
+ * atom, -1 for hydrogens and padding; n_heavy_out [B]; label_out [B][A]: element * 8 + H count in rank order; n_hbonds_out [B]:
+ * bonds between non-hydrogen atoms; cbonds_out [B][M][2]: those bonds as (lo, hi) rank pairs, sorted; nodes_out [B]: search-tree
+ * nodes spent; status_out [B].  The outputs are a function of the molecule's own arrays (never of its place in the batch) and
+ * bit for bit what gaudi_host_canonical_order returns.  A molecule that fails never disturbs the others of the batch. */
+int gaudi_canonical_order(gaudi_handle* h, int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                          const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int32_t* rank_out,
+                          int32_t* n_heavy_out, uint8_t* label_out, int32_t* n_hbonds_out, uint16_t* cbonds_out,
+                          int32_t* nodes_out, int32_t* status_out);
+/* Number of gaudi_canonical_order launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
+int gaudi_canon_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -558,6 +596,12 @@ int gaudi_host_atoms_to_rings(const gaudi_perception_tables* tables, int B, int 
 int gaudi_host_bond_orders(const gaudi_valence_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
                            const int32_t* bonds, const int32_t* n_bonds, uint8_t* order_out, int8_t* charge_out,
                            int32_t* n_charged_out, int32_t* status_out);
+/* gaudi_canonical_order without a handle: the same source text (csrc/canon.inc: canonical_order) compiled for the host and run
+ * serially.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_canonical_order(int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                               const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int32_t* rank_out,
+                               int32_t* n_heavy_out, uint8_t* label_out, int32_t* n_hbonds_out, uint16_t* cbonds_out,
+                               int32_t* nodes_out, int32_t* status_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),
