@@ -131,6 +131,7 @@ struct gaudi_handle {
   bool split = true;          // 8-wave kernels: GEMMs on the fp16 matrix pipe with operands split into fp16 pairs (GAUDI_EDGE_MATH=fp32: off)
   bool no_fr = false;         // GAUDI_NO_FR=1: never the FR instantiation of the resident full-ring kernel (kern8s2_*.hip)
   bool no_n1 = false;         // GAUDI_NO_N1=1: never the N1 instantiation of the resident full-ring kernel (kern8s1_*.hip)
+  bool no_side = false;       // GAUDI_NO_SIDE=1: the N1 fused kernel never runs its side job (w8_pred.h: pred_forward, SD)
   std::string last_key;       // key_name of the kernel the most recent launch ran (gaudi_last_kernel_key)
   std::vector<std::string> key_log;  // the distinct key_names launched since gaudi_create, in first-launch order (gaudi_kernel_key_log)
   bool wide_full = true;      // GAUDI_WIDE_FULL=0: wide groups that do not fit the full ring run on the half ring (round 5)
@@ -788,11 +789,15 @@ static int build_meta8(int B, int N, const float* node_mask, const float* edge_m
 // (kernel_table.h).  A build that links fewer of them (tools/build_stamped.sh, tools/build_variant.sh) finds fewer kernels.
 KernelTable* gaudi::g_kernel_tables;
 
-static kernel_fn find_kernel(const KernelKey& k) {
+static const KernelEntry* find_entry(const KernelKey& k) {
   for (const KernelTable* t = g_kernel_tables; t; t = t->next)
     for (int i = 0; i < t->n; ++i)
-      if (t->entries[i].key == k) return t->entries[i].fn;
+      if (t->entries[i].key == k) return &t->entries[i];
   return nullptr;
+}
+static kernel_fn find_kernel(const KernelKey& k) {
+  const KernelEntry* e = find_entry(k);
+  return e ? e->fn : nullptr;
 }
 static std::string key_name(const KernelKey& k) {
   char buf[160];
@@ -1028,6 +1033,10 @@ static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long
   HIPCHECK(h, hipGetLastError());
   h->last_key = key_name(key);
   if (std::find(h->key_log.begin(), h->key_log.end(), h->last_key) == h->key_log.end()) h->key_log.push_back(h->last_key);
+  // A launch that runs the side job -- the plan placed its rows AND the kernel launched has the job compiled in -- says so behind
+  // its key (the log keeps the table's keys: the job is a launch parameter, not an instantiation)
+  if (const KernelEntry* e = find_entry(key); e && (e->side & 1) && P.side_off != 0) h->last_key += " SD=" + std::to_string(e->side);
+  if (getenv("GAUDI_DEBUG_PLAN")) fprintf(stderr, "[launch] %s\n", h->last_key.c_str());
   if (h->prof) {
     HIPCHECK(h, h->prof_log.end(h->stream, ev));
     h->prof_steps += steps;
@@ -1382,17 +1391,34 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   P.ncomp = packed ? h->d_ncomp.as<int32_t>() : nullptr;
   // Kept split copy of h (w8_nodes_f16.h: node_ctx_keep): behind everything the plan of BOTH networks needs, when 160 KiB leave the
   // room -- C2 / C3 do (46 KB free), 20-22 node slots do not.  Same results either way (the copy is a function of h alone).
+  // The side job of the N1 fused kernel (w8_pred.h: pred_forward, SD; asked for through P.side_off): the last wave of EVERY workgroup is without an
+  // edge tile (at most 7 tiles each: 11 fully connected nodes), h's copy is kept, and the job's rows -- [node slots][hpp + 4], in
+  // front of that copy -- fit too.  Same results as the N1 kernel.
   P.hk_off = 0;
+  P.side_off = 0;
   int hk = 0;
+  bool side_run = false;
   if (h->keep_h && GAUDI_NODE_F16 && acc.mode >= 1 && nodes == kResident) {
     const size_t floats = lds_bytes8(hpe, hpp, n_slots, Dz, M.S, acc.pubx, acc.mode) / sizeof(float);
     const size_t at = (floats + 3) & ~(size_t)3;
     const size_t need = (size_t)w8::nh_keep_floats(std::max(hpe, hpp), n_slots);
-    if ((at + need) * sizeof(float) + 1024 <= 160 * 1024) {
+    KernelKey kn = key8(hpe, hpp, 1, false);  // (the fused N1 kernel this plan's guided launches take, if it has the job)
+    kn.n1 = true;
+    const KernelEntry* const en = find_entry(kn);
+    const bool side_want = !h->no_side && n1_run && hpe && hpp && !mr_run && en != nullptr && (en->side & 1) &&
+                           *std::max_element(M.ntiles.begin(), M.ntiles.begin() + B) <= w8::kWaves - 1;
+    const size_t side = (size_t)n_slots * (hpp + 4);  // (a multiple of 4 floats)
+    if (side_want && (at + side + need) * sizeof(float) + 1024 <= 160 * 1024) {
+      P.side_off = (int)at;
+      P.hk_off = (int)(at + side);
+      hk = (int)need;
+      side_run = true;
+    } else if ((at + need) * sizeof(float) + 1024 <= 160 * 1024) {
       P.hk_off = (int)at;
       hk = (int)need;
     }
   }
+  if (getenv("GAUDI_DEBUG_PLAN")) fprintf(stderr, "[plan] side=%d side_off=%d hk_off=%d hk=%d\n", (int)side_run, P.side_off, P.hk_off, hk);
   if (pg_run) {  // one [node slots][hpp + 4] buffer per workgroup
     const size_t stride = ((size_t)n_slots * (hpp + 4) + 63) / 64 * 64;
     HIPCHECK(h, h->d_gnode.reserve(sizeof(float) * (stride * (size_t)B + 256)));
@@ -1563,6 +1589,7 @@ int gaudi_create(int device, gaudi_handle** out) {
   if (const char* v = getenv("GAUDI_PRED_ROUNDS")) h->pred_rounds = atoi(v) != 0;
   h->no_fr = getenv("GAUDI_NO_FR") != nullptr;
   h->no_n1 = getenv("GAUDI_NO_N1") != nullptr;
+  h->no_side = getenv("GAUDI_NO_SIDE") != nullptr;
   h->plan.waves = h->variant;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;

@@ -28,6 +28,8 @@ inline bool operator==(const KernelKey& a, const KernelKey& b) {
 struct KernelEntry {
   KernelKey key;
   kernel_fn fn;
+  int side;  // not part of the key: stages of the side job the kernel has compiled in (sampler_kernel.h: V8T, SD); a launch asks for
+             // the job through KParams::side_off, and a kernel without it ignores that
 };
 template <class V, int HPE, int HPP, bool VT = false>
 constexpr KernelEntry entry() {
@@ -44,6 +46,7 @@ constexpr KernelEntry entry() {
   e.key.hpp = HPP;
   e.key.vt = VT;
   e.fn = &sampler_kernel_v<V, HPE, HPP, VT>;
+  e.side = HPP != 0 ? V::kSD : 0;  // (the job is the predictor's)
   return e;
 }
 

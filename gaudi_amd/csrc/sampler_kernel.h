@@ -84,6 +84,8 @@ struct KParams {
   // counters at kernel entry [0], [1] and at the end of its last step [2], [3] -- the clock the chip HELD under this kernel's
   // load (1.7-2.0 GHz against the nominal 2.4 the roofline peaks assume), bench.py: roofline.clock_mhz.  nullptr otherwise.
   unsigned long long* clock_out;
+  int side_off;                // the N1 fused kernel: float offset (from the start of LDS) of the rows its last wave leaves for the
+                               // predictor's node MLP (w8_pred.h: pred_forward, SD), 0 = no side job in this launch
   int hk_off;                  // 8-wave split kernels: float offset (from the start of LDS) of the kept split copy of h, 0 = none
                                // (w8_nodes_f16.h: node_ctx_keep; placed by the host behind the whole plan when 160 KiB leave the room)
   // Value targets (gaudi_sample_target / gaudi_step_target): read by the VT instantiations of the kernels only (sampler_kernel_v),
@@ -125,6 +127,7 @@ struct V4T {
   // what the host's kernel table files an instantiation under (kernel_table.h: KernelKey); no device code reads these
   static constexpr int kWaveCount = 4, kSplit = 0, kGN = GN ? 1 : 0, kEF = EF;
   static constexpr bool kMR = false, kFR = false, kPG = false, kN1 = false;
+  static constexpr int kSD = 0;
   using Graph = gaudi::MolGraph;
   template <int HP> using EdmSmem = gaudi::NetSmem<HP, GN, EF>;
   __device__ __forceinline__ static void set_rows(Graph&, const int*, int, int) {}  // the 4-wave kernels are never packed
@@ -309,9 +312,10 @@ __device__ __attribute__((noinline)) void edm8_call(EdmDev W_, Graph8Args ga_, f
 }
 // the predictor's forward and reverse passes are separate functions too (the reverse pass holds three 52-register
 // operand sets at its peak; allocated together with the forward it spilled twice as much)
-template <int HP, int SP, bool MR, int GN = 0, int FL = 0, bool PG = false>
+// SD: w8_pred.h, pred_forward -- side_: float offset of the side wave's output rows (KParams::side_off), 0 = no side job
+template <int HP, int SP, bool MR, int GN = 0, int FL = 0, bool PG = false, int SD = 0>
 __device__ __attribute__((noinline)) void pred_fwd8_call(PredDev W_, Graph8Args ga_, float t_val_, float* stash_, float readout_div_,
-                                                         float* gnode_ = nullptr) {
+                                                         float* gnode_ = nullptr, int side_ = 0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const PredDev W = uni(W_);
   const Graph8Args ga = uni(ga_);
@@ -320,7 +324,8 @@ __device__ __attribute__((noinline)) void pred_fwd8_call(PredDev W_, Graph8Args 
   w8::PredSmem<HP, SP, GN, PG> sm;
   sm.carve(L.net, ga.N, ga.S, ga.pubx, (GN || PG) ? uni(gnode_) : nullptr);
   sm.hk = ga.hk ? smem + ga.hk : nullptr;
-  w8::pred_forward<HP, SP, MR, GN, FL>(W, mg, sm, L.sZ, uni(t_val_), uni(stash_), uni(readout_div_), (int)threadIdx.x);
+  if constexpr (SD != 0) sm.side = w8::lds_at(uni(side_));
+  w8::pred_forward<HP, SP, MR, GN, FL, SD>(W, mg, sm, L.sZ, uni(t_val_), uni(stash_), uni(readout_div_), (int)threadIdx.x);
 }
 template <int HP, int SP, bool MR, int GN = 0, int FL = 0, bool PG = false>
 __device__ __attribute__((noinline)) void pred_bwd8_call(PredDev W_, Graph8Args ga_, float* stash_, float readout_div_, int resume_,
@@ -348,9 +353,14 @@ __device__ __attribute__((noinline)) void pred_bwd8_call(PredDev W_, Graph8Args 
 // N1: the resident single-round kernel for workgroups of at most 16 node slots whose tail blocks hold one k-step: its node GEMMs are
 //     compiled for ONE column tile (w8_nodes_f16.h: kNodeOneTile; kern8s1_*.hip).  Same arithmetic in the same order as the plain
 //     kernel; nothing but the node GEMMs' form depends on it
-template <int SP, bool MR = false, int GN = 0, bool FR = false, bool PG = false, bool N1 = false>
+// SD: (N1 only, bit 0) the predictor's forward pass can give its last wave a side job during the edge phases (w8_pred.h:
+//     pred_forward); the host asks for it per launch (KParams::side_off) when no workgroup has an edge tile for that wave.  Same
+//     results either way
+template <int SP, bool MR = false, int GN = 0, bool FR = false, bool PG = false, bool N1 = false, int SD = 0>
 struct V8T {
   static_assert(!N1 || (!MR && GN == 0 && !FR && !PG), "N1 is a form of the plain resident kernel");
+  static_assert(SD == 0 || N1, "the side job is a form of the N1 kernel");
+  static constexpr int kSD = SD;  // (kernel_table.h: KernelEntry::side)
   static constexpr int kFL = N1 ? w8::kNodeOneTile : (MR || GN != 0 || FR) ? w8::kNodeFresh : w8::kNodePlain;
   static constexpr int kThreads = w8::kThreads;
   static constexpr int kSplit = SP;
@@ -381,6 +391,7 @@ struct V8T {
     mg.pubx = P.pubx;
     mg.pub_ch = P.pub_ch;
     mg.hk = P.hk_off;
+    mg.side = P.side_off;
     mg.mask = sMask; mg.edge = sEdge; mg.em = sEm; mg.seg = sSeg; mg.soff = sOff; mg.sidx = sIdx;
     return base;
   }
@@ -417,7 +428,7 @@ struct V8T {
     (void)sTmp;
     w8::PredSmem<HP, SP, GN, PG> sm;
     sm.carve(net, mg.N, mg.S, mg.pubx, gnode);
-    if (phase != 2) pred_fwd8_call<HP, SP, MR, GN, kFL, PG>(W, gargs(mg), t_val, stash, readout_div, gnode);
+    if (phase != 2) pred_fwd8_call<HP, SP, MR, GN, kFL, PG, SD>(W, gargs(mg), t_val, stash, readout_div, gnode, SD != 0 ? mg.side : 0);
     // (a value target takes out-of-line helpers around the unchanged affine code; vt is a compile-time nullptr in every
     // instantiation but the VT ones, so these branches exist in those alone)
     if (vt != nullptr) vt_seed8(vt, b, srow, W.K, (int)(sm.pred - lds_base()));

@@ -593,6 +593,7 @@ struct MolGraph {
   int NC;                 // node columns that matter: 1 + last node that is live or touches a live edge (<= N)
   int ntiles, rounds;     // 16-slot tiles of THIS molecule, ceil(ntiles / 8)
   int pubx, pub_ch;       // predictor reverse pass: see w8_pred.h
+  int side = 0;           // float offset of the side wave's rows (w8_pred.h: PredSmem::side), 0 = no side job in this launch
   int hk = 0;             // float offset of the kept split copy of h from the start of LDS, 0 = none (w8_nodes_f16.h)
   const float* mask;      // LDS [N]
   const uint32_t* edge;   // LDS [S]  edge words (ew_* above)

@@ -312,6 +312,11 @@ struct NodeCtxH {
   float* scales_b = nullptr;  // the second source's, when they do not follow the first's (a kept copy of h: node_ctx_keep)
 };
 
+// what y starts from
+struct YInitBias {};
+struct YInitRows {
+  const float* y;
+};
 // One node GEMM of the workgroup (all waves call it; N <= 16 MAXNT node columns).
 //   TWO: a second source (Wb, sXb).  do_split_a = false: an earlier call of this phase left the first source's split copy in
 //   cx.split_a (P and Q share h, the two transposed GEMMs of dnpre share it).  PIN: chunks of Wa that were loaded ahead of the call
@@ -320,14 +325,17 @@ struct NodeCtxH {
 // places a barrier between this call's stores to sY and their readers, as for the fp32 form.
 // sXb: the second source's rows, a pointer or a row source (RowsOne / RowsSum above).
 // NU (microbenchmark only, GAUDI_NODE_ABLATE & 8): the output tiles this body loads and multiplies, 0 = the geometry's.
+// sXa: the first source's rows, a pointer or a row source too.  yinit (YInitRows): y starts from the rows of an LDS array [N][HP + 4]
+// instead of the bias -- a first source's whole contribution computed elsewhere (side_job_h below), bias and tail step included.
 template <int HP, int EPI, bool TWO, int MAXNT, int PIN = kAheadOne, int POUT = kAheadOne, int FL = kNodePlain, int TAIL = kTailRuntime,
-          int NU = 0, class XB = const float*>
-__device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float* sXa, bool do_split_a, int Wb, const XB& sXb,
+          int NU = 0, class XB = const float*, class XA = const float*, class YI = YInitBias>
+__device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sXa, bool do_split_a, int Wb, const XB& sXb,
                                             const float* sBias, float* sY, const float* sRes, const float* sMask, int N, int wave,
                                             int lane, const NodeCtxH& cx, NodePFH<HP>& pf, int nextW = -1, float* gPre = nullptr,
                                             uint32_t* sMaxOut = nullptr /* LDS [N], zeroed: max |y| bits of every node's row */,
-                                            NodeStampH* ns = nullptr) {
+                                            NodeStampH* ns = nullptr, const YI& yinit = YI{}) {
   (void)ns;
+  (void)yinit;
   using G = NodeGeoH<HP>;
   constexpr int T = G::T, LD = HP + 4, NTW = NU > 0 ? NU : G::NTW, nc = G::nc, D = G::D;
   constexpr int kIn = PIN < D ? PIN : D, kOut = POUT < D ? POUT : D;
@@ -386,6 +394,8 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
       acc0[j][u] = splat(0.f);
       acc1[j][u] = splat(0.f);
       y[j][u] = sBias != nullptr ? *(const f4*)(sBias + 16 * t + 4 * g) : splat(0.f);
+      if constexpr (std::is_same<YI, YInitRows>::value)  // (columns >= N are never stored)
+        y[j][u] = j * 16 + c < N ? *(const f4*)(yinit.y + (j * 16 + c) * LD + 16 * t + 4 * g) : splat(0.f);
     }
   struct BH {
     u4 h, l;
@@ -556,6 +566,124 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const float*
     }
   });
   NSTAMP(6);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Side job (round 10): ONE wave computes a whole one-source node GEMM  Y[n][o] = bias[o] + sum_k W[o][k] X[n][k]  for one column
+// tile, from a split copy of X that stays in place (the kept copy of h), while the other waves run an edge phase in which it has no
+// tile.  Same images, same chunk order and the same operations per output element as node_gemm_h -- bias; the tail's fp32 step; per
+// K chunk w_hi x_lo, w_hi x_hi, w_lo x_hi; y += (acc0 + acc1 2^-11) sc -- so Y holds the bits node_gemm_h's y holds behind its first
+// source, and a GEMM that starts from Y (YInitRows) ends on the bits of the two-source call.
+// The job is cut into STEPS that fit between two trip barriers: one K chunk of a GROUP of at most 7 output tiles (14 one-KiB loads,
+// 21 matrix instructions; 56 registers of weights, 56 of acc0 / acc1) -- a wave's 26 requests take as long as a trip (DESIGN
+// C.1).  Step s = (group s / nc, chunk s % nc); a group's last step adds the tail step and the fold and stores its rows.  The
+// weights of step s + 1 are requested behind step s's matrix instructions (one register set) and fly across the barrier.
+// Tail blocks hold ONE k-step here (kTailOne): the side job belongs to the N1 kernels.
+template <int HP>
+struct SideGeoH {
+  static constexpr int T = HP / 16, nc = nh_chunks(HP), TG = 7;
+  static constexpr int NG = (T + TG - 1) / TG;
+  static constexpr int kSteps = NG * nc;
+  static constexpr bool odd = nh_odd(HP);
+  static_assert(nc >= 1, "at least one fp16 chunk");
+  __host__ __device__ static constexpr int tiles(int gq) { return (gq + 1) * TG <= T ? TG : T - gq * TG; }
+  // loads step s issues: two units per tile, and the group's tail weights with its last chunk; none outside the job
+  __host__ __device__ static constexpr int loads(int s) {
+    return (s < 0 || s >= kSteps) ? 0 : tiles(s / nc) * (2 + ((odd && s % nc == nc - 1) ? 1 : 0));
+  }
+};
+template <int HP>
+struct SideJobH {
+  using G = SideGeoH<HP>;
+  u4 w[G::TG][2];
+  float tw[G::TG];
+  f4 acc0[G::TG], acc1[G::TG];  // (y exists in a group's last step only: bias, tail step, fold, store -- tile by tile)
+};
+struct SideArgsH {
+  WBuf wh;
+  int W;              // fp32 float offset of the matrix (image at 2 W)
+  const float* bias;  // LDS [HP]
+  SplitBufH x;        // the split copy of the input (one column tile) and its descale factors
+  float winv;
+  float* out;         // LDS [N][HP + 4]
+  int N;
+};
+template <int HP, int S>
+__device__ __forceinline__ void side_issue(SideJobH<HP>& job, const SideArgsH& a, int lane) {
+  using G = SideGeoH<HP>;
+  if constexpr (S < G::kSteps) {
+    constexpr int gq = S / G::nc, m = S % G::nc;
+    static_for<G::tiles(gq)>([&](auto u_tag) {
+      constexpr int u = decltype(u_tag)::value, t = gq * G::TG + u;
+      const int so = (2 * a.W + m * nh_chunk_floats(HP)) * 4 + t * 2048;
+      job.w[u][0] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(a.wh.r, lane * 16, so, GAUDI_NODE_LOAD_AUX));
+      job.w[u][1] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(a.wh.r, lane * 16 + 1024, so, GAUDI_NODE_LOAD_AUX));
+    });
+    if constexpr (G::odd && m == G::nc - 1)
+      static_for<G::tiles(gq)>([&](auto u_tag) {
+        constexpr int u = decltype(u_tag)::value, t = gq * G::TG + u;
+        job.tw[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(a.wh.r, lane * 4, (2 * a.W + nh_tail_off(HP) + t * 256) * 4, 0));
+      });
+  }
+}
+template <int HP, int S>
+__device__ __forceinline__ void side_compute(SideJobH<HP>& job, const SideArgsH& a, int lane) {
+  using G = SideGeoH<HP>;
+  if constexpr (S < G::kSteps) {
+    constexpr int gq = S / G::nc, m = S % G::nc, NT = G::tiles(gq), LD = HP + 4;
+    const int c = lane & 15, g = lane >> 4;
+    if constexpr (m == 0)
+      static_for<NT>([&](auto u_tag) {
+        constexpr int u = decltype(u_tag)::value;
+        job.acc0[u] = splat(0.f);
+        job.acc1[u] = splat(0.f);
+      });
+    const float* q = a.x.chunk(m) + nh_bpos(c, g);
+    const u4 bh = *(const u4*)q, bl = *(const u4*)(q + 256);
+    static_for<NT>([&](auto u_tag) { constexpr int u = decltype(u_tag)::value; job.acc1[u] = mfma_h(job.w[u][0], bl, job.acc1[u]); });
+    static_for<NT>([&](auto u_tag) { constexpr int u = decltype(u_tag)::value; job.acc0[u] = mfma_h(job.w[u][0], bh, job.acc0[u]); });
+    static_for<NT>([&](auto u_tag) { constexpr int u = decltype(u_tag)::value; job.acc1[u] = mfma_h(job.w[u][1], bh, job.acc1[u]); });
+    if constexpr (m == G::nc - 1) {
+      const float xt = G::odd ? a.x.tail(HP)[g * 16 + c] : 0.f;  // [input k = g][column c]
+      const float sc = a.x.scale(HP)[c] * a.winv;
+      static_for<NT>([&](auto u_tag) {
+        constexpr int u = decltype(u_tag)::value, t = gq * G::TG + u;
+        f4 y = a.bias != nullptr ? *(const f4*)(a.bias + 16 * t + 4 * g) : splat(0.f);
+        if constexpr (G::odd) y = mfma1(job.tw[u], xt, y);
+        y = y + (job.acc0[u] + job.acc1[u] * (1.0f / kLoScale)) * sc;
+        if (c < a.N) *(f4*)(a.out + c * LD + 16 * t + 4 * g) = y;
+      });
+    }
+  }
+}
+// steps S .. of the job back to back: what the phase's trips left over
+template <int HP, int S>
+__device__ __forceinline__ void side_rest(SideJobH<HP>& job, const SideArgsH& a, int lane) {
+  if constexpr (S < SideGeoH<HP>::kSteps) {
+    side_compute<HP, S>(job, a, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    side_issue<HP, S + 1>(job, a, lane);
+    side_rest<HP, S + 1>(job, a, lane);
+  }
+}
+// The trips of one edge GEMM as the side wave runs them (w8_split.h: the schedule of edge_gemm_pq_s / edge_gemm_regs_s -- the same
+// barriers, the wave's share of the ring traffic, the ring's parity) with step S0 + trip of the job between the barriers.  The
+// ring's request goes out FIRST, the step's weights behind it: the barrier that opens the next trip then waits for the request
+// and lets the weights fly.
+template <int HP, int MODE, int S0>
+__device__ __forceinline__ void side_trips(RingS<HP, MODE>& ring, const WBuf& wb, int W, int nextW, int lane, SideJobH<HP>& job,
+                                           const SideArgsH& a) {
+  static_for<side_trip_count<HP, MODE>()>([&](auto tr_tag) {
+    constexpr int tr = decltype(tr_tag)::value, s = S0 + tr;
+    side_barrier<SideGeoH<HP>::loads(s)>();  // (step s's weights were requested behind this trip's group)
+    RingsStageSide<HP, MODE, tr>::run(ring, wb, W, nextW, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    side_compute<HP, s>(job, a, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    side_issue<HP, s + 1>(job, a, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    ring.par ^= 1;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------

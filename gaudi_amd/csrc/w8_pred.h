@@ -35,6 +35,7 @@ struct PredSmem {
   float* pred;                    // [16] pred | [16] dpred
   float* vec;                     // [10*HP] the current layer's vectors (cr,cd,b1,b2,wa,bc1,wc2,bn1,bn2,ba)
   float* hk = nullptr;            // kept split copy of h (w8_nodes_f16.h: node_ctx_keep), behind the whole plan; nullptr: none
+  float* side = nullptr;          // [N][HP+4] what the side wave leaves for the node MLP's first Linear (pred_forward: SD); nullptr: no side job
   __host__ __device__ static int floats(int N, int S, int pubx) {
     return EdgeRing<HP, SP>::kFloats + (GN ? gn_lds_buffers(GN) : PG ? 4 : 5) * N * (HP + 4) + pubx + 12 * N + 2 * align4(N) + 96 + S * 10 + 32 + 10 * HP;
   }
@@ -95,7 +96,14 @@ __host__ __device__ inline int pub_chunk_tiles(int S, long long avail_floats, in
 // MR: the kernel takes graphs of more than one round of eight edge tiles (more than 128 slots).  A separate instantiation: the
 // round loops (and the second copy of the reverse chain that parks du in the stash) cost the single-round kernels 2-4 % when
 // they live in the same function (hipcc's register allocation of the out-of-line phases changes), measured on C3.
-template <int HP, int SP = 0, bool MR = false, int GN = 0, int FL = 0, class SM = PredSmem<HP, SP, GN>>
+// SD (round 10, bit 0), in launches where the host placed sm.side -- the LAST wave has no edge tile in any workgroup, h's copy is
+// kept --: during the edge phase it computes the h half of the node MLP's first Linear, Wn1h h + bn1 -> sm.side, as a
+// side job (w8_nodes_f16.h: SideJobH), and the GEMM behind the phase is the one-source Wn1a (agg + agg1) that starts from those
+// rows.  Same operations per output element in the same order: the same bits.  Not in the LAST layer, whose edge phase is one GEMM --
+// 7 trips for 12 steps: the wave would finish the rest behind the phase with everybody waiting (measured: the whole gain and more,
+// DESIGN section 8, round 10); that layer keeps the two-source GEMM.  The side wave's copy of the trip schedule counts the K-tail
+// trip of a width that can have one, so a network without the tail (W.ktail) runs no side job.
+template <int HP, int SP = 0, bool MR = false, int GN = 0, int FL = 0, int SD = 0, class SM = PredSmem<HP, SP, GN>>
 __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& mg, const SM& sm, const float* sZ,
                                              float t_val, float* stash, float readout_div, int tid STAMP_DECL) {
   constexpr int LD = HP + 4;
@@ -154,6 +162,8 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
   };
   // a kept split copy of h: P splits it, Q and the node MLP's first Linear read the same copy (w8_nodes_f16.h: node_ctx_keep)
   const bool keep = NH && sm.hk != nullptr;
+  constexpr bool kSideA = (SD & 1) != 0;
+  static_assert(!kSideA || (NH && !MR && GN == 0 && !RI && FL == kNodeOneTile), "the side job is a form of the resident N1 kernel");
   constexpr int NV = (PredLayerW::vec_count(HP) + kThreads - 1) / kThreads;
   VecPF<NV> vpf;  // the next layer's vectors, loaded one node GEMM ahead
   vec_prefetch<NV, kThreads>(vpf, wb, PredLayerW::vec_off(lay.layer(0), HP), PredLayerW::vec_count(HP), tid);
@@ -161,6 +171,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
   for (int l = 0; l < W.L; ++l) {
     const bool last = l == W.L - 1;  // the last layer's coordinate update never reaches the readout
     const PredLayerW Lw(w, lay.layer(l), HP, sm.vec);
+    const bool side_l = kSideA && sm.side != nullptr && !last && (tw || !SplitGeo<HP, SP == 0 ? 1 : SP>::kTailOK);  // this layer's first node-MLP Linear is split between the side wave and the rest
     vec_commit<NV, kThreads>(vpf, sm.vec, PredLayerW::vec_count(HP), tid);
     if constexpr (STG) stage_rows(xs0, h, N * LD, wave, lane);
     for (int idx = tid; idx < N * LD; idx += kThreads) {
@@ -182,7 +193,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
       node_gemm_x<HP, EPI_NONE, false, GN, NH, kAheadOne, kAheadAll, FL>(wb, wbe, Lw.A, h, xs0, true, -1, nullptr, nullptr, Lw.b1, p, nullptr, nullptr, mg.NC, wave,
                                                     lane, tw, cx, pf, Lw.Bm, nullptr, sm.pmax);
       node_gemm_x<HP, EPI_NONE, false, GN, NH, kAheadAll, kAheadOne, FL>(wb, wbe, Lw.Bm, h, xs0, false, -1, nullptr, nullptr, nullptr, q, nullptr, nullptr, mg.NC,
-                                                    wave, lane, tw, cx, pf, Lw.Wn1h, nullptr, sm.qmax);
+                                                    wave, lane, tw, cx, pf, side_l ? Lw.Wn1a : Lw.Wn1h, nullptr, sm.qmax);
     }
     STAMP(ST_NODE);
     __syncthreads();
@@ -200,6 +211,19 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
     // rounds existed (a loop that folds away, or a lambda called once, cost C3 1-4 % through hipcc's register allocation):
     // the round is a plain block, and only an MR kernel has the backward jump that repeats it.
     int rd = 0;
+    if (side_l && wave == kWaves - 1) {
+      // the side wave's own code region for the whole edge phase (sharing one with the edge waves' accumulators, its live state
+      // adds to theirs): the trips of the GEMMs below with the steps of the side job between their barriers, then what is left
+      if constexpr (kSideA) {
+        constexpr int n = side_trip_count<HP, SP>();
+        SideJobH<HP> job;
+        const SideArgsH sa{wbe, Lw.Wn1h, Lw.bn1, SplitBufH{sm.hk + kScaleFloatsH, 1, sm.hk}, W.hinv, sm.side, mg.NC};
+        side_issue<HP, 0>(job, sa, lane);
+        side_trips<HP, SP, 0>(ring, wbe, split_off(Lw.W2), split_off(Lw.Wc1), lane, job, sa);
+        side_trips<HP, SP, n>(ring, wbe, split_off(Lw.Wc1), split_off(lay.layer(l + 1) + 2 * HP * HP), lane, job, sa);
+        side_rest<HP, 2 * n>(job, sa, lane);  // (widths whose job has more steps than the phase has trips)
+      }
+    } else
     {
     pred_fwd_round:
       const bool more = MR && rd + 1 < mg.rounds;
@@ -279,6 +303,13 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
       else __syncthreads();
     }
     STAMP(ST_MISC);
+    if constexpr (kSideA) {
+      if (side_l)
+        node_gemm_h<HP, EPI_SILU, false, 1, kAheadOne, kAheadOne, FL, nh_odd(HP) ? kTailOne : kTailRuntime>(
+            wbe, Lw.Wn1a, RowsSum<false>{agg, agg1, 1.f}, true, -1, (const float*)nullptr, nullptr, p, nullptr, nullptr, mg.NC, wave, lane,
+            hctx(), pf, Lw.Wn2, st + 2 * N * HP /* npre -> stash */, nullptr, nullptr, YInitRows{sm.side});
+    }
+    if (!side_l)
     node_gemm_x<HP, EPI_SILU, true, GN, NH, kAheadOne, kAheadOne, FL, SUM ? 1 : 0>(
         wb, wbe, Lw.Wn1h, h, xs0, !keep, Lw.Wn1a, agg, xs1, Lw.bn1, p, nullptr, nullptr, mg.NC, wave, lane, tw,
         keep ? node_ctx_keep<HP>(hctx(), sm.hk, mg.NC) : hctx(), pf, Lw.Wn2, st + 2 * N * HP /* npre -> stash */, nullptr, agg1);

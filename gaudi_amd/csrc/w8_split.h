@@ -215,6 +215,50 @@ __device__ __forceinline__ void rings_stage(RingS<HP, MODE>& r, const WBuf& wb, 
   rings_dma(r, wb, r.slot(r.par ^ 1), W, nextW, tr + 1, wave, lane);
 }
 
+// The trips of one edge GEMM as every wave counts them (edge_gemm_pq_s / edge_gemm_regs_s below; the side wave's copy of the schedule,
+// side_trips, must pass the same number of barriers).  The kernels that use this run matrices WITH a K tail at every width that
+// can have one (the host's condition for their N1 form: gaudi_hip.hip).
+template <int HP, int MODE>
+__host__ __device__ constexpr int side_trip_count() {
+  return SplitGeo<HP, MODE>::kTailOK ? SplitGeo<HP, MODE>::kTripsTail : SplitGeo<HP, MODE>::kTrips;
+}
+// RingsStageSide::run: rings_stage as the LAST wave (kWaves - 1) runs it while it works on a side job (w8_nodes_f16.h: SideJobH): the same units to the
+// same places, with the trip index -- and so the number of loads -- a compile-time fact.  The wave's weight stream shares the
+// in-order vmcnt counter with these loads: with their number known hipcc waits for a weight register with the exact count and the
+// barrier that opens the next trip (side_barrier) can leave the stream in flight.  The caller's chains always have a next matrix
+// (nextW >= 0): a branch around a load would make every later count the conservative one.
+// (a class template's static member: called as a function template from the second instantiation of side_trips, hipcc 7.2's host
+// pass fails to match it)
+template <int HP, int MODE, int TR>
+struct RingsStageSide {
+__device__ __forceinline__ static void run(const RingS<HP, MODE>& r, const WBuf& wb, int W, int nextW, int lane) {
+  using G = SplitGeo<HP, MODE>;
+  constexpr int n = side_trip_count<HP, MODE>();
+  constexpr bool nxt = TR + 1 >= n;
+  constexpr int t2 = nxt ? TR + 1 - n : TR + 1;
+  constexpr bool tt = G::kTailOK && t2 == n - 1;
+  constexpr int units = tt ? G::T : G::tiles_of(t2 % G::NH) * kPieces;
+  constexpr int rel = tt ? (G::NC - 1) * G::T * kPieces * G::kUnit : ((t2 / G::NH) * G::T + (t2 % G::NH) * G::CH) * kPieces * G::kUnit;
+  constexpr int first = (unsigned)((kWaves - 1) * units) / kWaves, count = units - first;  // (rings_dma: wave w = kWaves - 1)
+  static_assert(count <= G::UT, "the side wave's share of a group");
+  const int vo = lane * 16;
+  const int off = __builtin_amdgcn_readfirstlane(((nxt ? nextW : W) + rel + first * G::kUnit) * 4);
+  float* const l = r.slot(r.par ^ 1) + first * G::kUnit;
+  static_for<count>([&](auto u_tag) {
+    constexpr int U = decltype(u_tag)::value;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(wb.r, (__attribute__((address_space(3))) void*)l, 16, vo, off, U * G::kUnit * 4, 0);
+  });
+}
+};
+// the barrier that opens a trip for the side wave: the group this trip reads has landed when at most PENDING loads -- the weight
+// loads the wave issued BEHIND that group's request -- are still in flight (trip_barrier waits for all)
+template <int PENDING>
+__device__ __forceinline__ void side_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PENDING) : "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
 // The barrier that opens a trip.  With LDS-DMA the group this trip reads was written by the LDS-DMA loads (rings_dma) of ALL
 // waves: each wave retires its own (vmcnt) before the barrier -- hipcc does not track these loads for the __syncthreads
 // fence on every path (seen in the ISA: barriers with lgkmcnt(0) only, and a run-to-run difference in the results).

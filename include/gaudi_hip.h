@@ -83,7 +83,8 @@ const char* gaudi_last_error(const gaudi_handle* h);
 const char* gaudi_last_warning(const gaudi_handle* h);
 /* The kernel the most recent launch of the handle ran, as its kernel-table key ("waves=8 SP=1 MR=0 GN=0 FR=0 PG=0 N1=1 EF=2 HPE=192
  * HPP=208 VT=0": csrc/kernel_table.h), NUL-terminated and cut to n bytes; "" before the first launch.  For tests and tooling: which
- * instantiation a plan picked (GAUDI_NO_FR / GAUDI_NO_N1 at gaudi_create keep the resident full-ring kernel on its plain form). */
+ * instantiation a plan picked (GAUDI_NO_FR / GAUDI_NO_N1 at gaudi_create keep the resident full-ring kernel on its plain form).
+ * A launch in which the kernel's last wave ran its side job (GAUDI_NO_SIDE at gaudi_create: never) has " SD=1" behind the key. */
 int gaudi_last_kernel_key(const gaudi_handle* h, char* buf, int n);
 /* Every distinct key the handle has launched since gaudi_create, in first-launch order, one per line (each line ends in '\n'),
  * NUL-terminated and cut to n bytes.  gaudi_last_kernel_key names one launch; a call that makes two (a guided step on the 4-wave
