@@ -89,6 +89,28 @@ struct LaunchPlan {
   int pubx = 0, pub_ch = 0;  // reverse pass: extra floats of the du publish buffer, feature tiles published per chunk (plan_pub8)
 };
 
+// A value-target request (gaudi_sample_target / gaudi_step_target): the chain stages the parameter rows of ITS molecules
+// (request index = b0 + k), the window flags and the trace, and keeps every molecule alone in its workgroup.
+struct VtCall {
+  const gaudi_target_spec* spec = nullptr;
+  int K = 0, Btot = 0, b0 = 0;
+  float* trace = nullptr;  // host [rows][Btot][K + 2], zero-filled by the entry point, or nullptr
+};
+
+// What ONE call tells the planner beyond its graph (stage_graph / stage_graph8): filled in chain_host.inc, the defaults elsewhere.
+struct CallHints {
+  int min_slots = 0, force_waves = 0;  // gaudi_sample's sub-batches plan with their whole bucket's figures (cf. plan_min_slots)
+  bool cut = false;  // gaudi_sample cut this request into sub-batches
+  // Per-molecule kernel family (round 6): gaudi_sample sorts a request whose padded N is beyond the resident kernels' LDS limit into
+  // molecules that fit those kernels on their OWN (few enough live nodes and edge tiles) and the rest (V8G), and runs the two
+  // buckets one after the other.  narrow = node slots per workgroup of the first bucket's packed launch (< N); molmap =
+  // the bucket's molecule -> index in the request (the Philox key is the molecule's global sample index).
+  int narrow = 0;
+  const int32_t* molmap = nullptr;
+  bool may_pack = false;       // small molecules may share a workgroup (sampling chains only: run_chain)
+  const VtCall* vt = nullptr;  // the value-target request this call is part of
+};
+
 struct gaudi_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -113,14 +135,6 @@ struct gaudi_handle {
   DevBuf d_bonds[9];   // gaudi_bond_orders (bonds.inc): its four inputs, its tables and its four outputs
   DevBuf d_canon[11];  // gaudi_canonical_order (canon.inc): its four inputs and its seven outputs
   DevBuf d_vtpar, d_vttrace, d_vtdev;  // value targets: per-molecule parameter rows, the guidance trace, the VtDev that names them
-  // Value-target call in flight (gaudi_sample_target / gaudi_step_target set it around sample_impl / run_chain; nullptr otherwise):
-  // run_chain stages the parameter rows of ITS molecules (request index = b0 + k), the window flags and the trace, and keeps
-  // every molecule alone in its workgroup.
-  struct VtCall {
-    const gaudi_target_spec* spec = nullptr;
-    int K = 0, Btot = 0, b0 = 0;
-    float* trace = nullptr;  // host [rows][Btot][K + 2], zero-filled by the entry point, or nullptr
-  }* vt = nullptr;
   PinBuf p_pred, p_dpred;     // gaudi_sample_cb: pred [B,K] device -> host, dT/dpred [B,K] host -> device, once per step
   PinBuf p_z, p_dz;           // gaudi_sample_cbz: z_s [B,N,D] device -> host, scale * dT/dz host -> device
   DevBuf d_dz;
@@ -146,7 +160,6 @@ struct gaudi_handle {
                               // shared weight stream worth the second round), 2 = always (GAUDI_PAIRS)
   int num_cus = 256;
   bool pred_rounds = true;    // GAUDI_PRED_ROUNDS=0: guided calls with more than 128 edge slots go to the 4-wave kernels
-  bool pack_now = false;      // set by run_chain around stage_graph: this call may pack
   bool force_mr = false;      // GAUDI_FORCE_MR
   bool force_gn = false;      // GAUDI_FORCE_GN=1 at gaudi_create: use them whenever they exist (test knob)
   bool fix_noise = false;     // en_diffusion.py:562-566: one raw draw per call, broadcast over the batch
@@ -157,17 +170,9 @@ struct gaudi_handle {
   bool edm_stale = false;  // gaudi_edm_set_train_weights changed the weights after the sampler images were packed
   // Plan hint (gaudi_set_plan_hint): the kernel family and the edge-GEMM arithmetic of a call follow from batch-wide maxima
   // (edge slots, a node's live edges).  A shard of a larger logical batch plans with the WHOLE batch's figures, so that a
-  // molecule's rounding does not depend on where the batch was cut.  call_* = the same, set by gaudi_sample for its own
-  // sub-batches.
+  // molecule's rounding does not depend on where the batch was cut.  gaudi_sample passes the same for its own sub-batches as
+  // an argument (CallHints above).
   int plan_min_slots = 0, plan_force_waves = 0;
-  int call_min_slots = 0, call_force_waves = 0;
-  bool call_cut = false;      // gaudi_sample cut this request into sub-batches
-  // Per-molecule kernel family (round 6): gaudi_sample sorts a request whose padded N is beyond the resident kernels' LDS limit into
-  // molecules that fit those kernels on their OWN (few enough live nodes and edge tiles) and the rest (V8G), and runs the two
-  // buckets one after the other.  call_narrow = node slots per workgroup of the first bucket's packed launch (< N); call_molmap =
-  // the bucket's molecule -> index in the request (the Philox key is the molecule's global sample index).
-  int call_narrow = 0;
-  const int32_t* call_molmap = nullptr;
   bool keep_h = true;         // GAUDI_KEEP_H=0: every node GEMM that reads h splits it again (round 5)
   bool gn8_pack = true;       // GAUDI_GN8_PACK=0: V8G launches keep a molecule's nodes where the masks have them (round 5)
   bool family_split = false;  // GAUDI_FAMILY_SPLIT=1: per-molecule kernel family (below).  Off by default: the two buckets run as two launches
@@ -1140,11 +1145,11 @@ static void pack_groups(int B, int N, const float* node_mask, const float* edge_
 // -> GAUDI_OK, or a positive value = "run this call on the 4-wave kernels" (graph outside the 8-wave kernels' limits)
 // plan: written once, at the end (a fall-back or an error leaves it as it came)
 static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, KParams& P, int hpe,
-                        int hpp, LaunchPlan& plan) {
-  if (std::max(h->plan_force_waves, h->call_force_waves) == 4) return 1;  // the whole logical batch runs on 4 waves
+                        int hpp, const CallHints& hints, LaunchPlan& plan) {
+  if (std::max(h->plan_force_waves, hints.force_waves) == 4) return 1;  // the whole logical batch runs on 4 waves
   Meta8 M;
   std::string err;
-  int rc = build_meta8(B, N, node_mask, edge_mask, M, err, std::max(h->plan_min_slots, h->call_min_slots));
+  int rc = build_meta8(B, N, node_mask, edge_mask, M, err, std::max(h->plan_min_slots, hints.min_slots));
   if (rc == GAUDI_E_CAPACITY) return 1;
   if (rc) return fail(h, rc, err);
   // more than one round of eight edge tiles (a graph of more than 128 live-edge slots, e.g. a fully connected molecule of
@@ -1183,19 +1188,19 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   bool mr_run = mr;
   bool narrow_taken = false, use_pack = false, pg_run = false;
   // Round 6: a bucket of molecules that fit the resident kernels on their own (gaudi_sample: per-molecule kernel family) while the
-  // call's padded N does not -- packed groups of call_narrow (< N) node slots, one round of eight edge tiles.
-  if (h->call_narrow > 0 && h->call_narrow < N && h->pack_now && (int64_t)B * N < (1 << 28)) {
-    pack_groups(B, N, node_mask, edge_mask, M, pk, h->call_narrow, w8::kWaves, true, kMaxComp, h->call_molmap);
+  // call's padded N does not -- packed groups of hints.narrow (< N) node slots, one round of eight edge tiles.
+  if (hints.narrow > 0 && hints.narrow < N && hints.may_pack && (int64_t)B * N < (1 << 28)) {
+    pack_groups(B, N, node_mask, edge_mask, M, pk, hints.narrow, w8::kWaves, true, kMaxComp, hints.molmap);
     Meta8 M2;
-    rc = build_meta8(pk.G, h->call_narrow, pk.umask.data(), pk.uemask.data(), M2, err, 0, pk.align.data());
+    rc = build_meta8(pk.G, hints.narrow, pk.umask.data(), pk.uemask.data(), M2, err, 0, pk.align.data());
     if (rc != GAUDI_OK) return fail(h, rc, "per-molecule kernel family: " + err);
     const bool mr2 = hpp && M2.S > 16 * w8::kWaves;
-    const RingPlan p2 = plan_for(h->call_narrow, M2.S, mr2);
+    const RingPlan p2 = plan_for(hints.narrow, M2.S, mr2);
     if (p2.mode < 1 || mr2) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the resident plan of the small bucket does not fit");
     M = std::move(M2);
     B = pk.G;
     nm_used = pk.umask.data();
-    n_slots = h->call_narrow;
+    n_slots = hints.narrow;
     acc = p2;
     mode_u = p2.mode;
     mr_run = mr2;
@@ -1205,7 +1210,7 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   // buffers in a per-workgroup global scratch (split edge GEMMs, full ring, several rounds of edge tiles) -- before round 4
   // such calls fell to the 4-wave V4G kernels (fp32 matrix instructions, two launches per guided step)
   // Round 6: of the five, P and Q stay in LDS where that plan fits (kern8gp_*.hip; +3.6 % on 40-node molecules) -- a function of
-  // the widths, N and the edge slots the plan is made with (the whole batch's: call_min_slots / plan_min_slots), like the rest
+  // the widths, N and the edge slots the plan is made with (the whole batch's: hints.min_slots / plan_min_slots), like the rest
   NodeBuf gn8 = kResident;
   RingPlan gplan{1, 0, 0};
   if (!narrow_taken && (mode_u < 0 || h->force_gn8) && h->gn8 && h->split && (!hpe || h->edm_ws_bytes) && (!hpp || h->pred_ws_bytes) && node_f16_ok &&
@@ -1220,9 +1225,9 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
   if (mode_u < 0) return 1;
   // V8G sampling calls (round 6): every molecule alone in its workgroup as before, but its nodes COMPACTED to the front slots
   // (a hetero molecule's rings and orientation nodes are two blocks of the padded index range: n rings occupy columns up to
-  // N / 2 + n) -- fewer node-GEMM column tiles; the packed form also carries the molecule's index in the request (call_molmap).
-  if (gn8 && h->pack_now && h->pack && h->gn8_pack && (int64_t)B * N < (1 << 28)) {
-    pack_groups(B, N, node_mask, edge_mask, M, pk, N, 1 << 20, false, 1, h->call_molmap);
+  // N / 2 + n) -- fewer node-GEMM column tiles; the packed form also carries the molecule's index in the request (hints.molmap).
+  if (gn8 && hints.may_pack && h->pack && h->gn8_pack && (int64_t)B * N < (1 << 28)) {
+    pack_groups(B, N, node_mask, edge_mask, M, pk, N, 1 << 20, false, 1, hints.molmap);
     Meta8 M2;
     int pubx2 = 0, pub_ch2 = 0;
     if (build_meta8(pk.G, N, pk.umask.data(), pk.uemask.data(), M2, err, M.S, pk.align.data()) == GAUDI_OK && M2.S == M.S &&
@@ -1234,12 +1239,12 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
       acc.pub_ch = pub_ch2;
       use_pack = true;
     } else {
-      if (h->call_molmap) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the packed V8G plan does not fit");
+      if (hints.molmap) return fail(h, GAUDI_E_CAPACITY, "per-molecule kernel family: the packed V8G plan does not fit");
       pk = Pack();
     }
   }
   // (a row of the map holds molecule * N + node in 28 bits)
-  if (!gn8 && !narrow_taken && h->pack_now && h->pack && B > 1 && (int64_t)B * N < (1 << 28)) {
+  if (!gn8 && !narrow_taken && hints.may_pack && h->pack && B > 1 && (int64_t)B * N < (1 << 28)) {
     // Candidate group shapes, widest first.  WIDE groups (opt-in: GAUDI_PAIRS=1 for batches of at least two molecules per CU, 2
     // always): up to 2 N node slots and two rounds of eight edge tiles -- e.g. two 11-ring cata molecules, or three to four small
     // hetero ones, per workgroup.  Every node-level matrix is then streamed from L2 once for all of them and the per-GEMM fixed
@@ -1448,7 +1453,7 @@ static int stage_graph8(gaudi_handle* h, int B, int N, const float* node_mask, c
 
 // hpe / hpp: padded hidden sizes of the networks this call runs (0 = not used)
 static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, KParams& P, int hpe,
-                       int hpp) {
+                       int hpp, const CallHints& hints) {
   if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
   // a node slot's row word holds molecule * N + node in 28 bits (sampler_kernel.h: row_of / comp_of)
   if ((int64_t)B * N >= (1 << 28)) return fail(h, GAUDI_E_CAPACITY, "B * N must stay below 2^28 per call: cut the request into several calls");
@@ -1456,7 +1461,7 @@ static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, co
   // a sin_embedding denoiser (24 edge features per first Linear, egnn_new.py:269-273) exists in the 4-wave family only
   const bool se = hpe && h->ecfg.sin_embedding;
   if (h->variant == 8 && !h->force_gn && !se) {
-    const int rc8 = stage_graph8(h, B, N, node_mask, edge_mask, P, hpe, hpp, plan);
+    const int rc8 = stage_graph8(h, B, N, node_mask, edge_mask, P, hpe, hpp, hints, plan);
     if (rc8 == GAUDI_OK) h->plan = plan;
     if (rc8 <= 0) return rc8;
     P.pubx = P.pub_ch = 0;  // fall back to the 4-wave kernels for this call
@@ -1504,7 +1509,7 @@ static int stage_graph(gaudi_handle* h, int B, int N, const float* node_mask, co
   // kernels because one of them happens to be sparser.  A call that stands alone decides from its own edge lists (a sparse
   // hetero batch of 18-20 nodes fits the resident kernels where the dense graph would not).
   const int Dz = 3 + (hpe ? h->ecfg.in_node_nf : h->pcfg.in_nf);
-  const bool part_of_batch = h->plan_min_slots || h->plan_force_waves || h->call_min_slots || h->call_force_waves || h->call_cut;
+  const bool part_of_batch = h->plan_min_slots || h->plan_force_waves || hints.min_slots || hints.force_waves || hints.cut;
   const int ef = plan.ef = se ? 24 : 2;
   // (the V4G predictor-only kernel is the ordinary one for a sin_embedding handle too)
   const bool have_g = (!hpe || find_kernel(key4(hpe, 0, true, ef))) && (!hpp || find_kernel(key4(0, hpp, true)));
@@ -1861,7 +1866,7 @@ int gaudi_phi(gaudi_handle* h, int B, int N, const float* z, const float* t, con
   if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
   HIPCHECK(h, hipSetDevice(h->device));
   KParams P{};
-  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, 0);
+  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, 0, CallHints{});
   if (rc) return rc;
   fill_edm(h, P);
   const size_t zb = sizeof(float) * B * N * (3 + P.F);
@@ -1878,890 +1883,6 @@ int gaudi_phi(gaudi_handle* h, int B, int N, const float* z, const float* t, con
   if (rc) return rc;
   HIPCHECK(h, hipMemcpyAsync(eps_out, h->d_zout.p, zb, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(h, hipStreamSynchronize(h->stream));
-  return GAUDI_OK;
-}
-
-static int fill_pred(gaudi_handle* h, KParams& P, const float* target_w, int B, int N);  // pred_host.inc
-
-// diagnostics replacing assert_correctly_masked / assert_mean_zero_with_mask (utils.py:52-65) and the
-// CoG re-projection of en_diffusion.py:1000-1006 (batch-wide condition -> host side)
-static void finish_sample(int B, int N, const float* node_mask, float* x_out, int nanc, gaudi_diag* diag) {
-  float leak = 0.f, cog = 0.f, big = 0.f;
-  for (int b = 0; b < B; ++b) {
-    float s[3] = {0, 0, 0};
-    for (int n = 0; n < N; ++n)
-      for (int d = 0; d < 3; ++d) {
-        const float v = x_out[((size_t)b * N + n) * 3 + d];
-        s[d] += v;
-        big = std::max(big, std::fabs(v));
-        leak = std::max(leak, std::fabs(v * (1.f - node_mask[b * N + n])));
-      }
-    for (int d = 0; d < 3; ++d) cog = std::max(cog, std::fabs(s[d]));
-  }
-  int reproj = 0;
-  if (cog > 5e-2f) {
-    reproj = 1;
-    for (int b = 0; b < B; ++b) {
-      float cnt = 0.f;
-      for (int n = 0; n < N; ++n) cnt += node_mask[b * N + n];
-      cnt = std::max(cnt, 1.f);
-      for (int d = 0; d < 3; ++d) {
-        float s = 0.f;
-        for (int n = 0; n < N; ++n) s += x_out[((size_t)b * N + n) * 3 + d];
-        const float mean = s / cnt;
-        for (int n = 0; n < N; ++n) x_out[((size_t)b * N + n) * 3 + d] -= mean * node_mask[b * N + n];
-      }
-    }
-  }
-  if (diag) {
-    diag->max_masked_leak = leak;
-    diag->max_cog_abs = cog;
-    diag->max_cog_rel = cog / (big + 1e-10f);
-    diag->nan_count = nanc;
-    diag->reprojected = reproj;
-  }
-}
-
-// ---- value targets (gaudi_sample_target): one molecule's parameter row w | q | c | side | scale (device_common.h: target_seed)
-static void vt_pack_row(const gaudi_target_spec& sp, int K, int b, float* row) {
-  for (int k = 0; k < K; ++k) {
-    row[k] = sp.w ? sp.w[(sp.w_per_mol ? (size_t)b * K : 0) + k] : 0.f;
-    row[K + k] = sp.q ? sp.q[(sp.q_per_mol ? (size_t)b * K : 0) + k] : 0.f;
-    row[2 * K + k] = sp.c ? sp.c[(sp.c_per_mol ? (size_t)b * K : 0) + k] : 0.f;
-    row[3 * K + k] = sp.side ? (float)sp.side[(sp.side_per_mol ? (size_t)b * K : 0) + k] : 0.f;
-  }
-  row[4 * K] = sp.scale ? sp.scale[sp.scale_per_mol ? b : 0] : 1.f;
-}
-// refusals that need no device: K, sides, finiteness, the window against T (T <= 0: not checked)
-static const char* vt_check(const gaudi_target_spec* sp, int B, int K, int T) {
-  if (!sp) return "no target spec";
-#ifdef GAUDI_STAMPS
-  if (T > 0) return "value targets are not available in the GAUDI_STAMPS diagnostic build (it times the affine fused step only)";
-#endif
-  if (B <= 0) return "B must be positive";
-  if (sp->K != K) return "the target spec's K differs from the predictor's number of outputs";
-  if (K <= 0 || K > 16) return "a target spec takes 1 to 16 predictor outputs";
-  auto finite = [&](const float* a, int per_mol, size_t per) {
-    if (!a) return true;
-    const size_t n = per_mol ? (size_t)B * per : per;
-    for (size_t i = 0; i < n; ++i)
-      if (!std::isfinite(a[i])) return false;
-    return true;
-  };
-  if (!finite(sp->w, sp->w_per_mol, K) || !finite(sp->q, sp->q_per_mol, K) || !finite(sp->c, sp->c_per_mol, K) ||
-      !finite(sp->scale, sp->scale_per_mol, 1))
-    return "a target parameter (w, q, c or scale) is not finite";
-  if (sp->side) {
-    const size_t n = sp->side_per_mol ? (size_t)B * K : (size_t)K;
-    for (size_t i = 0; i < n; ++i)
-      if (sp->side[i] < -1 || sp->side[i] > 1) return "side must be -1 (lower bound), 0 (value) or +1 (upper bound)";
-  }
-  const bool dflt = sp->t_lo == 0 && sp->t_hi == 0;
-  if (!dflt && T > 0) {
-    if (sp->t_lo < 1 || sp->t_hi > T) return "the guidance window must lie inside 1..T";
-    if (sp->t_lo > sp->t_hi) return "the guidance window is empty (t_lo > t_hi)";
-  }
-  return nullptr;
-}
-
-// shared by gaudi_step / gaudi_decode / gaudi_sample
-static int run_chain(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, const float* z_in,
-                     bool do_init, int s_hi, int s_lo, bool do_decode, const float* noise, int draw_base, int n_draws,
-                     uint64_t seed, int64_t sample_offset, float std0, const float* target_w, float scale,
-                     float* z_out, float* x_out, float* onehot_out, int* nan_count, float* chain_out = nullptr,
-                     int keep_frames = 0, const GridPlan* gp = nullptr, bool seeded = false, float* zt_out = nullptr) {
-  // gp: s_hi / s_lo are rows of its table.  seeded: z_in holds the un-normalised [x | onehot] of given molecules; the first
-  // launch noises them to time index gp->t0 with raw draw 0 (the forward-noising prologue of gaudi_predict_noised) -> zt_out
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
-  HIPCHECK(h, hipSetDevice(h->device));
-  KParams P{};
-  // sampling calls may pack small molecules into one workgroup (stage_graph8); a value target's seed and trace are per
-  // molecule while a shared workgroup has ONE readout: those calls keep one molecule per workgroup
-  h->pack_now = chain_out == nullptr && h->vt == nullptr;
-  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, target_w ? h->HPP : 0);
-  h->pack_now = false;
-  if (rc) return rc;
-  fill_edm(h, P);
-  const int D = 3 + P.F, T = P.T;
-  if (s_hi >= (gp ? gp->rows : T) || s_lo < 0) return fail(h, GAUDI_E_INVALID, "step index out of range");
-  const size_t zb = sizeof(float) * B * N * D;
-  if (gp) {
-    HIPCHECK(h, h->d_gcoef.reserve(sizeof(float) * gp->coef.size()));
-    HIPCHECK(h, h->d_gidx.reserve(sizeof(int32_t) * gp->idx.size()));
-    HIPCHECK(h, hipMemcpyAsync(h->d_gcoef.p, gp->coef.data(), sizeof(float) * gp->coef.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipMemcpyAsync(h->d_gidx.p, gp->idx.data(), sizeof(int32_t) * gp->idx.size(), hipMemcpyHostToDevice, h->stream));
-    P.coef = h->d_gcoef.as<float>();
-    P.step_idx = h->d_gidx.as<int>();
-  }
-  std::vector<float> as_start;
-  if (seeded) {
-    const float g = h->gamma[gp->t0];  // as gaudi_predict_noised: alpha (en_diffusion.py:375-377), sigma (:370-373)
-    as_start.resize((size_t)B * 2);
-    for (int b = 0; b < B; ++b) {
-      as_start[2 * b] = sqrtf(sigmoid_host(-g));
-      as_start[2 * b + 1] = sqrtf(sigmoid_host(g));
-    }
-    HIPCHECK(h, h->d_as.reserve(sizeof(float) * 2 * B));
-    HIPCHECK(h, hipMemcpyAsync(h->d_as.p, as_start.data(), sizeof(float) * 2 * B, hipMemcpyHostToDevice, h->stream));
-    P.alpha_sigma = h->d_as.as<float>();
-    if (zt_out) {
-      HIPCHECK(h, h->d_zt.reserve(zb));
-      HIPCHECK(h, hipMemsetAsync(h->d_zt.p, 0, zb, h->stream));
-      P.zt_out = h->d_zt.as<float>();
-    }
-  }
-  HIPCHECK(h, h->d_zin.reserve(zb));
-  HIPCHECK(h, h->d_zout.reserve(zb));
-  HIPCHECK(h, h->d_x.reserve(sizeof(float) * B * N * 3));
-  HIPCHECK(h, h->d_h.reserve(sizeof(float) * B * N * P.F));
-  HIPCHECK(h, h->d_nan.reserve(sizeof(int)));
-  HIPCHECK(h, hipMemsetAsync(h->d_nan.p, 0, sizeof(int), h->stream));
-  if (P.rowmap != nullptr) {  // packed: masked nodes have no slot in any workgroup -- their rows stay zero
-    HIPCHECK(h, hipMemsetAsync(h->d_zin.p, 0, zb, h->stream));
-    HIPCHECK(h, hipMemsetAsync(h->d_zout.p, 0, zb, h->stream));
-    HIPCHECK(h, hipMemsetAsync(h->d_x.p, 0, sizeof(float) * B * N * 3, h->stream));
-    HIPCHECK(h, hipMemsetAsync(h->d_h.p, 0, sizeof(float) * B * N * P.F, h->stream));
-  }
-  if (z_in) HIPCHECK(h, hipMemcpyAsync(h->d_zin.p, z_in, zb, hipMemcpyHostToDevice, h->stream));
-  const bool fixn = h->fix_noise && do_init;  // whole-chain calls only (gaudi_step / gaudi_decode inject per-molecule draws)
-  const size_t nzb = fixn ? sizeof(float) * N * D : zb;  // bytes of one raw draw
-  if (noise) {
-    HIPCHECK(h, h->d_noise.reserve(nzb * (size_t)n_draws));
-    HIPCHECK(h, hipMemcpyAsync(h->d_noise.p, noise, nzb * (size_t)n_draws, hipMemcpyHostToDevice, h->stream));
-    P.noise = h->d_noise.as<float>();
-  }
-  P.draw_base = draw_base;
-  P.draw_stride = fixn ? (long long)N * D : (long long)B * N * D;
-  P.fix_noise = fixn ? 1 : 0;
-  P.fix_key = h->fix_key;
-  P.seed = seed;
-  P.sample_offset = sample_offset;
-  P.std0 = std0;
-  P.mode = MODE_SAMPLE;
-  P.x_out = h->d_x.as<float>();
-  P.h_out = h->d_h.as<float>();
-  P.nan_count = h->d_nan.as<int>();
-  P.guided = target_w != nullptr;
-  P.scale = scale;
-  if (chain_out) {
-    HIPCHECK(h, h->d_chain.reserve(zb * (size_t)keep_frames));
-    HIPCHECK(h, hipMemsetAsync(h->d_chain.p, 0, zb * (size_t)keep_frames, h->stream));
-    P.chain_out = h->d_chain.as<float>();
-    P.keep_frames = keep_frames;
-  }
-  int hpp = 0;
-  if (target_w) {
-    rc = fill_pred(h, P, target_w, B, N);
-    if (rc) return rc;
-    hpp = h->HPP;
-  }
-  std::vector<int32_t> vt_on;  // value target: which rows of the step table lie in the guidance window
-  const int vt_rows = gp ? gp->rows : T;
-  size_t vt_trace_bytes = 0;
-  if (h->vt && target_w) {
-    const gaudi_handle::VtCall& v = *h->vt;
-    if (P.rowmap != nullptr || P.NR != P.N || P.B != B) return fail(h, GAUDI_E_STATE, "a value-target launch must hold one molecule per workgroup");
-    const int K = v.K, RW = target_row_floats(K);
-    std::vector<float> par((size_t)B * RW);
-    for (int b = 0; b < B; ++b) vt_pack_row(*v.spec, K, v.b0 + b, &par[(size_t)b * RW]);
-    HIPCHECK(h, h->d_vtpar.reserve(sizeof(float) * par.size()));
-    HIPCHECK(h, hipMemcpyAsync(h->d_vtpar.p, par.data(), sizeof(float) * par.size(), hipMemcpyHostToDevice, h->stream));
-    VtDev vd{};
-    vd.par = h->d_vtpar.as<float>();
-    vd.B = B;
-    const int t_lo = v.spec->t_lo > 0 ? v.spec->t_lo : 1, t_hi = v.spec->t_hi > 0 ? v.spec->t_hi : T;
-    vt_on.resize(vt_rows);
-    for (int r = 0; r < vt_rows; ++r) {
-      const int t_from = gp ? (r == gp->rows - 1 ? gp->t0 : gp->idx[r + 1]) : r + 1;  // the step of row r starts at this time index
-      vt_on[r] = t_lo <= t_from && t_from <= t_hi;
-    }
-    if (v.trace) {
-      vt_trace_bytes = sizeof(float) * (size_t)(s_hi - s_lo + 1) * B * (K + 2);
-      HIPCHECK(h, h->d_vttrace.reserve(vt_trace_bytes));
-      HIPCHECK(h, hipMemsetAsync(h->d_vttrace.p, 0, vt_trace_bytes, h->stream));
-      vd.trace = h->d_vttrace.as<float>();
-      vd.top = s_hi;
-    }
-    HIPCHECK(h, h->d_vtdev.reserve(sizeof(VtDev)));
-    HIPCHECK(h, hipMemcpyAsync(h->d_vtdev.p, &vd, sizeof(VtDev), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipStreamSynchronize(h->stream));  // (par and vd are locals of this block)
-    P.vt = h->d_vtdev.as<VtDev>();
-  }
-  float* zin = h->d_zin.as<float>();
-  float* zout = h->d_zout.as<float>();
-  if (h->plan.two && target_w) {
-    // Large molecules (V4G kernels) and sin_embedding denoisers without a fused kernel, guided: every reverse step is two launches -- the EDM-only kernel runs the step up to
-    // z_s before guidance (split = 1: denoise, update with noise), the predictor-only kernel the guidance update, the
-    // projection and the NaN scrub (MODE_GUIDE) -- then one decode pass.
-    for (int s = s_hi; s >= s_lo; --s) {
-      P.mode = MODE_SAMPLE;
-      P.s_hi = P.s_lo = s;
-      P.do_init = (s == s_hi) && do_init;
-      P.do_decode = 0;
-      const bool off_window = !vt_on.empty() && !vt_on[s];  // zero gradient: the denoiser-only kernel finishes the step itself
-      P.split = off_window ? 0 : 1;
-      P.z_in = zin;
-      P.z_out = zout;
-      rc = launch(h, P, h->HPE, 0, 1);
-      if (rc) return rc;
-      P.alpha_sigma = nullptr;  // (a seeded start: the first launch has noised the given molecules)
-      P.zt_out = nullptr;
-      if (off_window) {
-        std::swap(zin, zout);
-        continue;
-      }
-      P.mode = MODE_GUIDE;
-      P.do_init = 0;
-      P.split = 0;
-      P.z_in = zout;
-      P.z_out = zin;
-      rc = launch(h, P, 0, hpp, 0);
-      if (rc) return rc;
-    }
-    if (do_decode) {
-      P.mode = MODE_SAMPLE;
-      P.split = 0;
-      P.s_hi = -1;
-      P.s_lo = 0;
-      P.do_init = (s_hi < s_lo) && do_init;
-      P.do_decode = 1;
-      P.z_in = zin;
-      P.z_out = zout;
-      rc = launch(h, P, h->HPE, 0, 0);
-      if (rc) return rc;
-      std::swap(zin, zout);
-    }
-  } else {
-  // chunk the chain into launches of steps_per_launch steps; z ping-pongs zout -> zin
-  bool first = true;
-  int s = s_hi;
-  const bool any_steps = s_hi >= s_lo;
-  do {
-    int lo = any_steps ? std::max(s_lo, s - h->steps_per_launch + 1) : s + 1;
-    if (!vt_on.empty() && any_steps) {
-      // a guidance window is launch-uniform: the launch ends where the next step falls on the other side of it, and a launch
-      // outside the window takes the guided step with a zero gradient (guided = 2: no predictor pass)
-      int cut = s;
-      while (cut > lo && vt_on[cut - 1] == vt_on[s]) --cut;
-      lo = cut;
-      P.guided = vt_on[s] ? 1 : 2;
-    }
-    P.s_hi = s;
-    P.s_lo = lo;
-    P.do_init = first && do_init;
-    P.do_decode = do_decode && lo <= s_lo;
-    P.z_in = zin;
-    P.z_out = zout;
-    rc = launch(h, P, h->HPE, hpp, any_steps ? (s - lo + 1) : 0);
-    if (rc) return rc;
-    P.alpha_sigma = nullptr;  // (a seeded start: the first launch has noised the given molecules)
-    P.zt_out = nullptr;
-    std::swap(zin, zout);
-    first = false;
-    s = lo - 1;
-  } while (any_steps && s >= s_lo);
-  }
-  // after the swap, `zin` holds the latest z
-  if (z_out) HIPCHECK(h, hipMemcpyAsync(z_out, zin, zb, hipMemcpyDeviceToHost, h->stream));
-  if (seeded && zt_out) HIPCHECK(h, hipMemcpyAsync(zt_out, h->d_zt.p, zb, hipMemcpyDeviceToHost, h->stream));
-  if (do_decode) {
-    HIPCHECK(h, hipMemcpyAsync(x_out, h->d_x.p, sizeof(float) * B * N * 3, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(h, hipMemcpyAsync(onehot_out, h->d_h.p, sizeof(float) * B * N * P.F, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (chain_out)
-    HIPCHECK(h, hipMemcpyAsync(chain_out, h->d_chain.p, zb * (size_t)keep_frames, hipMemcpyDeviceToHost, h->stream));
-  std::vector<float> vt_tr;
-  if (vt_trace_bytes) {
-    vt_tr.resize(vt_trace_bytes / sizeof(float));
-    HIPCHECK(h, hipMemcpyAsync(vt_tr.data(), h->d_vttrace.p, vt_trace_bytes, hipMemcpyDeviceToHost, h->stream));
-  }
-  int nanc = 0;
-  HIPCHECK(h, hipMemcpyAsync(&nanc, h->d_nan.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(h, hipStreamSynchronize(h->stream));
-  if (vt_trace_bytes) {  // this call's molecules are rows b0 .. b0 + B of the request's [steps][Btot][K + 2]
-    const gaudi_handle::VtCall& v = *h->vt;
-    const size_t row = (size_t)v.K + 2;
-    for (int st = 0; st <= s_hi - s_lo; ++st)
-      std::memcpy(v.trace + ((size_t)st * v.Btot + v.b0) * row, &vt_tr[(size_t)st * B * row], sizeof(float) * B * row);
-  }
-  if (nan_count) *nan_count = nanc;
-  return GAUDI_OK;
-}
-
-int gaudi_step(gaudi_handle* h, int B, int N, int s_idx, const float* z_t, const float* node_mask,
-               const float* edge_mask, const float* eps_raw, const float* target_w, float scale, float* zs_out) {
-  if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  const int T = h->ecfg.diffusion_steps;
-  return run_chain(h, B, N, node_mask, edge_mask, z_t, false, s_idx, s_idx, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f,
-                   target_w, scale, zs_out, nullptr, nullptr, nullptr);
-}
-
-int gaudi_step_pair(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
-                    const float* edge_mask, const float* eps_raw, const float* target_w, float scale, float* zs_out) {
-  if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  const int T = h->ecfg.diffusion_steps;
-  if (s_idx < 0 || t_idx <= s_idx || t_idx > T) return fail(h, GAUDI_E_INVALID, "a step needs 0 <= s_idx < t_idx <= T");
-  GridPlan gp;  // the one-row table of this pair; eps_raw stands for raw draw T - s_idx, the draw of the step that lands on s_idx
-  gp.rows = 1;
-  gp.t0 = t_idx;
-  gp.coef.resize(4);
-  coef_row(h->gamma, T, s_idx, t_idx, gp.coef.data());
-  gp.idx.assign(1, s_idx);
-  return run_chain(h, B, N, node_mask, edge_mask, z_t, false, 0, 0, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f, target_w, scale,
-                   zs_out, nullptr, nullptr, nullptr, nullptr, 0, &gp);
-}
-
-int gaudi_decode(gaudi_handle* h, int B, int N, const float* z0, const float* node_mask, const float* edge_mask,
-                 const float* eps_raw, float* x_out, float* onehot_out) {
-  if (!h || !z0 || !node_mask || !edge_mask || !eps_raw || !x_out || !onehot_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  const int T = h->ecfg.diffusion_steps;
-  return run_chain(h, B, N, node_mask, edge_mask, z0, false, -1, 0, true, eps_raw, T + 1, 1, 0, 0, 1.0f, nullptr, 0.f,
-                   nullptr, x_out, onehot_out, nullptr);
-}
-
-// Largest sub-batch one chain may run at once.  The guided path keeps an activation stash of 2.9 MB per molecule (default
-// sizes) for the whole call; very large requests are cut into sub-batches of whole multiples of 256 molecules (one per
-// CU) that fit `budget` bytes.  Noise is keyed by the global sample index, so the result does not depend on the cut.
-static int max_sub_batch(gaudi_handle* h, int B, int N, bool guided) {
-  if (!guided) return B;
-  const long long per_mol = 4LL * pred_stash_floats(N, h->HPP, h->pcfg.n_layers, dense_ew4(N));
-  long long budget = 0;
-  if (const char* e = getenv("GAUDI_MAX_WORKSPACE_MB")) budget = atoll(e) * (1LL << 20);
-  const bool forced = budget > 0;
-  if (!forced) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return B;
-    budget = (long long)((free_b + h->d_stash.cap) * 0.8);
-  }
-  long long bmax = std::max(1LL, budget / std::max(1LL, per_mol));
-  if (bmax >= 256) bmax = bmax / 256 * 256;
-  else if (!forced) bmax = std::min<long long>(B, 256);  // let the allocation itself report a too-small device
-  return (int)std::min<long long>(B, bmax);
-}
-
-// Node slots of the widest packed group the RESIDENT split kernels take at these widths (one round of eight edge tiles), below N;
-// 0: none (no split images, no such kernel).  A function of the widths only.
-static int resident_node_limit(gaudi_handle* h, int N, bool guided) {
-  const int hpe = h->HPE, hpp = guided ? h->HPP : 0;
-  if (h->variant != 8 || !h->split || !h->edm_ws_bytes || (hpp && !h->pred_ws_bytes)) return 0;
-  if (GAUDI_NODE_F16 && (!(h->edm_hinv > 0.f) || (hpp && !(h->pred_hinv > 0.f)))) return 0;
-  const int Dz = 3 + h->ecfg.in_node_nf;
-  for (int ng = std::min(N - 1, 32); ng >= 8; --ng)
-    for (int mode = 1; mode <= 2; ++mode) {
-      int pubx = 0, pub_ch = 0;
-      if (have_kernel8(hpe, hpp, mode, false) && plan_pub8(hpe, hpp, ng, Dz, 16 * w8::kWaves, mode, pubx, pub_ch)) return ng;
-    }
-  return 0;
-}
-
-// The arguments a time grid adds to a chain, checked (gaudi_sample_grid and its callback forms).  A seeded start refuses
-// fix_noise: that option shares the PRIOR draw between molecules, and given molecules have no prior draw.
-static int grid_args(gaudi_handle* h, int n_grid, const int32_t* grid, const float* x0, const float* onehot0, GridPlan& gp) {
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  const int T = h->ecfg.diffusion_steps;
-  if (const char* why = grid_check(T, n_grid, grid)) return fail(h, GAUDI_E_INVALID, why);
-  if ((x0 != nullptr) != (onehot0 != nullptr)) return fail(h, GAUDI_E_INVALID, "a start from given molecules needs both x0 and onehot0");
-  if (!x0 && grid[0] != T) return fail(h, GAUDI_E_INVALID, "a chain from the prior must start at time index T (grid[0] == T)");
-  if (x0 && h->fix_noise) return fail(h, GAUDI_E_INVALID, "fix_noise applies to chains from the prior, not to a start from given molecules");
-  make_grid_plan(h->gamma, T, n_grid, grid, gp);
-  return GAUDI_OK;
-}
-// [x | onehot] rows of the given molecules, as the forward-noising prologue reads them
-static std::vector<float> concat_xh(int B, int N, int F, const float* x, const float* onehot) {
-  const int D = 3 + F;
-  std::vector<float> xh((size_t)B * N * D);
-  for (size_t r = 0; r < (size_t)B * N; ++r) {
-    for (int d = 0; d < 3; ++d) xh[r * D + d] = x[r * 3 + d];
-    for (int k = 0; k < F; ++k) xh[r * D + 3 + k] = onehot[r * F + k];
-  }
-  return xh;
-}
-
-static int sample_impl(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                       int64_t sample_offset, const float* noise, float std, const float* target_w, float scale,
-                       float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag, const GridPlan* gp, const float* xh0,
-                       float* zt_out) {
-  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  if (target_w && !h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
-  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
-  HIPCHECK(h, hipSetDevice(h->device));
-  const int T = h->ecfg.diffusion_steps, F = h->ecfg.in_node_nf, D = 3 + F;
-  const int s_top = gp ? gp->rows - 1 : T - 1;  // first row of the step table the chain walks down from
-  struct CallHint {
-    gaudi_handle* h;
-    ~CallHint() {
-      h->call_min_slots = h->call_force_waves = h->call_narrow = 0;
-      h->call_cut = false;
-      h->call_molmap = nullptr;
-    }
-  } call_hint{h};
-  h->last_split_resident = 0;
-  // ---- per-molecule kernel family (round 6).  A request whose padded N is beyond the resident kernels' LDS limit used to run
-  // EVERY molecule on the V8G kernels (node buffers in a global scratch: 20 % slower on a molecule that would fit).
-  // Now the molecules that fit the resident kernels on their own -- at most `lim` live nodes and one round of eight edge tiles: a
-  // function of the molecule's own graph and the widths, so a molecule's kernel (and its rounding) does not depend on which
-  // other molecules share the call or the shard -- form a first bucket that runs packed on the resident kernels; the rest
-  // run on V8G as before.  Noise is keyed by the molecule's index in the request either way.
-  std::vector<int32_t> small, large;
-  int lim = 0;
-  if (h->variant == 8 && h->family_split && h->pack && h->gn8 && h->gn8_pack && !h->force_gn && !h->force_gn8 && !h->fix_noise &&
-      !h->plan_force_waves && (int64_t)B * N < (1 << 28) && !h->vt) {  // (the first bucket runs PACKED: not for a value target)
-    Meta8 M;
-    std::string err;
-    const int hpp = target_w ? h->HPP : 0;
-    if (build_meta8(B, N, node_mask, edge_mask, M, err, h->plan_min_slots) == GAUDI_OK) {
-      int pubx = 0, pub_ch = 0;
-      bool fits = false;  // the unpacked resident plan of the whole call, any split mode
-      for (int mode = 1; mode <= 2 && !fits; ++mode)
-        fits = have_kernel8(h->HPE, hpp, mode, hpp && M.S > 16 * w8::kWaves) && plan_pub8(h->HPE, hpp, N, D, M.S, mode, pubx, pub_ch);
-      if (!fits && (lim = resident_node_limit(h, N, target_w != nullptr)) > 0) {
-        const std::vector<std::vector<int>> used = used_nodes(B, N, node_mask, edge_mask);
-        for (int b = 0; b < B; ++b) ((int)used[b].size() <= lim && M.ntiles[b] <= w8::kWaves ? small : large).push_back(b);
-      }
-    }
-  }
-  struct Bucket {
-    const std::vector<int32_t>* idx;  // nullptr: the whole request in place
-    int narrow;
-  };
-  std::vector<Bucket> buckets;
-  if (small.empty()) buckets.push_back({nullptr, 0});
-  else {
-    buckets.push_back({&small, lim});
-    if (!large.empty()) buckets.push_back({&large, 0});
-    h->last_split_resident = (int)small.size();
-  }
-  int nanc = 0;
-  std::vector<float> nz, gm, ge, gx, gh, gz, gs, gt;
-  for (const Bucket& bk : buckets) {
-    const int Bb = bk.idx ? (int)bk.idx->size() : B;
-    const float *nmb = node_mask, *emb = edge_mask, *nsb = noise;
-    float *xo = x_out, *ho = onehot_out, *zo = z0_out, *zto = xh0 ? zt_out : nullptr;
-    const float* xhb = xh0;
-    if (bk.idx) {  // gather the bucket's molecules
-      gm.resize((size_t)Bb * N);
-      ge.resize((size_t)Bb * N * N);
-      gx.assign((size_t)Bb * N * 3, 0.f);
-      gh.assign((size_t)Bb * N * F, 0.f);
-      for (int k = 0; k < Bb; ++k) {
-        const int b = (*bk.idx)[k];
-        std::memcpy(&gm[(size_t)k * N], node_mask + (size_t)b * N, sizeof(float) * N);
-        std::memcpy(&ge[(size_t)k * N * N], edge_mask + (size_t)b * N * N, sizeof(float) * N * N);
-      }
-      nmb = gm.data();
-      emb = ge.data();
-      xo = gx.data();
-      ho = gh.data();
-      if (z0_out) {
-        gz.assign((size_t)Bb * N * D, 0.f);
-        zo = gz.data();
-      }
-      if (xh0) {
-        gs.resize((size_t)Bb * N * D);
-        for (int k = 0; k < Bb; ++k)
-          std::memcpy(&gs[(size_t)k * N * D], xh0 + (size_t)(*bk.idx)[k] * N * D, sizeof(float) * (size_t)N * D);
-        xhb = gs.data();
-        if (zto) {
-          gt.assign((size_t)Bb * N * D, 0.f);
-          zto = gt.data();
-        }
-      }
-    }
-    h->call_narrow = bk.narrow;
-    h->call_min_slots = h->call_force_waves = 0;
-    const int bmax = max_sub_batch(h, Bb, N, target_w != nullptr);
-    // sub-batches plan with the whole batch's graph figures (same kernel family and edge-GEMM arithmetic for every cut)
-    h->call_cut = bmax < Bb;
-    if (bmax < Bb && h->variant == 8 && !bk.narrow) {
-      Meta8 M;
-      std::string err;
-      const int rc = build_meta8(Bb, N, nmb, emb, M, err);
-      if (rc == GAUDI_E_CAPACITY) h->call_force_waves = 4;
-      else if (rc) return fail(h, rc, err);
-      else h->call_min_slots = M.S;
-    }
-    for (int b0 = 0; b0 < Bb; b0 += bmax) {
-      const int nb = std::min(bmax, Bb - b0);
-      const float* nzp = nsb;
-      if (noise && !h->fix_noise && (nb != B || bk.idx)) {  // gather this sub-batch's draws out of [T+2][B][N][D]
-        nz.resize((size_t)(T + 2) * nb * N * D);
-        for (int d = 0; d < T + 2; ++d)
-          for (int k = 0; k < nb; ++k) {
-            const int b = bk.idx ? (*bk.idx)[b0 + k] : b0 + k;
-            std::memcpy(&nz[((size_t)d * nb + k) * N * D], noise + ((size_t)d * B + b) * N * D, sizeof(float) * (size_t)N * D);
-          }
-        nzp = nz.data();
-      }
-      h->call_molmap = bk.idx ? bk.idx->data() + b0 : nullptr;
-      if (h->vt) h->vt->b0 = b0;
-      int nan_sub = 0;
-      int rc = run_chain(h, nb, N, nmb + (size_t)b0 * N, emb + (size_t)b0 * N * N, xhb ? xhb + (size_t)b0 * N * D : nullptr, xhb == nullptr,
-                         s_top, 0, true, nzp, 0, T + 2, seed,
-                         bk.idx ? sample_offset : sample_offset + b0, std, target_w, scale, zo ? zo + (size_t)b0 * N * D : nullptr,
-                         xo + (size_t)b0 * N * 3, ho + (size_t)b0 * N * F, &nan_sub, nullptr, 0, gp, xhb != nullptr,
-                         zto ? zto + (size_t)b0 * N * D : nullptr);
-      h->call_molmap = nullptr;
-      if (rc) return rc;
-      nanc += nan_sub;
-    }
-    if (bk.idx)  // scatter the bucket's results
-      for (int k = 0; k < Bb; ++k) {
-        const int b = (*bk.idx)[k];
-        std::memcpy(x_out + (size_t)b * N * 3, &gx[(size_t)k * N * 3], sizeof(float) * N * 3);
-        std::memcpy(onehot_out + (size_t)b * N * F, &gh[(size_t)k * N * F], sizeof(float) * N * F);
-        if (z0_out) std::memcpy(z0_out + (size_t)b * N * D, &gz[(size_t)k * N * D], sizeof(float) * N * D);
-        if (zto) std::memcpy(zt_out + (size_t)b * N * D, &gt[(size_t)k * N * D], sizeof(float) * N * D);
-      }
-  }
-  finish_sample(B, N, node_mask, x_out, nanc, diag);
-  return GAUDI_OK;
-}
-
-int gaudi_sample(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                 int64_t sample_offset, const float* noise, float std, const float* target_w, float scale,
-                 float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
-  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_w, scale, x_out, onehot_out, z0_out,
-                     diag, nullptr, nullptr, nullptr);
-}
-
-int gaudi_sample_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                      int64_t sample_offset, const float* noise, float std, const float* target_w, float scale, int n_grid,
-                      const int32_t* grid, const float* x0, const float* onehot0, float* x_out, float* onehot_out, float* z0_out,
-                      float* zt_out, gaudi_diag* diag) {
-  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
-  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
-  GridPlan gp;
-  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
-  std::vector<float> xh0;
-  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
-  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_w, scale, x_out, onehot_out, z0_out,
-                     diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
-}
-
-int gaudi_host_target_seed(const gaudi_target_spec* spec, int B, int K, const float* pred, float* out) {
-  if (!spec || !pred || !out || vt_check(spec, B, K, 0)) return GAUDI_E_INVALID;
-  std::vector<float> row(target_row_floats(K));
-  for (int b = 0; b < B; ++b) {
-    vt_pack_row(*spec, K, b, row.data());
-    for (int k = 0; k < K; ++k) out[(size_t)b * K + k] = target_seed(row.data(), K, k, pred[(size_t)b * K + k]);
-  }
-  return GAUDI_OK;
-}
-
-// clears the handle's value-target call when the entry point returns, whichever way
-struct VtScope {
-  gaudi_handle* h;
-  gaudi_handle::VtCall call;
-  VtScope(gaudi_handle* h_, const gaudi_target_spec* sp, int K, int B, float* trace) : h(h_) {
-    call.spec = sp;
-    call.K = K;
-    call.Btot = B;
-    call.trace = trace;
-    h->vt = &call;
-  }
-  ~VtScope() { h->vt = nullptr; }
-};
-
-int gaudi_sample_target(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                        int64_t sample_offset, const float* noise, float std, const gaudi_target_spec* spec, int n_grid,
-                        const int32_t* grid, const float* x0, const float* onehot0, float* x_out, float* onehot_out,
-                        float* z0_out, float* zt_out, float* trace_out, gaudi_diag* diag) {
-  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
-  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
-  const int T = h->ecfg.diffusion_steps, K = h->pcfg.out_nf;
-  if (const char* why = vt_check(spec, B, K, T)) return fail(h, GAUDI_E_INVALID, why);
-  std::vector<int32_t> unit;
-  if (!grid) {  // the unit grid T, T - 1, ..., 0: gaudi_sample's chain
-    unit.resize(T + 1);
-    for (int k = 0; k <= T; ++k) unit[k] = T - k;
-    grid = unit.data();
-    n_grid = T + 1;
-  }
-  GridPlan gp;
-  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
-  std::vector<float> xh0;
-  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
-  if (trace_out) std::memset(trace_out, 0, sizeof(float) * (size_t)gp.rows * B * (K + 2));
-  VtScope scope(h, spec, K, B, trace_out);
-  std::vector<float> zero_w(16, 0.f);  // (target_w != NULL marks the chain as guided; the kernels read the parameter rows instead)
-  return sample_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, zero_w.data(), 1.0f, x_out, onehot_out, z0_out,
-                     diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
-}
-
-int gaudi_step_target(gaudi_handle* h, int B, int N, int s_idx, int t_idx, const float* z_t, const float* node_mask,
-                      const float* edge_mask, const float* eps_raw, const gaudi_target_spec* spec, float* zs_out,
-                      float* trace_out) {
-  if (!h || !z_t || !node_mask || !edge_mask || !eps_raw || !zs_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
-  const int T = h->ecfg.diffusion_steps, K = h->pcfg.out_nf;
-  if (s_idx < 0 || t_idx <= s_idx || t_idx > T) return fail(h, GAUDI_E_INVALID, "a step needs 0 <= s_idx < t_idx <= T");
-  if (const char* why = vt_check(spec, B, K, T)) return fail(h, GAUDI_E_INVALID, why);
-  GridPlan gp;
-  gp.rows = 1;
-  gp.t0 = t_idx;
-  gp.coef.resize(4);
-  coef_row(h->gamma, T, s_idx, t_idx, gp.coef.data());
-  gp.idx.assign(1, s_idx);
-  if (trace_out) std::memset(trace_out, 0, sizeof(float) * (size_t)B * (K + 2));
-  VtScope scope(h, spec, K, B, trace_out);
-  std::vector<float> zero_w(16, 0.f);
-  return run_chain(h, B, N, node_mask, edge_mask, z_t, false, 0, 0, false, eps_raw, T - s_idx, 1, 0, 0, 1.0f, zero_w.data(), 1.0f,
-                   zs_out, nullptr, nullptr, nullptr, nullptr, 0, &gp);
-}
-
-}  // extern "C"
-
-// gaudi_sample_cb / gaudi_sample_cbz: exactly one of the two callbacks is set
-static int sample_cb_impl(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                          int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad,
-                          gaudi_target_cbz target_grad_z, void* user, float scale, float* x_out, float* onehot_out, float* z0_out,
-                          gaudi_diag* diag, const GridPlan* gp = nullptr, const float* xh0 = nullptr, float* zt_out = nullptr) {
-  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out || (!target_grad && !target_grad_z)) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  if (!h->has_pred) return fail(h, GAUDI_E_STATE, "guided sampling needs predictor weights");
-#ifdef GAUDI_STAMPS
-  // the stamped diagnostic build times the fused step only: its 8-wave guide phase drops the direct dT/dz term (sampler_kernel.h)
-  if (target_grad_z) return fail(h, GAUDI_E_INVALID, "gaudi_sample_cbz is not available in the GAUDI_STAMPS diagnostic build");
-#endif
-  HIPCHECK(h, hipSetDevice(h->device));
-  KParams P{};
-  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, h->HPP);
-  if (rc) return rc;
-  fill_edm(h, P);
-  const int D = 3 + P.F, T = P.T, K = h->pcfg.out_nf;
-  const size_t zb = sizeof(float) * B * N * D, pb = sizeof(float) * B * K;
-  HIPCHECK(h, h->d_zin.reserve(zb));
-  HIPCHECK(h, h->d_zout.reserve(zb));
-  HIPCHECK(h, h->d_x.reserve(sizeof(float) * B * N * 3));
-  HIPCHECK(h, h->d_h.reserve(sizeof(float) * B * N * P.F));
-  HIPCHECK(h, h->d_nan.reserve(sizeof(int)));
-  HIPCHECK(h, h->d_pred.reserve(pb));
-  HIPCHECK(h, h->d_dpred.reserve(pb));
-  HIPCHECK(h, h->p_pred.reserve(pb));
-  HIPCHECK(h, h->p_dpred.reserve(pb));
-  if (target_grad_z) {  // the target also depends on z directly: z_s goes to the host, scale * mask * dT/dz comes back
-    HIPCHECK(h, h->d_dz.reserve(zb));
-    HIPCHECK(h, h->p_z.reserve(zb));
-    HIPCHECK(h, h->p_dz.reserve(zb));
-  }
-  if (!h->cb_event) HIPCHECK(h, hipEventCreateWithFlags(&h->cb_event, hipEventDisableTiming));
-  HIPCHECK(h, hipMemsetAsync(h->d_nan.p, 0, sizeof(int), h->stream));
-  const size_t nzb = h->fix_noise ? sizeof(float) * N * D : zb;
-  if (noise) {
-    HIPCHECK(h, h->d_noise.reserve(nzb * (size_t)(T + 2)));
-    HIPCHECK(h, hipMemcpyAsync(h->d_noise.p, noise, nzb * (size_t)(T + 2), hipMemcpyHostToDevice, h->stream));
-    P.noise = h->d_noise.as<float>();
-  }
-  P.draw_base = 0;
-  P.draw_stride = h->fix_noise ? (long long)N * D : (long long)B * N * D;
-  P.fix_noise = h->fix_noise ? 1 : 0;
-  P.fix_key = h->fix_key;
-  P.seed = seed;
-  P.sample_offset = sample_offset;
-  P.std0 = std;
-  P.mode = MODE_SAMPLE;
-  P.x_out = h->d_x.as<float>();
-  P.h_out = h->d_h.as<float>();
-  P.nan_count = h->d_nan.as<int>();
-  P.guided = 1;
-  const int s_top = gp ? gp->rows - 1 : T - 1;  // rows of the step table (a time grid: its own table, as in run_chain)
-  const float* coef_h = gp ? gp->coef.data() : h->coef.data();
-  if (gp) {
-    HIPCHECK(h, h->d_gcoef.reserve(sizeof(float) * gp->coef.size()));
-    HIPCHECK(h, h->d_gidx.reserve(sizeof(int32_t) * gp->idx.size()));
-    HIPCHECK(h, hipMemcpyAsync(h->d_gcoef.p, gp->coef.data(), sizeof(float) * gp->coef.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipMemcpyAsync(h->d_gidx.p, gp->idx.data(), sizeof(int32_t) * gp->idx.size(), hipMemcpyHostToDevice, h->stream));
-    P.coef = h->d_gcoef.as<float>();
-    P.step_idx = h->d_gidx.as<int>();
-  }
-  std::vector<float> as_start;
-  if (xh0) {  // given molecules: the first launch noises them to time index gp->t0 with raw draw 0
-    const float g = h->gamma[gp->t0];
-    as_start.resize((size_t)B * 2);
-    for (int b = 0; b < B; ++b) {
-      as_start[2 * b] = sqrtf(sigmoid_host(-g));
-      as_start[2 * b + 1] = sqrtf(sigmoid_host(g));
-    }
-    HIPCHECK(h, h->d_as.reserve(sizeof(float) * 2 * B));
-    HIPCHECK(h, hipMemcpyAsync(h->d_as.p, as_start.data(), sizeof(float) * 2 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipMemcpyAsync(h->d_zin.p, xh0, zb, hipMemcpyHostToDevice, h->stream));
-    P.alpha_sigma = h->d_as.as<float>();
-    if (zt_out) {
-      HIPCHECK(h, h->d_zt.reserve(zb));
-      P.zt_out = h->d_zt.as<float>();
-    }
-  }
-  P.scale = scale;
-  std::vector<float> zero_w(16, 0.f);
-  rc = fill_pred(h, P, zero_w.data(), B, N);
-  if (rc) return rc;
-  P.pred_out = h->d_pred.as<float>();
-  P.dpred_in = h->d_dpred.as<float>();
-  float* pred = h->p_pred.as<float>();
-  float* dT = h->p_dpred.as<float>();
-  float* zin = h->d_zin.as<float>();
-  float* zout = h->d_zout.as<float>();
-  // Large molecules (V4G kernels: node buffers in global memory) have no fused EDM + predictor instantiation (DESIGN.md
-  // 7.12): phase A is the EDM-only kernel (split = 1: z_t -> z_s before guidance) followed by the predictor-only kernel's
-  // forward half (MODE_GUIDE, split = 1), phase B the predictor-only kernel's second half (MODE_GUIDE, split = 2).
-  const bool gn = h->plan.two;
-  // GAUDI_DEBUG_CB: where a callback step's host time goes (enqueue / wait for pred / the caller's function)
-  const bool dbg_cb = getenv("GAUDI_DEBUG_CB") != nullptr;
-  double t_enq = 0, t_wait = 0, t_user = 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  for (int s = s_top; s >= 0; --s) {
-    const double t0 = dbg_cb ? now() : 0;
-    const float t_step = gp ? coef_h[4 * s + 3] : (float)(s + 1) / (float)T;  // (the same float either way: coef_row)
-    // phase A: z_t -> z_s (before guidance) and pred = predictor(z_s, t); the activation stash stays on the device
-    P.mode = MODE_SAMPLE;
-    P.s_hi = P.s_lo = s;
-    P.do_init = s == s_top && !xh0;
-    P.do_decode = 0;
-    P.split = 1;
-    P.z_in = zin;
-    P.z_out = zout;
-    rc = launch(h, P, h->HPE, gn ? 0 : h->HPP, 1);
-    if (rc) return rc;
-    P.alpha_sigma = nullptr;
-    P.zt_out = nullptr;
-    if (gn) {
-      P.mode = MODE_GUIDE;
-      P.do_init = 0;
-      P.z_in = zout;
-      P.z_out = zin;
-      rc = launch(h, P, 0, h->HPP, 0);
-      if (rc) return rc;
-    }
-    HIPCHECK(h, hipMemcpyAsync(pred, h->d_pred.p, pb, hipMemcpyDeviceToHost, h->stream));
-    if (target_grad_z) HIPCHECK(h, hipMemcpyAsync(h->p_z.p, zout, zb, hipMemcpyDeviceToHost, h->stream));  // z_s before guidance
-    HIPCHECK(h, hipEventRecord(h->cb_event, h->stream));
-    const double t1 = dbg_cb ? now() : 0;
-    HIPCHECK(h, hipEventSynchronize(h->cb_event));
-    const double t2 = dbg_cb ? now() : 0;
-    std::memset(dT, 0, pb);
-    if (target_grad_z) {
-      float* dz = h->p_dz.as<float>();
-      std::memset(dz, 0, zb);
-      target_grad_z(user, B, N, D, K, h->p_z.as<float>(), pred, t_step, dT, dz);
-      // energy = scale * sum_b T (en_diffusion.py:899-903); the reference asserts that the x part of the gradient is zero on
-      // masked nodes (remove_mean_with_mask, utils.py:33-44): the direct term is masked here
-      for (int b = 0; b < B; ++b)
-        for (int n = 0; n < N; ++n) {
-          const float m = scale * node_mask[(size_t)b * N + n];
-          for (int d = 0; d < D; ++d) dz[((size_t)b * N + n) * D + d] *= m;
-        }
-      HIPCHECK(h, hipMemcpyAsync(h->d_dz.p, dz, zb, hipMemcpyHostToDevice, h->stream));
-      P.dz_in = h->d_dz.as<float>();
-    } else {
-      target_grad(user, B, K, pred, t_step, dT);
-    }
-    const double t3 = dbg_cb ? now() : 0;
-    HIPCHECK(h, hipMemcpyAsync(h->d_dpred.p, dT, pb, hipMemcpyHostToDevice, h->stream));
-    // phase B: reverse pass with the caller's dT/dpred, clip / project / apply, CoG removal
-    P.mode = gn ? MODE_GUIDE : MODE_SAMPLE;
-    P.do_init = 0;
-    P.split = 2;
-    P.z_in = zout;
-    P.z_out = zin;
-    rc = launch(h, P, gn ? 0 : h->HPE, h->HPP, 0);
-    if (rc) return rc;
-    if (dbg_cb) {
-      t_enq += (t1 - t0) + (now() - t3);
-      t_wait += t2 - t1;
-      t_user += t3 - t2;
-    }
-  }
-  if (dbg_cb)
-    fprintf(stderr, "[callback] per step: enqueue %.1f us, wait for pred %.1f us, caller's function %.1f us (%d steps)\n",
-            1e6 * t_enq / (s_top + 1), 1e6 * t_wait / (s_top + 1), 1e6 * t_user / (s_top + 1), s_top + 1);
-  // decode pass
-  P.mode = MODE_SAMPLE;
-  P.split = 0;
-  P.s_hi = -1;
-  P.s_lo = 0;
-  P.do_init = 0;
-  P.do_decode = 1;
-  P.z_in = zin;
-  P.z_out = zout;
-  rc = launch(h, P, h->HPE, gn ? 0 : h->HPP, 0);
-  if (rc) return rc;
-  if (z0_out) HIPCHECK(h, hipMemcpyAsync(z0_out, zout, zb, hipMemcpyDeviceToHost, h->stream));
-  if (xh0 && zt_out) HIPCHECK(h, hipMemcpyAsync(zt_out, h->d_zt.p, zb, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(h, hipMemcpyAsync(x_out, h->d_x.p, sizeof(float) * B * N * 3, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(h, hipMemcpyAsync(onehot_out, h->d_h.p, sizeof(float) * B * N * P.F, hipMemcpyDeviceToHost, h->stream));
-  int nanc = 0;
-  HIPCHECK(h, hipMemcpyAsync(&nanc, h->d_nan.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(h, hipStreamSynchronize(h->stream));
-  finish_sample(B, N, node_mask, x_out, nanc, diag);
-  return GAUDI_OK;
-}
-
-extern "C" {
-
-int gaudi_sample_cb(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                    int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad, void* user,
-                    float scale, float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
-  if (!target_grad) return GAUDI_E_INVALID;
-  return sample_cb_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_grad, nullptr, user, scale, x_out,
-                        onehot_out, z0_out, diag);
-}
-
-int gaudi_sample_cbz(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                     int64_t sample_offset, const float* noise, float std, gaudi_target_cbz target_grad, void* user,
-                     float scale, float* x_out, float* onehot_out, float* z0_out, gaudi_diag* diag) {
-  if (!target_grad) return GAUDI_E_INVALID;
-  return sample_cb_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, nullptr, target_grad, user, scale, x_out,
-                        onehot_out, z0_out, diag);
-}
-
-int gaudi_sample_cb_grid(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                         int64_t sample_offset, const float* noise, float std, gaudi_target_cb target_grad,
-                         gaudi_target_cbz target_grad_z, void* user, float scale, int n_grid, const int32_t* grid, const float* x0,
-                         const float* onehot0, float* x_out, float* onehot_out, float* z0_out, float* zt_out, gaudi_diag* diag) {
-  if (!h || !node_mask || !edge_mask || !x_out || !onehot_out) return GAUDI_E_INVALID;
-  if ((target_grad != nullptr) == (target_grad_z != nullptr)) return fail(h, GAUDI_E_INVALID, "exactly one of the two callbacks must be set");
-  if (B <= 0 || N <= 0) return fail(h, GAUDI_E_INVALID, "B and N must be positive");
-  GridPlan gp;
-  if (int rc = grid_args(h, n_grid, grid, x0, onehot0, gp)) return rc;
-  std::vector<float> xh0;
-  if (x0) xh0 = concat_xh(B, N, h->ecfg.in_node_nf, x0, onehot0);
-  return sample_cb_impl(h, B, N, node_mask, edge_mask, seed, sample_offset, noise, std, target_grad, target_grad_z, user, scale, x_out,
-                        onehot_out, z0_out, diag, &gp, x0 ? xh0.data() : nullptr, zt_out);
-}
-
-int gaudi_sample_chain(gaudi_handle* h, int B, int N, const float* node_mask, const float* edge_mask, uint64_t seed,
-                       int64_t sample_offset, const float* noise, float std, int keep_frames, float* chain_out) {
-  if (!h || !node_mask || !edge_mask || !chain_out) return GAUDI_E_INVALID;
-  if (!h->has_edm) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
-  if (h->edm_stale) return fail(h, GAUDI_E_STATE, kEdmStale);
-  const int T = h->ecfg.diffusion_steps, F = h->ecfg.in_node_nf, D = 3 + F;
-  if (keep_frames < 1 || keep_frames > T) return fail(h, GAUDI_E_INVALID, "keep_frames must be in 1..T");
-  std::vector<float> x((size_t)B * N * 3), oh((size_t)B * N * F);
-  int rc = run_chain(h, B, N, node_mask, edge_mask, nullptr, true, T - 1, 0, true, noise, 0, T + 2, seed, sample_offset,
-                     std, nullptr, 0.f, nullptr, x.data(), oh.data(), nullptr, chain_out, keep_frames);
-  if (rc) return rc;
-  // chain[0] = cat[x, h_categorical] (en_diffusion.py:1168-1169)
-  for (int b = 0; b < B; ++b)
-    for (int n = 0; n < N; ++n) {
-      float* dst = chain_out + ((size_t)b * N + n) * D;
-      for (int d = 0; d < 3; ++d) dst[d] = x[((size_t)b * N + n) * 3 + d];
-      for (int k = 0; k < F; ++k) dst[3 + k] = oh[((size_t)b * N + n) * F + k];
-    }
   return GAUDI_OK;
 }
 
@@ -3021,6 +2142,7 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 }  // extern "C"
 
 #include "pred_host.inc"
+#include "chain_host.inc"
 #include "pred_train_host.inc"
 #include "stability.inc"
 #include "atoms.inc"

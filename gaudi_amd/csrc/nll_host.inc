@@ -72,8 +72,8 @@ static int run_edm_nll(gaudi_handle* h, int B, int N, const float* x, const floa
     }
   }
   KParams P{};
-  h->pack_now = false;  // one EDM pass takes one t per workgroup: molecules with different t cannot share one
-  rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, 0);
+  // (the default hints do not pack: one EDM pass takes one t per workgroup, molecules with different t cannot share one)
+  rc = stage_graph(h, B, N, node_mask, edge_mask, P, h->HPE, 0, CallHints{});
   if (rc) return rc;
   fill_edm(h, P);
   const size_t zb = sizeof(float) * B * N * D;

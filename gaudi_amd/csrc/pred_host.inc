@@ -39,7 +39,7 @@ static int run_predictor(gaudi_handle* h, int B, int N, const float* z, const fl
   if (!h->has_pred) return fail(h, GAUDI_E_STATE, "predictor weights not loaded");
   HIPCHECK(h, hipSetDevice(h->device));
   KParams P{};
-  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, 0, h->HPP);
+  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, 0, h->HPP, CallHints{});
   if (rc) return rc;
   P.F = h->pcfg.in_nf;
   fill_pred_common(h, P, B, N);
@@ -92,7 +92,7 @@ static int run_predict_noised(gaudi_handle* h, int B, int N, const float* x, con
     }
   }
   KParams P{};
-  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, 0, h->HPP);
+  int rc = stage_graph(h, B, N, node_mask, edge_mask, P, 0, h->HPP, CallHints{});
   if (rc) return rc;
   P.F = F;
   fill_pred_common(h, P, B, N);
