@@ -112,7 +112,14 @@ static int64_t pt_floats_per_mol(int N, int H, int L, int F1, int K) {
          8LL * E + 6LL * E;
 }
 
-static constexpr int64_t kPtScratchBytes = 1LL << 30;  // chunk size: the largest batch slice whose scratch fits in 1 GiB
+// chunk size: the largest batch slice whose scratch fits in 1 GiB, or in GAUDI_PRED_TRAIN_SCRATCH_KB (tests of the chunked path)
+static int64_t pt_scratch_bytes() {
+  if (const char* e = getenv("GAUDI_PRED_TRAIN_SCRATCH_KB")) {
+    const long long kb = atoll(e);
+    if (kb > 0) return kb * 1024LL;
+  }
+  return 1LL << 30;
+}
 
 extern "C" {
 
@@ -169,7 +176,7 @@ int gaudi_predictor_loss_grad(gaudi_handle* h, int B, int N, const float* x, con
   std::vector<float> tval(B);
   for (int b = 0; b < B; ++b) tval[b] = (float)t_int[b] / (float)T;
   const int64_t per = pt_floats_per_mol(N, H, L, F1, K);
-  const int Bc = (int)std::max<int64_t>(1, std::min<int64_t>(B, kPtScratchBytes / (int64_t)sizeof(float) / per));
+  const int Bc = (int)std::max<int64_t>(1, std::min<int64_t>(B, pt_scratch_bytes() / (int64_t)sizeof(float) / per));
   HIPCHECK(h, s.scratch.reserve(sizeof(float) * (size_t)per * Bc));
   HIPCHECK(h, s.grad.reserve(sizeof(float) * (size_t)std::max<int64_t>(s.total, 1)));
   HIPCHECK(h, s.y.reserve(sizeof(float) * (size_t)B * K));
