@@ -193,6 +193,7 @@ EXPORTS = {
     "gaudi_edm_set_train_weights": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64)]),
     "gaudi_host_edm_train_layout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(FP), C.POINTER(C.c_int64),
                                               IP, IP, FP]),
+    "gaudi_host_train_floats_per_mol": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int64)]),
     "gaudi_host_edm_seed_coef": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, FP, FP, FP]),
     "gaudi_sample_grid": (C.c_int, [C.c_void_p, C.c_int, C.c_int, FP, FP, C.c_uint64, C.c_int64, FP, C.c_float, FP, C.c_float,
                                     C.c_int, IP, FP, FP, FP, FP, FP, FP, C.POINTER(Diag)]),

@@ -1,17 +1,14 @@
-// edm_train_host.inc -- EDM training half of the C ABI (included at the end of gaudi_hip.hip): the denoiser in torch layout
-// kept next to the sampler's packed images, gaudi_edm_set_train_weights and gaudi_edm_loss_grad (edm_train.h describes the
-// kernels).
+// edm_train_host.inc -- EDM training half of the C ABI (included at the end of gaudi_hip.hip after train_host.inc, the core it
+// shares with the predictor's half): the denoiser's role table, what its state and scratch add, gaudi_edm_set_train_weights
+// and gaudi_edm_loss_grad (edm_train.h describes the kernels).  The torch-layout copy is kept next to the sampler's packed
+// images.
 #include "edm_train.h"
 
-struct EdmTrainState {
-  std::vector<std::string> names;     // the names passed to gaudi_load_edm, in order
-  std::vector<int64_t> numel, start;  // per tensor
-  std::vector<int32_t> has_grad;
-  std::vector<int> off;               // gaudi_etrain::n_slots(S, L) float offsets (-1 absent)
-  int64_t total = 0;
-  DevBuf w, wt, doff, grad, scratch, jobs, tiles, in, net, sums;
+struct EdmTrainState : TrainState {
+  DevBuf in, net, sums;
   void release() {
-    DevBuf* bufs[] = {&w, &wt, &doff, &grad, &scratch, &jobs, &tiles, &in, &net, &sums};
+    TrainState::release();
+    DevBuf* bufs[] = {&in, &net, &sums};
     for (DevBuf* b : bufs) b->release();
   }
 };
@@ -26,73 +23,35 @@ static void et_release(gaudi_handle* h) {
 
 // The name -> role table of EGNN_dynamics_QM9's state dict (edm/egnn/models.py:29-45, egnn_new.py:6-312) and the rule for
 // which tensors have a gradient path: every dynamics.egnn.* role (gamma.gamma is an nn.Parameter with requires_grad=False,
-// en_diffusion.py:216-218, and buffer is a buffer; neither is a role).  Host only: start / off / has_grad per tensor, and
-// wt = the flat buffer with every matrix transposed (NULL: skip).  Returns 0, or the name of a tensor whose size does not
-// match its role.
+// en_diffusion.py:216-218, and buffer is a buffer; neither is a role).  Host only (train_host.inc: tr_layout).  Returns 0,
+// or the name of a tensor whose size does not match its role.
 static const char* et_layout(const gaudi_edm_config* cfg, int n, const char* const* names, const float* const* tensors,
                              const int64_t* numel, std::vector<int64_t>& start, std::vector<int>& off,
                              std::vector<int32_t>& has_grad, float* wt) {
   using namespace gaudi_etrain;
   const int H = cfg->hidden_nf, L = cfg->n_layers, S = cfg->inv_sublayers, F1 = cfg->in_node_nf + 1;
   const int A = cfg->sin_embedding ? 24 : 2, ld1 = 2 * H + A;
-  start.resize(n);
-  has_grad.assign(n, 0);
-  off.assign(n_slots(S, L), -1);
-  int64_t total = 0;
-  std::map<std::string, int> idx;
-  for (int i = 0; i < n; ++i) {
-    start[i] = total;
-    total += numel[i];
-    idx[names[i]] = i;
-    if (wt && tensors) std::copy(tensors[i], tensors[i] + numel[i], wt + start[i]);
-  }
-  const char* bad = nullptr;
-  auto see = [&](int slot, const std::string& name, int rows, int cols) {
-    auto it = idx.find(name);
-    if (it == idx.end()) return;
-    const int i = it->second;
-    if (numel[i] != (int64_t)rows * cols) {
-      if (!bad) bad = names[i];
-      return;
-    }
-    off[slot] = (int)start[i];
-    has_grad[i] = 1;
-    if (wt && tensors && rows > 1 && cols > 1)
-      for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) wt[start[i] + (int64_t)c * rows + r] = tensors[i][(int64_t)r * cols + c];
-  };
   const std::string p = "dynamics.egnn.";
-  see(EMB_W, p + "embedding.weight", H, F1);
-  see(EMB_B, p + "embedding.bias", H, 1);
-  see(OUT_W, p + "embedding_out.weight", F1, H);
-  see(OUT_B, p + "embedding_out.bias", F1, 1);
+  std::vector<TrainRole> t = {{EMB_W, p + "embedding.weight", H, F1, true},
+                              {EMB_B, p + "embedding.bias", H, 1, true},
+                              {OUT_W, p + "embedding_out.weight", F1, H, true},
+                              {OUT_B, p + "embedding_out.bias", F1, 1, true}};
   for (int l = 0; l < L; ++l) {
     const std::string blk = p + "e_block_" + std::to_string(l) + ".";
     for (int s = 0; s < S; ++s) {
       const std::string q = blk + "gcl_" + std::to_string(s) + ".";
-      const int o = gcl_slot(S, l, s, 0);
-      see(o + E0W, q + "edge_mlp.0.weight", H, ld1);
-      see(o + E0B, q + "edge_mlp.0.bias", H, 1);
-      see(o + E2W, q + "edge_mlp.2.weight", H, H);
-      see(o + E2B, q + "edge_mlp.2.bias", H, 1);
-      if (cfg->attention) {
-        see(o + AW, q + "att_mlp.0.weight", 1, H);
-        see(o + AB, q + "att_mlp.0.bias", 1, 1);
-      }
-      see(o + N0W, q + "node_mlp.0.weight", H, 2 * H);
-      see(o + N0B, q + "node_mlp.0.bias", H, 1);
-      see(o + N2W, q + "node_mlp.2.weight", H, H);
-      see(o + N2B, q + "node_mlp.2.bias", H, 1);
+      tr_edge_roles(t, q, H, ld1, cfg->attention, gcl_slot(S, l, s, E0W));
+      tr_node_roles(t, q, H, gcl_slot(S, l, s, N0W));
     }
     const std::string q = blk + "gcl_equiv.coord_mlp.";
     const int o = equiv_slot(S, l, 0);
-    see(o + C0W, q + "0.weight", H, ld1);
-    see(o + C0B, q + "0.bias", H, 1);
-    see(o + C2W, q + "2.weight", H, H);
-    see(o + C2B, q + "2.bias", H, 1);
-    see(o + C4W, q + "4.weight", 1, H);
+    t.push_back({o + C0W, q + "0.weight", H, ld1, true});
+    t.push_back({o + C0B, q + "0.bias", H, 1, true});
+    t.push_back({o + C2W, q + "2.weight", H, H, true});
+    t.push_back({o + C2B, q + "2.bias", H, 1, true});
+    t.push_back({o + C4W, q + "4.weight", 1, H, true});
   }
-  return bad;
+  return tr_layout(t, n_slots(S, L), n, names, tensors, numel, start, off, has_grad, wt);
 }
 
 // gaudi_load_edm's check before it replaces anything: 0, or the name of a tensor whose size does not match its role
@@ -123,45 +82,20 @@ static bool et_complete(const gaudi_edm_config* cfg, const std::vector<int>& off
 static int et_upload(gaudi_handle* h, const gaudi_edm_config* cfg, int n, const char* const* names, const float* const* tensors,
                      const int64_t* numel) {
   if (!h->et) h->et = new EdmTrainState();
-  EdmTrainState& s = *h->et;
-  std::vector<int64_t> start;
-  std::vector<int> off;
-  std::vector<int32_t> has;
-  int64_t total = 0;
-  for (int i = 0; i < n; ++i) total += numel[i];
-  std::vector<float> w((size_t)total), wt((size_t)total);
-  const char* bad = et_layout(cfg, n, names, tensors, numel, start, off, has, wt.data());
-  if (bad) return fail(h, GAUDI_E_MISSING, std::string("EDM tensor mis-shaped: ") + bad);
-  for (int i = 0; i < n; ++i) std::copy(tensors[i], tensors[i] + numel[i], w.begin() + start[i]);
-  s.names.assign(names, names + n);
-  s.numel.assign(numel, numel + n);
-  s.start = start;
-  s.off = off;
-  s.has_grad = has;
-  s.total = total;
-  HIPCHECK(h, s.w.reserve(sizeof(float) * std::max<size_t>(w.size(), 1)));
-  HIPCHECK(h, s.wt.reserve(sizeof(float) * std::max<size_t>(wt.size(), 1)));
-  HIPCHECK(h, s.doff.reserve(sizeof(int) * s.off.size()));
-  HIPCHECK(h, hipMemcpy(s.w.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(s.wt.p, wt.data(), sizeof(float) * wt.size(), hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(s.doff.p, s.off.data(), sizeof(int) * s.off.size(), hipMemcpyHostToDevice));
-  return GAUDI_OK;
+  return tr_upload(h, *h->et, "EDM", n, names, tensors, numel,
+                   [&](std::vector<int64_t>& start, std::vector<int>& off, std::vector<int32_t>& has, float* wt) {
+                     return et_layout(cfg, n, names, tensors, numel, start, off, has, wt);
+                   });
 }
 
-// floats of chunk scratch per molecule (edm_train.h)
-static int64_t et_floats_per_mol(int N, int H, int L, int S, int F, int A) {
-  const int64_t E = (int64_t)N * N, F1 = F + 1, D = 3 + F;
-  return ((int64_t)L * (S + 1) + 1) * N * H + (int64_t)(L + 1) * N * 4 + N * F1 + N * D + E * (A / 2) + E * A + 8 * E +
-         2 * E + 9LL * N * H + 4LL * N + N * F1 + 6 * E * H + 5 * E;
-}
-
-// chunk size: the largest batch slice whose scratch fits in 1 GiB, or in GAUDI_EDM_TRAIN_SCRATCH_KB (tests of the chunked path)
-static int64_t et_scratch_bytes() {
-  if (const char* e = getenv("GAUDI_EDM_TRAIN_SCRATCH_KB")) {
-    const long long kb = atoll(e);
-    if (kb > 0) return kb * 1024LL;
-  }
-  return 1LL << 30;
+// the chunk scratch of the EDM, from b's N, H, L, S, F, A (train_host.inc: Carver -- run once to count, once to carve)
+static void et_carve(gaudi_etrain::ETBufs& b, Carver& c) {
+  const int64_t N = b.N, E = N * N;
+  tr_carve(b, c, (int64_t)b.L * (b.S + 1) + 1, b.F + 1, b.F + 1);
+  b.eps = c.take(N * (3 + b.F));
+  b.d0a = c.take(E * (b.A / 2));
+  b.ea = c.take(E * b.A);
+  b.drad = c.take(E);
 }
 
 // d loss_b / d net = coef (net - eps): coef_out[0] for the x columns, coef_out[1] for the h columns (en_diffusion.py:507-515,
@@ -250,7 +184,6 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
                         const float* noise, int loss_type, const float* weight, float* loss_out, float* net_out,
                         float* grad_out, int32_t* has_grad_out) {
   using namespace gaudi_etrain;
-  using gaudi_train::OuterJob;
   if (!h || !x || !onehot || !t_int || !node_mask || !edge_mask || !loss_out || (grad_out && !has_grad_out))
     return GAUDI_E_INVALID;
   if (!h->has_edm || !h->et) return fail(h, GAUDI_E_STATE, "EDM weights not loaded");
@@ -286,9 +219,17 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
     et_seed_coef(loss_type, t_int[b], T, D, N, terms[4 * b + 3], weight ? weight[b] : 1.0f, &coef[2 * b]);
   }
   const bool rev = grad_out != nullptr;
-  const int64_t per = et_floats_per_mol(N, H, L, S, F, A);
-  const int Bc = (int)std::max<int64_t>(1, std::min<int64_t>(B, et_scratch_bytes() / (int64_t)sizeof(float) / per));
-  HIPCHECK(h, s.scratch.reserve(sizeof(float) * (size_t)per * Bc));
+  ETBufs b{};
+  b.F = F;
+  b.H = H;
+  b.L = L;
+  b.S = S;
+  b.N = N;
+  b.A = A;
+  Carver count{nullptr, 0};
+  et_carve(b, count);
+  const int Bc = tr_chunk(B, count.per, "GAUDI_EDM_TRAIN_SCRATCH_KB");
+  HIPCHECK(h, s.scratch.reserve(sizeof(float) * (size_t)count.per * Bc));
   HIPCHECK(h, s.net.reserve(sizeof(float) * (size_t)B * N * D));
   HIPCHECK(h, s.sums.reserve(sizeof(float) * (size_t)B * 4));
   // inputs: x, onehot, t, alpha / sigma, coef, node_mask, edge_mask, noise
@@ -301,7 +242,6 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
     p += cnt;
     return hipMemcpyAsync(dst, src, sizeof(float) * cnt, hipMemcpyHostToDevice, h->stream) == hipSuccess ? dst : nullptr;
   };
-  ETBufs b{};
   b.x = put(x, (size_t)B * N * 3);
   b.oh = put(onehot, (size_t)B * N * F);
   b.t = put(tval.data(), B);
@@ -319,12 +259,6 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
   b.w = s.w.as<float>();
   b.wt = s.wt.as<float>();
   b.off = s.doff.as<int>();
-  b.F = F;
-  b.H = H;
-  b.L = L;
-  b.S = S;
-  b.N = N;
-  b.A = A;
   b.attention = c.attention;
   b.use_tanh = c.tanh;
   b.sin = c.sin_embedding;
@@ -335,101 +269,43 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
   b.nv1 = c.norm_values[1];
   b.sig_cat = sqrtf(sigmoid_host(h->gamma[0])) * c.norm_values[1];
   b.bcap = Bc;
-  {
-    float* q = s.scratch.as<float>();
-    auto take = [&](int64_t cnt) {
-      float* r = q;
-      q += cnt * Bc;
-      return r;
-    };
-    b.hs = take(((int64_t)L * (S + 1) + 1) * N * H);
-    b.xs = take((int64_t)(L + 1) * N * 4);
-    b.hin = take((int64_t)N * F1);
-    b.eps = take((int64_t)N * D);
-    b.d0a = take((int64_t)E * (A / 2));
-    b.ea = take((int64_t)E * A);
-    b.diff = take(4LL * E);
-    b.dcd = take(4LL * E);
-    b.rad = take(E);
-    b.drad = take(E);
-    float** node[] = {&b.P, &b.Q, &b.agg, &b.qp, &b.q, &b.dr, &b.dP, &b.dQ, &b.dh};
-    for (float** r : node) *r = take((int64_t)N * H);
-    b.dx = take(4LL * N);
-    b.dhout = take((int64_t)N * F1);
-    float** edge[] = {&b.U, &b.Sx, &b.V, &b.M, &b.EF, &b.DE};
-    for (float** r : edge) *r = take((int64_t)E * H);
-    float** sc[] = {&b.gate, &b.dap, &b.phi, &b.ppre, &b.dp};
-    for (float** r : sc) *r = take(E);
-  }
+  Carver carve{s.scratch.as<float>(), Bc};
+  et_carve(b, carve);
 
-  // the weight-gradient products per reverse launch (gcl_equiv, then the GCLs from the last, per block from the last;
-  // then the head), per chunk size
-  std::vector<OuterJob> jobs;
-  std::vector<int4> tiles;
-  std::vector<std::pair<int, int>> launches;
+  // the weight-gradient products per reverse launch: per block from the last, gcl_equiv, then the GCLs from the last; then
+  // the head
+  OuterPlan plan;
   if (rev) {
     HIPCHECK(h, s.grad.reserve(sizeof(float) * (size_t)std::max<int64_t>(s.total, 1)));
     HIPCHECK(h, hipMemsetAsync(s.grad.p, 0, sizeof(float) * (size_t)s.total, h->stream));
-    float* G = s.grad.as<float>();
+    plan.G = s.grad.as<float>();
     const int* o0 = s.off.data();
-    const int ld1 = 2 * H + A;
-    auto job = [&](const float* Yp, int ldy, int M, const float* Xp, int ldx, int Kc, int off, int ldg, int R) {
-      jobs.push_back(OuterJob{Yp, Xp, G + off, ldy, ldx, ldg, M, Kc, R});
-      for (int m0 = 0; m0 < M; m0 += 32)
-        for (int k0 = 0; k0 < Kc; k0 += 32) tiles.push_back(make_int4((int)jobs.size() - 1, m0, k0, 0));
-    };
     auto hst = [&](int l, int sub) { return b.hs + (size_t)(l * (S + 1) + sub) * Bc * N * H; };
-    // the first two layers of an edge MLP: W1 = [A | B | C] over [h_i | h_j | ea], b1, W2, b2
-    auto edge_jobs = [&](const float* hl, int w1, int b1, int w2, int b2, int Rn, int Re) {
-      job(b.dP, H, H, hl, H, H, w1, ld1, Rn);
-      job(b.dQ, H, H, hl, H, H, w1 + H, ld1, Rn);
-      job(b.U, H, H, b.ea, A, A, w1 + 2 * H, ld1, Re);
-      job(b.dP, H, H, nullptr, 0, 1, b1, 1, Rn);
-      job(b.V, H, H, b.Sx, H, H, w2, H, Re);
-      job(b.V, H, H, nullptr, 0, 1, b2, 1, Re);
-    };
-    auto plan = [&](int bc) {
+    plan.build(B, Bc, [&](int bc) {
       const int Rn = bc * N, Re = bc * E;
       for (int l = L - 1; l >= 0; --l) {
-        int first = (int)tiles.size();
+        plan.begin();
         const int* o = o0 + equiv_slot(S, l, 0);
-        edge_jobs(hst(l, S), o[C0W], o[C0B], o[C2W], o[C2B], Rn, Re);
-        job(b.dp, 1, 1, b.M, H, H, o[C4W], H, Re);
-        launches.push_back({first, (int)tiles.size() - first});
+        plan.edge_jobs(b, hst(l, S), o[C0W], o[C0B], o[C2W], o[C2B], A, Rn, Re, {{b.ea, A}});
+        plan.job(b.dp, 1, 1, b.M, H, H, o[C4W], H, Re);
+        plan.end();
         for (int sub = S - 1; sub >= 0; --sub) {
-          first = (int)tiles.size();
+          plan.begin();
           const int* g = o0 + gcl_slot(S, l, sub, 0);
           const float* hl = hst(l, sub);
-          edge_jobs(hl, g[E0W], g[E0B], g[E2W], g[E2B], Rn, Re);
-          if (c.attention) {
-            job(b.dap, 1, 1, b.M, H, H, g[AW], H, Re);
-            job(b.dap, 1, 1, nullptr, 0, 1, g[AB], 1, Re);
-          }
-          job(b.qp, H, H, hl, H, H, g[N0W], 2 * H, Rn);
-          job(b.qp, H, H, b.agg, H, H, g[N0W] + H, 2 * H, Rn);
-          job(b.qp, H, H, nullptr, 0, 1, g[N0B], 1, Rn);
-          job(b.dr, H, H, b.q, H, H, g[N2W], H, Rn);
-          job(b.dr, H, H, nullptr, 0, 1, g[N2B], 1, Rn);
-          launches.push_back({first, (int)tiles.size() - first});
+          plan.edge_jobs(b, hl, g[E0W], g[E0B], g[E2W], g[E2B], A, Rn, Re, {{b.ea, A}});
+          if (c.attention) plan.att_jobs(b, g[AW], g[AB], Re);
+          plan.node_jobs(b, hl, g[N0W], g[N0B], g[N2W], g[N2B], Rn);
+          plan.end();
         }
       }
-      const int first = (int)tiles.size();
-      job(b.dhout, F1, F1, hst(L, 0), H, H, o0[OUT_W], H, Rn);
-      job(b.dhout, F1, F1, nullptr, 0, 1, o0[OUT_B], 1, Rn);
-      job(b.dh, H, H, b.hin, F1, F1, o0[EMB_W], F1, Rn);
-      job(b.dh, H, H, nullptr, 0, 1, o0[EMB_B], 1, Rn);
-      launches.push_back({first, (int)tiles.size() - first});
-    };
-    plan(Bc);
-    if (B % Bc) plan(B % Bc);
-    HIPCHECK(h, s.jobs.reserve(sizeof(OuterJob) * jobs.size()));
-    HIPCHECK(h, s.tiles.reserve(sizeof(int4) * tiles.size()));
-    HIPCHECK(h, hipMemcpyAsync(s.jobs.p, jobs.data(), sizeof(OuterJob) * jobs.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(h, hipMemcpyAsync(s.tiles.p, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice, h->stream));
+      plan.begin();
+      plan.head_jobs(b, hst(L, 0), F1, F1, o0, Rn);
+      plan.end();
+    });
+    const int rc = plan.upload(h, s);
+    if (rc) return rc;
   }
-  const OuterJob* djobs = s.jobs.as<OuterJob>();
-  const int4* dtiles = s.tiles.as<int4>();
-  const size_t per_plan = (size_t)L * (S + 1) + 1;  // reverse launches of one chunk's plan
 
   for (int b0 = 0; b0 < B; b0 += Bc) {
     const int bc = std::min(Bc, B - b0);
@@ -438,31 +314,47 @@ int gaudi_edm_loss_grad(gaudi_handle* h, int B, int N, const float* x, const flo
     for (int l = 0; l < L; ++l) HIPCHECK(h, (hipError_t)gaudi_et_block(b, bc, l, h->stream));
     HIPCHECK(h, (hipError_t)gaudi_et_readout(b, bc, rev ? 1 : 0, h->stream));
     if (!rev) continue;
-    size_t li = bc == Bc ? 0 : per_plan;
+    plan.select(bc);
+    size_t li = 0;
     for (int l = L - 1; l >= 0; --l) {
       HIPCHECK(h, (hipError_t)gaudi_et_equiv_reverse(b, bc, l, h->stream));
-      HIPCHECK(h, (hipError_t)gaudi_pt_outer(djobs, dtiles + launches[li].first, launches[li].second, h->stream));
-      ++li;
+      HIPCHECK(h, plan.launch(li++, h->stream));
       for (int sub = S - 1; sub >= 0; --sub) {
         HIPCHECK(h, (hipError_t)gaudi_et_gcl_reverse(b, bc, l, sub, h->stream));
-        HIPCHECK(h, (hipError_t)gaudi_pt_outer(djobs, dtiles + launches[li].first, launches[li].second, h->stream));
-        ++li;
+        HIPCHECK(h, plan.launch(li++, h->stream));
       }
     }
-    HIPCHECK(h, (hipError_t)gaudi_pt_outer(djobs, dtiles + launches[li].first, launches[li].second, h->stream));
+    HIPCHECK(h, plan.launch(li, h->stream));
   }
   std::vector<float> sums((size_t)B * 4);
   HIPCHECK(h, hipMemcpyAsync(sums.data(), s.sums.p, sizeof(float) * B * 4, hipMemcpyDeviceToHost, h->stream));
   if (net_out) HIPCHECK(h, hipMemcpyAsync(net_out, s.net.p, sizeof(float) * (size_t)B * N * D, hipMemcpyDeviceToHost, h->stream));
-  std::vector<float> g(rev ? (size_t)s.total : 0);
-  if (rev) HIPCHECK(h, hipMemcpyAsync(g.data(), s.grad.p, sizeof(float) * (size_t)s.total, hipMemcpyDeviceToHost, h->stream));
-  HIPCHECK(h, hipStreamSynchronize(h->stream));
+  if (rev) {
+    const int rc = tr_grads_out(h, s, grad_out, has_grad_out);
+    if (rc) return rc;
+  } else {
+    HIPCHECK(h, hipStreamSynchronize(h->stream));
+  }
   for (int b0 = 0; b0 < B; ++b0) loss_out[b0] = et_loss(loss_type, t_int[b0], T, D, N, &terms[4 * b0], &sums[4 * b0]);
-  if (rev)
-    for (size_t i = 0; i < s.numel.size(); ++i) {
-      has_grad_out[i] = s.has_grad[i];
-      if (s.has_grad[i]) std::copy(g.begin() + s.start[i], g.begin() + s.start[i] + s.numel[i], grad_out + s.start[i]);
-    }
+  return GAUDI_OK;
+}
+
+// The chunk scratch per molecule, in floats, as the carver counts it for a network (0: the predictor, 1: the EDM) of the
+// given shape -- the number that sizes a call's chunks.  Defined here, after both networks' lists.
+int gaudi_host_train_floats_per_mol(int net, int N, int H, int L, int S, int F, int K, int A, int64_t* floats_out) {
+  if ((net != 0 && net != 1) || N < 1 || H < 1 || L < 1 || S < 1 || F < 0 || K < 1 || A < 2 || !floats_out)
+    return GAUDI_E_INVALID;
+  Carver count{nullptr, 0};
+  if (net == 0) {
+    gaudi_train::PTBufs b{};
+    b.N = N, b.H = H, b.L = L, b.F = F, b.K = K, b.A = 2;
+    pt_carve(b, count);
+  } else {
+    gaudi_etrain::ETBufs b{};
+    b.N = N, b.H = H, b.L = L, b.S = S, b.F = F, b.A = A;
+    et_carve(b, count);
+  }
+  *floats_out = count.per;
   return GAUDI_OK;
 }
 

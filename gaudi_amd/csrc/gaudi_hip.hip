@@ -250,7 +250,7 @@ static int fail(gaudi_handle* h, int code, const std::string& msg) {
   return code;
 }
 
-// pred_train_host.inc
+// pred_train_host.inc (train_host.inc holds what it shares with edm_train_host.inc)
 static void pt_release(gaudi_handle* h);
 // edm_train_host.inc
 static void et_release(gaudi_handle* h);
@@ -2143,6 +2143,7 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 
 #include "pred_host.inc"
 #include "chain_host.inc"
+#include "train_host.inc"
 #include "pred_train_host.inc"
 #include "stability.inc"
 #include "atoms.inc"

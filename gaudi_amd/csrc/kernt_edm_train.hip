@@ -1,40 +1,16 @@
 // kernt_edm_train.hip -- the EDM's training kernels (edm_train.h): forward noising and embedding, one block forward, the
 // loss readout and its seed, and the reverse passes of gcl_equiv and of one GCL sub-layer.  One workgroup (256 threads) per
-// molecule; fp32 instructions throughout.  The weight-gradient reduction is pred_train.h's gaudi_pt_outer.
+// molecule; fp32 instructions throughout.  The pieces of a GCL it has in common with the
+// predictor's kernels are train_device.h's; the weight-gradient reduction is gaudi_pt_outer (kernt_pred_train.hip).
 #include "edm_train.h"
 #include "edm_device.h"
-#include "train_device.h"
 
 namespace gaudi_etrain {
 
-using gaudi_train::dsilu;
-using gaudi_train::kRows;
-using gaudi_train::kThreads;
-using gaudi_train::mm_rows;
-using gaudi_train::sigm;
-using gaudi_train::silu;
+using namespace gaudi_train;
 
-struct Mol {
-  int mb, bg, N, E, H;
-  const float *nm, *em;
-  __device__ Mol(const ETBufs& b) {
-    mb = blockIdx.x;
-    bg = b.b0 + mb;
-    N = b.N;
-    E = N * N;
-    H = b.H;
-    nm = b.nm + (size_t)bg * N;
-    em = b.em + (size_t)bg * E;
-  }
-  __device__ float* node(float* base) const { return base + (size_t)mb * N * H; }
-  __device__ float* edge(float* base) const { return base + (size_t)mb * E * H; }
-  __device__ float* escal(float* base, int w = 1) const { return base + (size_t)mb * E * w; }
-  // stash: h at sub-layer s (s = S: the input of gcl_equiv) of block l, x at the input of block l
-  __device__ float* hst(const ETBufs& b, int l, int s) const {
-    return b.hs + ((size_t)(l * (b.S + 1) + s) * b.bcap + mb) * N * H;
-  }
-  __device__ float* xst(const ETBufs& b, int l) const { return b.xs + ((size_t)l * b.bcap + mb) * N * 4; }
-};
+// stash: h at sub-layer s (s = S: the input of gcl_equiv) of block l; x at the input of block l is m.xstash(b, l)
+__device__ inline float* hst(const ETBufs& b, const Mol& m, int l, int s) { return m.hstash(b, l * (b.S + 1) + s); }
 
 // a sum over the nodes of one molecule in node order (thread 0), broadcast through LDS
 __device__ float node_sum(const float* v, int N, float* cell) {
@@ -57,7 +33,7 @@ __global__ void __launch_bounds__(kThreads) et_embed_kernel(const ETBufs b) {
   const int N = m.N, F = b.F, F1 = F + 1, D = 3 + F, A2 = b.A / 2, tid = threadIdx.x;
   float* eps = b.eps + (size_t)m.mb * N * D;
   float* hin = b.hin + (size_t)m.mb * N * F1;
-  float* x = m.xst(b, 0);
+  float* x = m.xstash(b, 0);
   // sample_combined_position_feature_noise (en_diffusion.py:937-956): raw draw 0, masked, x part mean-removed
   for (int i = tid; i < N * D; i += kThreads) {
     float raw;
@@ -110,14 +86,14 @@ __global__ void __launch_bounds__(kThreads) et_embed_kernel(const ETBufs b) {
     if (b.sin) gaudi::sin_features(r, d0a + (size_t)e * A2);
     else d0a[e] = r;
   }
-  mm_rows(b.wt + b.off[EMB_W], m.H, F1, m.H, hin, F1, N, m.hst(b, 0, 0), m.H, b.w + b.off[EMB_B], false, lds);
+  mm_rows(b.wt + b.off[EMB_W], m.H, F1, m.H, hin, F1, N, hst(b, m, 0, 0), m.H, b.w + b.off[EMB_B], false, lds);
 }
 
 // coord2diff (egnn_new.py:394-400) of the block input x -> diff [E][4] (coord_diff, norm), radial, and the edge attributes
 // [radial | d0] or their sinusoids (egnn_new.py:214-218)
 __device__ void block_geo(const ETBufs& b, const Mol& m, int l) {
   const int N = m.N, A = b.A, A2 = A / 2, tid = threadIdx.x;
-  const float* x = m.xst(b, l);
+  const float* x = m.xstash(b, l);
   float *diff = m.escal(b.diff, 4), *rad = m.escal(b.rad), *ea = m.escal(b.ea, A);
   const float* d0a = m.escal(b.d0a, A2);
   for (int e = tid; e < m.E; e += kThreads) {
@@ -143,7 +119,7 @@ __device__ void block_geo(const ETBufs& b, const Mol& m, int l) {
 // P = A h + b1, Q = B h, U = P_i + Q_j + C ea, S = silu(U), V = W2 S + b2, M = silu(V)
 __device__ void edge_mlp(const ETBufs& b, const Mol& m, const float* h, int w1, int b1, int w2, int b2, float* lds) {
   const int N = m.N, E = m.E, H = m.H, A = b.A, tid = threadIdx.x;
-  float *P = m.node(b.P), *Q = m.node(b.Q), *U = m.edge(b.U), *S = m.edge(b.Sx), *V = m.edge(b.V), *M = m.edge(b.M);
+  float *P = m.node(b.P), *Q = m.node(b.Q), *U = m.edge(b.U), *S = m.edge(b.Su), *V = m.edge(b.V), *M = m.edge(b.M);
   const float* ea = m.escal(b.ea, A);
   const float* W1T = b.wt + w1;  // [2H + A][H]
   mm_rows(W1T, H, H, H, h, H, N, P, H, b.w + b1, false, lds);
@@ -163,52 +139,19 @@ __device__ void edge_mlp(const ETBufs& b, const Mol& m, const float* h, int w1, 
 
 // GCL sub-layer s of block l (egnn_new.py:6-93) from the stash; with `out`, its output h into the stash
 __device__ void gcl_forward(const ETBufs& b, const Mol& m, int l, int s, bool out, float* lds) {
-  const int N = m.N, E = m.E, H = m.H, S = b.S, tid = threadIdx.x;
-  const float* h = m.hst(b, l, s);
-  float *agg = m.node(b.agg), *qp = m.node(b.qp), *q = m.node(b.q), *M = m.edge(b.M), *EF = m.edge(b.EF);
-  float* gate = m.escal(b.gate);
-  const int o = gcl_slot(S, l, s, 0);
-  edge_mlp(b, m, h, b.off[o + E0W], b.off[o + E0B], b.off[o + E2W], b.off[o + E2B], lds);
-  for (int e = tid; e < E; e += kThreads) {  // att_mlp (egnn_new.py:50-52)
-    float g = 1.f;
-    if (b.attention) {
-      const float* wa = b.w + b.off[o + AW];
-      float a = b.w[b.off[o + AB]];
-      for (int k = 0; k < H; ++k) a = fmaf(wa[k], M[e * H + k], a);
-      g = sigm(a);
-    }
-    gate[e] = g;
-  }
+  const float* h = hst(b, m, l, s);
+  const int* o = b.off + gcl_slot(b.S, l, s, 0);
+  edge_mlp(b, m, h, o[E0W], o[E0B], o[E2W], o[E2B], lds);
+  gate_edge_feat(b, m, o + AW);  // att_mlp (egnn_new.py:50-52)
   __syncthreads();
-  for (int idx = tid; idx < E * H; idx += kThreads) {
-    const int e = idx / H;
-    EF[idx] = M[idx] * gate[e] * m.em[e];
-  }
-  __syncthreads();
-  for (int idx = tid; idx < N * H; idx += kThreads) {  // unsorted_segment_sum over row (egnn_new.py:403-420)
-    const int i = idx / H, k = idx - i * H;
-    float a = 0.f;
-    for (int j = 0; j < N; ++j) a += EF[(i * N + j) * H + k];
-    agg[idx] = a / b.agg_div;
-  }
-  __syncthreads();
-  const float* Wn1T = b.wt + b.off[o + N0W];  // [2H][H]
-  mm_rows(Wn1T, H, H, H, h, H, N, qp, H, b.w + b.off[o + N0B], false, lds);
-  mm_rows(Wn1T + (size_t)H * H, H, H, H, agg, H, N, qp, H, nullptr, true, lds);
-  for (int idx = tid; idx < N * H; idx += kThreads) q[idx] = silu(qp[idx]);
-  __syncthreads();
-  if (out) {
-    float* ho = m.hst(b, l, s + 1);
-    mm_rows(b.wt + b.off[o + N2W], H, H, H, q, H, N, ho, H, b.w + b.off[o + N2B], false, lds);
-    for (int idx = tid; idx < N * H; idx += kThreads) ho[idx] = (h[idx] + ho[idx]) * m.nm[idx / H];
-    __syncthreads();
-  }
+  row_aggregate<true>(b, m, b.agg_div);  // unsorted_segment_sum over row (egnn_new.py:403-420)
+  node_mlp_forward(b, m, h, o + N0W, out ? l * (b.S + 1) + s + 1 : -1, lds);
 }
 
 // gcl_equiv of block l (egnn_new.py:96-168); with `out`, x of block l + 1 and the block's output h = h * node_mask
 __device__ void equiv_forward(const ETBufs& b, const Mol& m, int l, bool out, float* lds) {
   const int N = m.N, E = m.E, H = m.H, S = b.S, tid = threadIdx.x;
-  const float* h = m.hst(b, l, S);
+  const float* h = hst(b, m, l, S);
   float *M = m.edge(b.M), *diff = m.escal(b.diff, 4), *phi = m.escal(b.phi), *ppre = m.escal(b.ppre);
   const int o = equiv_slot(S, l, 0);
   edge_mlp(b, m, h, b.off[o + C0W], b.off[o + C0B], b.off[o + C2W], b.off[o + C2B], lds);
@@ -221,8 +164,8 @@ __device__ void equiv_forward(const ETBufs& b, const Mol& m, int l, bool out, fl
   }
   __syncthreads();
   if (out) {
-    const float* x = m.xst(b, l);
-    float* xo = m.xst(b, l + 1);
+    const float* x = m.xstash(b, l);
+    float* xo = m.xstash(b, l + 1);
     for (int i = tid; i < N; i += kThreads) {
       float a[3] = {0.f, 0.f, 0.f};
       for (int j = 0; j < N; ++j) {
@@ -232,7 +175,7 @@ __device__ void equiv_forward(const ETBufs& b, const Mol& m, int l, bool out, fl
       for (int k = 0; k < 3; ++k) xo[i * 4 + k] = (x[i * 4 + k] + a[k] / b.agg_div) * m.nm[i];
       xo[i * 4 + 3] = 0.f;
     }
-    float* hn = m.hst(b, l + 1, 0);
+    float* hn = hst(b, m, l + 1, 0);
     for (int idx = tid; idx < N * H; idx += kThreads) hn[idx] = h[idx] * m.nm[idx / H];
     __syncthreads();
   }
@@ -246,36 +189,11 @@ __global__ void __launch_bounds__(kThreads) et_block_kernel(const ETBufs b, int 
   equiv_forward(b, m, l, true, lds);
 }
 
-// the reverse of the edge MLP's first two layers, from dV (in V): leaves dU in U, its row / column sums in dP / dQ, adds
-// A^T dP + B^T dQ to dh, and (without sin_embedding) the radial column's C^T dU to drad
-__device__ void edge_mlp_reverse(const ETBufs& b, const Mol& m, int w1, int w2, float* lds) {
-  const int N = m.N, E = m.E, H = m.H, A = b.A, ld1 = 2 * H + A, tid = threadIdx.x;
-  float *dP = m.node(b.dP), *dQ = m.node(b.dQ), *dh = m.node(b.dh);
-  float *U = m.edge(b.U), *V = m.edge(b.V), *DE = m.edge(b.DE), *drad = m.escal(b.drad);
-  mm_rows(b.w + w2, H, H, H, V, H, E, DE, H, nullptr, false, lds);  // DE <- dS = W2^T dV
-  for (int idx = tid; idx < E * H; idx += kThreads) U[idx] = DE[idx] * dsilu(U[idx]);  // U: dU
-  __syncthreads();
-  for (int idx = tid; idx < N * H; idx += kThreads) {
-    const int i = idx / H, k = idx - i * H;
-    float a = 0.f, c = 0.f;
-    for (int j = 0; j < N; ++j) {
-      a += U[(i * N + j) * H + k];
-      c += U[(j * N + i) * H + k];
-    }
-    dP[idx] = a;
-    dQ[idx] = c;
-  }
-  const float* W1 = b.w + w1;  // [H][2H + A]
-  if (!b.sin) {  // (sin_embedding detaches the distance features: egnn_new.py:391)
-    for (int e = tid; e < E; e += kThreads) {
-      float g = 0.f;
-      for (int k = 0; k < H; ++k) g = fmaf(W1[(size_t)k * ld1 + 2 * H], U[e * H + k], g);
-      drad[e] += g;
-    }
-  }
-  __syncthreads();
-  mm_rows(W1, ld1, H, H, dP, H, N, dh, H, nullptr, true, lds);
-  mm_rows(W1 + H, ld1, H, H, dQ, H, N, dh, H, nullptr, true, lds);
+// the reverse of an edge MLP's first two layers (train_device.h: edge_mlp_reverse); the radial column's C^T dU adds to drad,
+// except with sin_embedding, which detaches the distance features (egnn_new.py:391)
+__device__ void edge_reverse(const ETBufs& b, const Mol& m, int w1, int w2, float* lds) {
+  float* drad = m.escal(b.drad);
+  edge_mlp_reverse(b, m, w1, w2, !b.sin, lds, [&](int e, float g) { drad[e] += g; });
 }
 
 // gcl_equiv of block l, reverse: d (h_out, x_out) in (dh, dx) -> d h at its input in dh, d x through the residual in dx,
@@ -287,7 +205,7 @@ __global__ void __launch_bounds__(kThreads) et_equiv_rev_kernel(const ETBufs b, 
   block_geo(b, m, l);
   equiv_forward(b, m, l, false, lds);
   const int o = equiv_slot(S, l, 0);
-  float *dh = m.node(b.dh), *dx = b.dx + (size_t)m.mb * N * 4, *V = m.edge(b.V);
+  float *dh = m.node(b.dh), *dx = m.dx(b), *V = m.edge(b.V);
   float *diff = m.escal(b.diff, 4), *dcd = m.escal(b.dcd, 4), *phi = m.escal(b.phi), *ppre = m.escal(b.ppre),
         *dp = m.escal(b.dp), *drad = m.escal(b.drad);
   for (int idx = tid; idx < N * H; idx += kThreads) dh[idx] *= m.nm[idx / H];  // h_out = h * node_mask
@@ -316,7 +234,7 @@ __global__ void __launch_bounds__(kThreads) et_equiv_rev_kernel(const ETBufs b, 
     V[idx] = dp[e] * w4[k] * dsilu(V[idx]);  // V: dV
   }
   __syncthreads();
-  edge_mlp_reverse(b, m, b.off[o + C0W], b.off[o + C2W], lds);
+  edge_reverse(b, m, b.off[o + C0W], b.off[o + C2W], lds);
 }
 
 // GCL sub-layer s of block l, reverse: d h_out in dh -> d h_in in dh; after sub-layer 0 the block's d coord_diff and
@@ -324,52 +242,23 @@ __global__ void __launch_bounds__(kThreads) et_equiv_rev_kernel(const ETBufs b, 
 __global__ void __launch_bounds__(kThreads) et_gcl_rev_kernel(const ETBufs b, int l, int s) {
   __shared__ float lds[kRows * 256];
   const Mol m(b);
-  const int N = m.N, E = m.E, H = m.H, S = b.S, tid = threadIdx.x;
+  const int N = m.N, E = m.E, H = m.H, tid = threadIdx.x;
   block_geo(b, m, l);
   gcl_forward(b, m, l, s, false, lds);
-  const int o = gcl_slot(S, l, s, 0);
-  float *dh = m.node(b.dh), *dr = m.node(b.dr), *qp = m.node(b.qp), *dP = m.node(b.dP), *dQ = m.node(b.dQ);
-  float *V = m.edge(b.V), *M = m.edge(b.M), *DE = m.edge(b.DE), *gate = m.escal(b.gate), *dap = m.escal(b.dap);
-  for (int idx = tid; idx < N * H; idx += kThreads) {
-    const float v = dh[idx] * m.nm[idx / H];
-    dr[idx] = v;
-    dh[idx] = v;
-  }
-  __syncthreads();
-  mm_rows(b.w + b.off[o + N2W], H, H, H, dr, H, N, dQ, H, nullptr, false, lds);  // dq = Wn2^T dr
-  for (int idx = tid; idx < N * H; idx += kThreads) qp[idx] = dQ[idx] * dsilu(qp[idx]);  // qp: dqpre
-  const float* Wn1 = b.w + b.off[o + N0W];  // [H][2H]
-  mm_rows(Wn1, 2 * H, H, H, qp, H, N, dh, H, nullptr, true, lds);   // dh += Wn1h^T dqpre
-  mm_rows(Wn1 + H, 2 * H, H, H, qp, H, N, dP, H, nullptr, false, lds);  // dP <- dagg
+  const int* o = b.off + gcl_slot(b.S, l, s, 0);
+  float *dP = m.node(b.dP), *DE = m.edge(b.DE);
+  node_mlp_reverse(b, m, o + N0W, lds);
   for (int idx = tid; idx < E * H; idx += kThreads) {
     const int e = idx / H, k = idx - e * H, i = e / N;
     DE[idx] = dP[i * H + k] / b.agg_div;  // d edge_feat
   }
+  attention_reverse(b, m, o + AW);
   __syncthreads();
-  for (int e = tid; e < E; e += kThreads) {
-    float a = 0.f;
-    if (b.attention) {
-      for (int k = 0; k < H; ++k) a = fmaf(DE[e * H + k], M[e * H + k], a);
-      a *= m.em[e] * gate[e] * (1.f - gate[e]);
-    }
-    dap[e] = a;
-  }
-  __syncthreads();
-  {
-    const float* wa = b.attention ? b.w + b.off[o + AW] : nullptr;
-    for (int idx = tid; idx < E * H; idx += kThreads) {
-      const int e = idx / H, k = idx - e * H;
-      float dm = DE[idx] * gate[e] * m.em[e];
-      if (wa) dm = fmaf(dap[e], wa[k], dm);
-      V[idx] = dm * dsilu(V[idx]);  // V: dV
-    }
-  }
-  __syncthreads();
-  edge_mlp_reverse(b, m, b.off[o + E0W], b.off[o + E2W], lds);
+  edge_reverse(b, m, o[E0W], o[E2W], lds);
   if (s > 0) return;
   // block input: x -> coord_diff = d / (|d| + norm_constant), radial = |d|^2
-  const float* x = m.xst(b, l);
-  float *dx = b.dx + (size_t)m.mb * N * 4, *dcd = m.escal(b.dcd, 4), *drad = m.escal(b.drad);
+  const float* x = m.xstash(b, l);
+  float *dcd = m.escal(b.dcd, 4), *drad = m.escal(b.drad);
   __syncthreads();
   for (int e = tid; e < E; e += kThreads) {
     const int i = e / N, j = e - i * N;
@@ -385,13 +274,7 @@ __global__ void __launch_bounds__(kThreads) et_gcl_rev_kernel(const ETBufs b, in
     for (int k = 0; k < 3; ++k) dcd[e * 4 + k] = dcd[e * 4 + k] / den - d[k] * c + 2.f * d[k] * drad[e];
   }
   __syncthreads();
-  for (int i = tid; i < N; i += kThreads) {
-    float a[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < N; ++j)
-      for (int k = 0; k < 3; ++k) a[k] += dcd[(i * N + j) * 4 + k] - dcd[(j * N + i) * 4 + k];
-    for (int k = 0; k < 3; ++k) dx[i * 4 + k] += a[k];
-  }
-  __syncthreads();
+  scatter_dx(b, m);
 }
 
 // net = [remove_mean_with_mask((x_L - x_0) nm) | (embedding_out(h_L) nm)[:, :F]] (models.py:108-152, egnn_new.py:306-312),
@@ -402,8 +285,8 @@ __global__ void __launch_bounds__(kThreads) et_readout_kernel(const ETBufs b, in
   __shared__ float red[3 * 256 + 8];
   const Mol m(b);
   const int N = m.N, F = b.F, F1 = F + 1, D = 3 + F, H = m.H, tid = threadIdx.x;
-  const float* hf = m.hst(b, b.L, 0);
-  const float *xf = m.xst(b, b.L), *x0 = m.xst(b, 0);
+  const float* hf = hst(b, m, b.L, 0);
+  const float *xf = m.xstash(b, b.L), *x0 = m.xstash(b, 0);
   const float* eps = b.eps + (size_t)m.mb * N * D;
   const float* hin = b.hin + (size_t)m.mb * N * F1;
   float* h3 = b.dhout + (size_t)m.mb * N * F1;
@@ -480,7 +363,7 @@ __global__ void __launch_bounds__(kThreads) et_readout_kernel(const ETBufs b, in
     for (int n = tid; n < N; n += kThreads) tmp[n] = dv[d * N + n] * m.nm[n];
     dm[d] = node_sum(tmp, N, &red[3 * 256 + 4 + d]) / cnt;
   }
-  float* dx = b.dx + (size_t)m.mb * N * 4;
+  float* dx = m.dx(b);
   for (int i = tid; i < N * 4; i += kThreads) {  // remove_mean_with_mask, then vel = (x_L - x_0) * node_mask
     const int n = i / 4, d = i - n * 4;
     dx[i] = d < 3 ? (dv[d * N + n] - dm[d]) * m.nm[n] : 0.f;

@@ -1,27 +1,10 @@
 // kernt_pred_train.hip -- the predictor's training kernels (pred_train.h): embedding, one GCL layer forward or reverse,
 // the L1 readout seed, and the fixed-order weight-gradient reduction.  One workgroup (256 threads) per molecule for the
-// network kernels; fp32 instructions throughout.
+// network kernels; fp32 instructions throughout.  The pieces of a GCL it has in common with the EDM's kernels are
+// train_device.h's; the reduction serves both passes.
 #include "pred_train.h"
-#include "train_device.h"
 
 namespace gaudi_train {
-
-struct Mol {
-  int mb, bg, N, E, H;
-  const float *nm, *em;
-  __device__ Mol(const PTBufs& b) {
-    mb = blockIdx.x;
-    bg = b.b0 + mb;
-    N = b.N;
-    E = N * N;
-    H = b.H;
-    nm = b.nm + (size_t)bg * N;
-    em = b.em + (size_t)bg * E;
-  }
-  __device__ float* node(float* base) const { return base + (size_t)mb * N * H; }
-  __device__ float* edge(float* base) const { return base + (size_t)mb * E * H; }
-  __device__ float* escal(float* base, int w = 1) const { return base + (size_t)mb * E * w; }
-};
 
 __global__ void __launch_bounds__(kThreads) pt_embed_kernel(const PTBufs b) {
   __shared__ float lds[kRows * 256];
@@ -29,7 +12,7 @@ __global__ void __launch_bounds__(kThreads) pt_embed_kernel(const PTBufs b) {
   const int N = m.N, F = b.F, F1 = F + 1, D = 3 + F, tid = threadIdx.x;
   const float* z = b.zt + (size_t)m.bg * N * D;
   float* hin = b.hin + (size_t)m.mb * N * F1;
-  float* x = b.xs + (size_t)m.mb * N * 4;
+  float* x = m.xstash(b, 0);
   for (int i = tid; i < N * F1; i += kThreads) {
     const int n = i / F1, k = i - n * F1;
     hin[i] = k < F ? z[n * D + 3 + k] * m.nm[n] : b.t[m.bg];  // h * node_mask | h_time (models.py:440-451)
@@ -49,22 +32,20 @@ __global__ void __launch_bounds__(kThreads) pt_embed_kernel(const PTBufs b) {
     }
     d0[e] = r;  // edge_attr (models.py:452)
   }
-  mm_rows(b.wt + b.off[EMB_W], m.H, F1, m.H, hin, F1, N, m.node(b.hs), m.H, b.w + b.off[EMB_B], false, lds);
+  mm_rows(b.wt + b.off[EMB_W], m.H, F1, m.H, hin, F1, N, m.hstash(b, 0), m.H, b.w + b.off[EMB_B], false, lds);
 }
 
 // The forward of GCL layer l (gcl.py:288-316) from the stash hs[l], xs[l], keeping every intermediate in the layer
 // scratch; with `out`, also h_{l+1}, x_{l+1} into hs[l+1], xs[l+1].
 __device__ void layer_forward(const PTBufs& b, const Mol& m, int l, bool out, float* lds) {
-  const int N = m.N, E = m.E, H = m.H, Bc = b.bcap, tid = threadIdx.x;
+  const int N = m.N, E = m.E, H = m.H, tid = threadIdx.x;
   const int* o = b.off + NHEAD + NLAYER * l;
-  const int ld1 = 2 * H + 2;
-  const float* h = b.hs + ((size_t)l * Bc + m.mb) * N * H;
-  const float* x = b.xs + ((size_t)l * Bc + m.mb) * N * 4;
-  float *P = m.node(b.P), *Q = m.node(b.Q), *agg = m.node(b.agg), *qp = m.node(b.qp), *q = m.node(b.q);
-  float *U = m.edge(b.U), *S = m.edge(b.S), *V = m.edge(b.V), *M = m.edge(b.M), *EF = m.edge(b.EFt), *CP = m.edge(b.CP),
+  const float* h = m.hstash(b, l);
+  const float* x = m.xstash(b, l);
+  float *P = m.node(b.P), *Q = m.node(b.Q);
+  float *U = m.edge(b.U), *S = m.edge(b.Su), *V = m.edge(b.V), *M = m.edge(b.M), *EF = m.edge(b.EF), *CP = m.edge(b.CP),
         *C = m.edge(b.C);
-  float *diff = m.escal(b.diff, 4), *rad = m.escal(b.rad), *gate = m.escal(b.gate), *phi = m.escal(b.phi),
-        *ppre = m.escal(b.ppre);
+  float *diff = m.escal(b.diff, 4), *rad = m.escal(b.rad), *phi = m.escal(b.phi), *ppre = m.escal(b.ppre);
   const float* d0 = m.escal(b.d0);
   const float* W1T = b.wt + o[E0W];  // [2H+2][H]
   // edge_mlp.0 over [h_i | h_j | radial | d0] = P_i + Q_j + c_r radial + c_d d0 (P carries the bias)
@@ -93,21 +74,7 @@ __device__ void layer_forward(const PTBufs& b, const Mol& m, int l, bool out, fl
   mm_rows(b.wt + o[E2W], H, H, H, S, H, E, V, H, b.w + o[E2B], false, lds);
   for (int idx = tid; idx < E * H; idx += kThreads) M[idx] = silu(V[idx]);
   __syncthreads();
-  for (int e = tid; e < E; e += kThreads) {  // att_mlp (gcl.py:261-263)
-    float g = 1.f;
-    if (b.attention) {
-      const float* wa = b.w + o[AW];
-      float a = b.w[o[AB]];
-      for (int k = 0; k < H; ++k) a = fmaf(wa[k], M[e * H + k], a);
-      g = sigm(a);
-    }
-    gate[e] = g;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < E * H; idx += kThreads) {
-    const int e = idx / H;
-    EF[idx] = M[idx] * gate[e] * m.em[e];
-  }
+  gate_edge_feat(b, m, o + AW);  // att_mlp (gcl.py:261-263)
   mm_rows(b.wt + o[C0W], H, H, H, EF, H, E, CP, H, b.w + o[C0B], false, lds);
   for (int idx = tid; idx < E * H; idx += kThreads) C[idx] = silu(CP[idx]);
   __syncthreads();
@@ -118,15 +85,9 @@ __device__ void layer_forward(const PTBufs& b, const Mol& m, int l, bool out, fl
     ppre[e] = p;
     phi[e] = b.use_tanh ? tanhf(p) * b.coords_range_layer : p;
   }
-  for (int idx = tid; idx < N * H; idx += kThreads) {  // unsorted_segment_sum over row (gcl.py:268-271)
-    const int i = idx / H, k = idx - i * H;
-    float a = 0.f;
-    for (int j = 0; j < N; ++j) a += EF[(i * N + j) * H + k];
-    agg[idx] = a;
-  }
-  __syncthreads();
+  row_aggregate<false>(b, m, 1.f);  // unsorted_segment_sum over row (gcl.py:268-271): a plain sum
   if (out) {
-    float* xo = b.xs + ((size_t)(l + 1) * Bc + m.mb) * N * 4;
+    float* xo = m.xstash(b, l + 1);
     for (int i = tid; i < N; i += kThreads) {  // coord_model, 'sum' (gcl.py:276-300)
       float a[3] = {0.f, 0.f, 0.f};
       for (int j = 0; j < N; ++j) {
@@ -138,61 +99,31 @@ __device__ void layer_forward(const PTBufs& b, const Mol& m, int l, bool out, fl
       xo[i * 4 + 3] = 0.f;
     }
   }
-  const float* Wn1T = b.wt + o[N0W];  // [2H][H]
-  mm_rows(Wn1T, H, H, H, h, H, N, qp, H, b.w + o[N0B], false, lds);
-  mm_rows(Wn1T + (size_t)H * H, H, H, H, agg, H, N, qp, H, nullptr, true, lds);
-  for (int idx = tid; idx < N * H; idx += kThreads) q[idx] = silu(qp[idx]);
-  __syncthreads();
-  if (out) {
-    float* ho = b.hs + ((size_t)(l + 1) * Bc + m.mb) * N * H;
-    mm_rows(b.wt + o[N2W], H, H, H, q, H, N, ho, H, b.w + o[N2B], false, lds);
-    for (int idx = tid; idx < N * H; idx += kThreads) ho[idx] = (h[idx] + ho[idx]) * m.nm[idx / H];  // recurrent, mask
-    __syncthreads();
-  }
-  (void)ld1;
+  node_mlp_forward(b, m, h, o + N0W, out ? l + 1 : -1, lds);
 }
 
-// The reverse pass of GCL layer l: from (dh_{l+1}, dx_{l+1}) in one half of the ping-pong pair to (dh_l, dx_l) in the
-// other, leaving the operands of every weight gradient of the layer in the scratch (pred_train_host.inc lists them).
+// The reverse pass of GCL layer l: (dh_{l+1}, dx_{l+1}) in dh / dx become (dh_l, dx_l) in place, leaving the operands of
+// every weight gradient of the layer in the scratch (pred_train_host.inc lists them).
 __device__ void layer_reverse(const PTBufs& b, const Mol& m, int l, float* lds) {
   const int N = m.N, E = m.E, H = m.H, tid = threadIdx.x;
   const int* o = b.off + NHEAD + NLAYER * l;
-  const int ld1 = 2 * H + 2;
   const bool coord = l < b.L - 1;  // the last layer's coordinate output never reaches h
-  const int par = (b.L - 1 - l) & 1;
-  const float* dhn = m.node(par ? b.dh1 : b.dh0);
-  float* dh = m.node(par ? b.dh0 : b.dh1);
-  const float* dxn = (par ? b.dx1 : b.dx0) + (size_t)m.mb * N * 4;
-  float* dx = (par ? b.dx0 : b.dx1) + (size_t)m.mb * N * 4;
-  float *agg = m.node(b.agg), *qp = m.node(b.qp), *dr = m.node(b.dr), *dP = m.node(b.dP), *dQ = m.node(b.dQ);
-  float *U = m.edge(b.U), *V = m.edge(b.V), *M = m.edge(b.M), *CP = m.edge(b.CP), *DE = m.edge(b.DE);
-  float *diff = m.escal(b.diff, 4), *ddiff = m.escal(b.ddiff, 4), *rad = m.escal(b.rad), *gate = m.escal(b.gate),
-        *phi = m.escal(b.phi), *ppre = m.escal(b.ppre), *dp = m.escal(b.dp), *dap = m.escal(b.dap);
-  (void)agg;
-  (void)rad;
+  float *dx = m.dx(b), *dP = m.node(b.dP), *CP = m.edge(b.CP), *DE = m.edge(b.DE);
+  float *diff = m.escal(b.diff, 4), *dcd = m.escal(b.dcd, 4), *phi = m.escal(b.phi), *ppre = m.escal(b.ppre),
+        *dp = m.escal(b.dp);
   // h_out = (h + node_mlp([h | agg])) * nm ;  x_out = (x + sum_j trans_ij) * nm
-  for (int idx = tid; idx < N * H; idx += kThreads) {
-    const float v = dhn[idx] * m.nm[idx / H];
-    dr[idx] = v;
-    dh[idx] = v;
-  }
-  for (int idx = tid; idx < N * 4; idx += kThreads) dx[idx] = dxn[idx] * m.nm[idx / 4];
-  __syncthreads();
-  mm_rows(b.w + o[N2W], H, H, H, dr, H, N, dQ, H, nullptr, false, lds);  // dq = Wn2^T dh'
-  for (int idx = tid; idx < N * H; idx += kThreads) qp[idx] = dQ[idx] * dsilu(qp[idx]);  // qp: dqpre
-  const float* Wn1 = b.w + o[N0W];  // [H][2H]
-  mm_rows(Wn1, 2 * H, H, H, qp, H, N, dh, H, nullptr, true, lds);         // dh += Wn1h^T dqpre
-  mm_rows(Wn1 + H, 2 * H, H, H, qp, H, N, dP, H, nullptr, false, lds);    // dP <- dagg = Wn1a^T dqpre
+  for (int idx = tid; idx < N * 4; idx += kThreads) dx[idx] = dx[idx] * m.nm[idx / 4];
+  node_mlp_reverse(b, m, o + N0W, lds);
   // coordinate branch -> d phi -> d cpre (in CP), d edge_feat (DE)
   for (int e = tid; e < E; e += kThreads) {
     const int i = e / N;
-    float g = 0.f, dcd[3] = {0.f, 0.f, 0.f};
+    float g = 0.f, dt3[3] = {0.f, 0.f, 0.f};
     if (coord) {
       const float inv = 1.f / (diff[e * 4 + 3] + 1.f);
       for (int k = 0; k < 3; ++k) {
         const float dt = dx[i * 4 + k] * m.em[e];
         g += dt * diff[e * 4 + k] * inv;
-        dcd[k] = dt * phi[e];
+        dt3[k] = dt * phi[e];
       }
       if (b.use_tanh) {
         const float th = tanhf(ppre[e]);
@@ -200,7 +131,7 @@ __device__ void layer_reverse(const PTBufs& b, const Mol& m, int l, float* lds) 
       }
     }
     dp[e] = g;
-    for (int k = 0; k < 3; ++k) ddiff[e * 4 + k] = dcd[k];
+    for (int k = 0; k < 3; ++k) dcd[e * 4 + k] = dt3[k];
   }
   __syncthreads();
   if (coord) {
@@ -218,59 +149,16 @@ __device__ void layer_reverse(const PTBufs& b, const Mol& m, int l, float* lds) 
     const int e = idx / H, k = idx - e * H, i = e / N;
     DE[idx] += dP[i * H + k];
   }
-  __syncthreads();
-  for (int e = tid; e < E; e += kThreads) {  // edge_feat = silu(v) * gate * em
-    float a = 0.f;
-    if (b.attention) {
-      for (int k = 0; k < H; ++k) a = fmaf(DE[e * H + k], M[e * H + k], a);
-      a *= m.em[e] * gate[e] * (1.f - gate[e]);
-    }
-    dap[e] = a;
-  }
-  __syncthreads();
-  {
-    const float* wa = b.attention ? b.w + o[AW] : nullptr;
-    for (int idx = tid; idx < E * H; idx += kThreads) {
-      const int e = idx / H, k = idx - e * H;
-      float dm = DE[idx] * gate[e] * m.em[e];
-      if (wa) dm = fmaf(dap[e], wa[k], dm);
-      V[idx] = dm * dsilu(V[idx]);  // V: dv
-    }
-  }
-  mm_rows(b.w + o[E2W], H, H, H, V, H, E, DE, H, nullptr, false, lds);  // DE <- ds = W2^T dv
-  for (int idx = tid; idx < E * H; idx += kThreads) U[idx] = DE[idx] * dsilu(U[idx]);  // U: du
-  __syncthreads();
-  for (int idx = tid; idx < N * H; idx += kThreads) {
-    const int i = idx / H, k = idx - i * H;
-    float a = 0.f, c = 0.f;
-    for (int j = 0; j < N; ++j) {
-      a += U[(i * N + j) * H + k];
-      c += U[(j * N + i) * H + k];
-    }
-    dP[idx] = a;  // d(A h_i): sum over the edges of row i
-    dQ[idx] = c;  // d(Bm h_j): sum over the edges of col j
-  }
-  const float* W1 = b.w + o[E0W];  // [H][2H+2]
-  for (int e = tid; e < E; e += kThreads) {  // radial and coord_diff -> d diff
-    float dradial = 0.f;
-    for (int k = 0; k < H; ++k) dradial = fmaf(W1[(size_t)k * ld1 + 2 * H], U[e * H + k], dradial);
+  attention_reverse(b, m, o + AW);  // edge_feat = silu(v) * gate * em
+  edge_mlp_reverse(b, m, o[E0W], o[E2W], true, lds, [&](int e, float dradial) {  // radial and coord_diff -> d diff
     const float w = diff[e * 4 + 3], inv = 1.f / (w + 1.f);
     float dot = 0.f;
-    for (int k = 0; k < 3; ++k) dot += ddiff[e * 4 + k] * diff[e * 4 + k];
+    for (int k = 0; k < 3; ++k) dot += dcd[e * 4 + k] * diff[e * 4 + k];
     const float c = dot * inv * inv / w;
     for (int k = 0; k < 3; ++k)
-      ddiff[e * 4 + k] = ddiff[e * 4 + k] * inv - diff[e * 4 + k] * c + 2.f * diff[e * 4 + k] * dradial;
-  }
-  __syncthreads();
-  mm_rows(W1, ld1, H, H, dP, H, N, dh, H, nullptr, true, lds);      // dh += A^T dP
-  mm_rows(W1 + H, ld1, H, H, dQ, H, N, dh, H, nullptr, true, lds);  // dh += Bm^T dQ
-  for (int i = tid; i < N; i += kThreads) {
-    float a[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < N; ++j)
-      for (int k = 0; k < 3; ++k) a[k] += ddiff[(i * N + j) * 4 + k] - ddiff[(j * N + i) * 4 + k];
-    for (int k = 0; k < 3; ++k) dx[i * 4 + k] += a[k];
-  }
-  __syncthreads();
+      dcd[e * 4 + k] = dcd[e * 4 + k] * inv - diff[e * 4 + k] * c + 2.f * diff[e * 4 + k] * dradial;
+  });
+  scatter_dx(b, m);
 }
 
 __global__ void __launch_bounds__(kThreads) pt_layer_kernel(const PTBufs b, int l, int reverse) {
@@ -292,9 +180,9 @@ __global__ void __launch_bounds__(kThreads) pt_readout_kernel(const PTBufs b) {
     const float s = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
     dho[i] = s * b.dpred_scale * m.nm[n] / b.readout_div;
   }
-  for (int i = tid; i < N * 4; i += kThreads) b.dx0[(size_t)m.mb * N * 4 + i] = 0.f;
+  for (int i = tid; i < N * 4; i += kThreads) m.dx(b)[i] = 0.f;
   __syncthreads();
-  mm_rows(b.w + b.off[OUT_W], m.H, K, m.H, dho, K, N, m.node(b.dh0), m.H, nullptr, false, lds);
+  mm_rows(b.w + b.off[OUT_W], m.H, K, m.H, dho, K, N, m.node(b.dh), m.H, nullptr, false, lds);
 }
 
 // G[m][k] += sum_r Y[r][m] X[r][k] over one 32 x 32 tile per workgroup on v_mfma_f32_16x16x4_f32 (A[m][r] = Y[r][m],

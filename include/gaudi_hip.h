@@ -616,6 +616,11 @@ int gaudi_host_pred_train_layout(const gaudi_pred_config* cfg, int n, const char
  * wt_out (or NULL) = the flat buffer with every matrix transposed.  GAUDI_E_MISSING when a known name has the wrong size. */
 int gaudi_host_edm_train_layout(const gaudi_edm_config* cfg, int n, const char* const* names, const float* const* tensors,
                                 const int64_t* numel, int32_t* off_out, int32_t* has_grad_out, float* wt_out);
+/* The chunk scratch per molecule, in floats, of gaudi_predictor_loss_grad (net 0) or gaudi_edm_loss_grad (net 1), counted by
+ * the list that carves it (train_host.inc: Carver): the number that, with the scratch budget, sizes a call's chunks.  N padded
+ * nodes, H hidden_nf, L n_layers, S inv_sublayers (EDM), F node features without the time column, K out_nf (predictor),
+ * A = 24 with sin_embedding, else 2 (EDM; the predictor's is 2). */
+int gaudi_host_train_floats_per_mol(int net, int N, int H, int L, int S, int F, int K, int A, int64_t* floats_out);
 /* The seed of gaudi_edm_loss_grad's reverse pass, by the function the call uses: d loss_b / d net = coef (net - eps), with
  * coef_out [B][2] = (x columns, h columns) for loss_type (0 l2, 1 vlb), t_int [B] in 0..T, snr_w [B] = SNR(s - t) - 1 (read
  * for vlb at t > 0 only), D = 3 + F, padded N, and weight [B] (or NULL: 1 each). */

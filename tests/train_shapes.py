@@ -179,27 +179,42 @@ def bar(ref):
     return max(1e-4, 2.0 * max(ref.spread.values()))
 
 
-# ---- the scratch formulas of the two host files, restated: the chunk a knob value gives
+# ---- the scratch of the two host files, restated: the chunk a knob value gives.  The host code counts the floats with the list
+# that carves them (csrc/train_host.inc: Carver); these polynomials are written independently of it, and
+# tests/test_train_scratch_cpu.py holds gaudi_host_train_floats_per_mol to them at every case of the table.
 
 def pt_floats_per_mol(N, H, L, F1, K):
-    """csrc/pred_train_host.inc: pt_floats_per_mol."""
+    """csrc/pred_train_host.inc: pt_carve.  (L+1) node stashes of h and x, the input, d0, 9 node arrays (the running dh among
+    them, updated in place), dx, the readout gradient, 8 edge arrays, coord_diff and its gradient, 6 edge scalars."""
     E = N * N
-    return (L + 1) * N * (H + 4) + N * F1 + E + 10 * N * H + 8 * N + N * K + 8 * E * H + 8 * E + 6 * E
+    return (L + 1) * N * (H + 4) + N * F1 + E + 9 * N * H + 4 * N + N * K + 8 * E * H + 8 * E + 6 * E
+
+
+def pt_floats_per_mol_two_buffers(N, H, L, F1, K):
+    """What the predictor's scratch took while its running gradient went between two buffers (dh0 / dh1, dx0 / dx1): one
+    [N][H] and one [N][4] array more.  A library built from such a revision needs this to turn a chunk size into a knob value."""
+    return pt_floats_per_mol(N, H, L, F1, K) + N * H + 4 * N
 
 
 def et_floats_per_mol(N, H, L, S, F, A):
-    """csrc/edm_train_host.inc: et_floats_per_mol."""
+    """csrc/edm_train_host.inc: et_carve."""
     E, F1, D = N * N, F + 1, 3 + F
     return ((L * (S + 1) + 1) * N * H + (L + 1) * N * 4 + N * F1 + N * D + E * (A // 2) + E * A + 8 * E + 2 * E + 9 * N * H + 4 * N
             + N * F1 + 6 * E * H + 5 * E)
 
 
-def floats_per_mol(case):
+def shape_of(case):
+    """-> (net, N, H, L, S, F, K, A): the arguments of gaudi_host_train_floats_per_mol for a case (net 0: predictor, 1: EDM)."""
     F = synth.num_node_features(case.dataset)
     if case.net == "pred":
-        return pt_floats_per_mol(case.N, case.pred["nf"], case.pred["n_layers"], F + 1, case.K)
+        return 0, case.N, case.pred["nf"], case.pred["n_layers"], 1, F, case.K, 2
     e = case.edm
-    return et_floats_per_mol(case.N, e["nf"], e["n_layers"], e.get("inv_sublayers", 1), F, 24 if e.get("sin_embedding") else 2)
+    return 1, case.N, e["nf"], e["n_layers"], e.get("inv_sublayers", 1), F, case.K, 24 if e.get("sin_embedding") else 2
+
+
+def floats_per_mol(case):
+    net, N, H, L, S, F, K, A = shape_of(case)
+    return pt_floats_per_mol(N, H, L, F + 1, K) if net == 0 else et_floats_per_mol(N, H, L, S, F, A)
 
 
 def chunk_of(case, kb):
