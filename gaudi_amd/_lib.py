@@ -78,6 +78,7 @@ BONDS_MAX_ATOMS, BONDS_MAX_HEAVY, BONDS_MAX_BONDS, BONDS_MAX_CHARGED = 384, 192,
 (BONDS_OK, BONDS_NO_STRUCTURE, BONDS_CAPPED, BONDS_NOT_CONNECTED, BONDS_BAD_VALENCE, BONDS_BAD_INPUT, BONDS_OVERFLOW,
  BONDS_EMPTY, BONDS_GAVE_UP) = range(9)
 
+FP_BINS = (256, 512, 1024)  # include/gaudi_hip.h: gaudi_circular_fingerprint
 # include/gaudi_hip.h: GAUDI_CANON_*
 CANON_MAX_ATOMS, CANON_MAX_HEAVY, CANON_MAX_BONDS, CANON_MAX_DEGREE, CANON_MAX_NODES, CANON_MAX_DEPTH = 384, 192, 384, 8, 4096, 16
 CANON_OK, CANON_GAVE_UP, CANON_BAD_INPUT, CANON_OVERFLOW, CANON_EMPTY = range(5)
@@ -85,6 +86,7 @@ CANON_OK, CANON_GAVE_UP, CANON_BAD_INPUT, CANON_OVERFLOW, CANON_EMPTY = range(5)
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
 DP = C.POINTER(C.c_double)
+U8P = C.POINTER(C.c_uint8)
 
 
 class TargetSpec(C.Structure):
@@ -143,6 +145,15 @@ EXPORTS = {
     "gaudi_canon_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_host_canonical_order": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, IP, IP, IP,
                                              C.POINTER(C.c_uint8), IP, C.POINTER(C.c_uint16), IP, IP]),
+    "gaudi_circular_fingerprint": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, IP, C.c_int,
+                                             C.c_int, U8P, IP, IP]),
+    "gaudi_host_circular_fingerprint": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP, IP, IP, IP, C.c_int,
+                                                  C.c_int, U8P, IP, IP]),
+    "gaudi_fp_library_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P]),
+    "gaudi_fp_nearest": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, U8P, C.c_int, IP, IP, IP]),
+    "gaudi_fp_common": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, U8P, IP]),
+    "gaudi_host_fp_nearest": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, U8P, C.c_int, IP, IP, IP]),
+    "gaudi_fp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -218,6 +229,8 @@ _ATOMS_EXPORTS = ("gaudi_rings_to_atoms", "gaudi_atoms_profile_get")  # ... and 
 _RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and the way back, atoms -> graph of rings
 _BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bond orders / formal charges
 _CANON_EXPORTS = ("gaudi_canonical_order", "gaudi_canon_profile_get")  # ... and the canonical numbering
+_FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_nearest", "gaudi_fp_common",
+               "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -246,7 +259,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -357,6 +370,58 @@ def host_canonical_order(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds)
     rc = lib.gaudi_host_canonical_order(*canon_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_canonical_order failed ({rc})")
+    return out
+
+
+def fp_outputs(B: int, n_bins: int) -> dict:
+    """The three output arrays of gaudi_circular_fingerprint / gaudi_host_circular_fingerprint, in argument order."""
+    return dict(fp=np.zeros((B, n_bins), np.uint8), total=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
+
+
+def fp_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, radius, n_bins, out):
+    """The arguments both entry points share."""
+    for a in (elem, n_atoms, bonds, n_bonds):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    ip = lambda a: a.ctypes.data_as(IP)
+    return (int(n_elems), int(h_elem), int(c_elem), B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), int(radius),
+            int(n_bins), out["fp"].ctypes.data_as(U8P), ip(out["total"]), ip(out["status"]))
+
+
+def host_circular_fingerprint(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, radius=2, n_bins=1024) -> dict:
+    """gaudi_host_circular_fingerprint (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = fp_outputs(elem.shape[0], n_bins if n_bins in FP_BINS else 1)
+    rc = lib.gaudi_host_circular_fingerprint(*fp_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, radius, n_bins, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_circular_fingerprint failed ({rc})")
+    return out
+
+
+def fp_rows(a) -> np.ndarray:
+    """Fingerprint rows as the entry points read them: uint8 [rows, n_bins], contiguous."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    if a.ndim != 2:
+        raise GaudiError(f"fingerprints must be [rows, n_bins], got shape {a.shape}")
+    return a
+
+
+def nearest_outputs(B: int, k: int) -> dict:
+    """The three output arrays of gaudi_fp_nearest / gaudi_host_fp_nearest, in argument order."""
+    k = max(int(k), 1)
+    return dict(idx=np.zeros((B, k), np.int32), common=np.zeros((B, k), np.int32), union=np.zeros((B, k), np.int32))
+
+
+def host_fp_nearest(q, lib_rows, k=1) -> dict:
+    """gaudi_host_fp_nearest (needs no device): plain loops with the kernels' comparison function.  Test surface only."""
+    lib = load_library()
+    q, lib_rows = fp_rows(q), fp_rows(lib_rows)
+    out = nearest_outputs(q.shape[0], k)
+    rc = lib.gaudi_host_fp_nearest(q.shape[1], q.shape[0], q.ctypes.data_as(U8P), lib_rows.shape[0], lib_rows.ctypes.data_as(U8P),
+                                   int(k), *(out[n].ctypes.data_as(IP) for n in ("idx", "common", "union")))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_fp_nearest failed ({rc})")
     return out
 
 

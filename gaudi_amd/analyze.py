@@ -167,7 +167,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
-                                exact=False, train_keys=None):
+                                exact=False, train_keys=None, similarity=False, train_library=None):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -190,8 +190,17 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     A built molecule without a key (the bounded search gave up) falls back to ``("fp", fingerprint)``.  ``mol_unique*`` count
     these keys, ``mol_novel*`` compare them with ``train_keys`` (a collection of ``bytes``; ``train_fingerprints`` is not used),
     and the dict gains ``canon_keys`` (one per molecule, None where not built), ``mol_undecided`` = built molecules without a
-    key / built molecules and, with ``valence_check``, ``smiles`` (one string or None per molecule)."""
+    key / built molecules and, with ``valence_check``, ``smiles`` (one string or None per molecule).
+
+    similarity: one more launch (gaudi_circular_fingerprint) gives every built molecule its circular count
+    fingerprint, and the dict gains ``diversity`` = 1 - the mean pairwise similarity of the built molecules (0.0 with fewer than
+    two).  With ``train_library`` (a gaudi_amd.similarity.Library of fingerprints of radius 2, resident on the engine used here)
+    also ``nearest_train_similarity`` and ``nearest_train_index``, one per molecule: how close the nearest training molecule is
+    and which it is, 0.0 and -1 where the molecule was not built.  Membership (``train_keys``) says novel or not; this says how
+    novel."""
     from .gor2goa import rings_to_atoms
+    if train_library is not None and not similarity:
+        raise ValueError("train_library needs similarity=True")
     # (the keyword only when asked for: a rings_to_atoms stand-in with the earlier signature, as tests/test_gor2goa_cpu.py passes, keeps working)
     extra = {"bond_orders": True} if valence_check else {}
     if exact:
@@ -230,4 +239,22 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         d["mol_unique_valid"] = len(set(valid_keys)) / float(n_valid) if n_valid else 0.0
         if train is not None:
             d["mol_novel_valid"] = sum(k not in train for k in valid_keys) / float(n_valid) if n_valid else 0.0
+    if similarity:
+        d.update(_similarity(recs, built, dataset, _engine(engine), train_library))
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
+
+
+def _similarity(recs, built, dataset, engine, train_library=None) -> dict:
+    """``diversity`` of the built records and, with a library, their nearest training molecules (analyze_atoms_for_molecules)."""
+    from .similarity import fingerprints, internal_diversity
+    n_bins = 1024 if train_library is None else train_library.n_bins
+    fp = fingerprints(recs, dataset, n_bins=n_bins, engine=engine)
+    out = {"diversity": internal_diversity(fp["fp"], fp["total"], engine=engine)}
+    if train_library is not None:
+        if train_library.engine is not engine:
+            raise GaudiError("train_library is resident on another engine than the one this call runs on")
+        idx, sim = train_library.nearest(fp["fp"], 1)
+        ok = np.array(built, dtype=bool)
+        out["nearest_train_similarity"] = np.where(ok, sim[:, 0], 0.0)
+        out["nearest_train_index"] = np.where(ok, idx[:, 0], -1)
+    return out

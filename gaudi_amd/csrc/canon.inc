@@ -158,14 +158,17 @@ __host__ __device__ inline void canon_code(CanonSmem& s, const unsigned char* co
   rw_fence();
 }
 
-// One molecule.  `s` is this wave's (host: this call's) working state; every `break` is lane-uniform.
-__host__ __device__ inline void canonical_order(const CanonParams& P, CanonSmem& s, int b, int lane) {
+// The labelled graph of molecule b into s (bl, hv, hidx, adj, label): the inputs read and checked.  Only the input fields of P are
+// used, so fp.inc reads its molecules through this too.  -> GAUDI_CANON_OK with H vertices and E edges, or the status that refuses
+// the molecule; every exit is lane-uniform.
+__host__ __device__ inline int canon_graph(const CanonParams& P, CanonSmem& s, int b, int lane, int& H_out, int& E_out) {
   const int A = P.A, M = P.M;
   const int n = P.n_atoms[b], m = P.n_bonds[b];
   const int* eb = P.elem + (size_t)b * A;
   const int* bb = P.bonds + (size_t)b * M * 2;
-  int status = GAUDI_CANON_OK, nodes = 0;
-
+  int status = GAUDI_CANON_OK;
+  H_out = 0;
+  E_out = 0;
   do {
     if (n <= 0) { status = GAUDI_CANON_EMPTY; break; }
     if (n > A || m < 0 || m > M) { status = GAUDI_CANON_BAD_INPUT; break; }  // (the entry points refuse these)
@@ -239,8 +242,21 @@ __host__ __device__ inline void canonical_order(const CanonParams& P, CanonSmem&
     rw_fence();
     if (rw_any(bad)) { status = GAUDI_CANON_BAD_INPUT; break; }
     if (rw_any(over)) { status = GAUDI_CANON_OVERFLOW; break; }
-    const int E = E2 / 2;
+    H_out = H;
+    E_out = E2 / 2;
+  } while (false);
+  return status;
+}
 
+// One molecule.  `s` is this wave's (host: this call's) working state; every `break` is lane-uniform.
+__host__ __device__ inline void canonical_order(const CanonParams& P, CanonSmem& s, int b, int lane) {
+  const int A = P.A, M = P.M;
+  const int n = P.n_atoms[b];
+  int nodes = 0, H = 0, E = 0;
+  int status = canon_graph(P, s, b, lane, H, E);
+
+  do {
+    if (status != GAUDI_CANON_OK) break;
     // ---- 3. the first colouring: the rank of the label
     for (int v = lane; v < H; v += kRwLanes) {
       const int lv = s.label[v];

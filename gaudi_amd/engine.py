@@ -814,6 +814,55 @@ class Engine:
         self._check(rc, "gaudi_canonical_order")
         return out
 
+    def fp_profile_get(self):
+        """(calls, summed milliseconds of their kernels) of the fingerprint / nearest / common calls since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_fp_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_fp_profile_get")
+        return n.value, ms.value
+
+    def circular_fingerprint(self, n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, radius=2, n_bins=1024):
+        """gaudi_circular_fingerprint on packed arrays (as bond_orders takes them) -> dict of the raw output arrays (fp [B,n_bins]
+        uint8, total [B], status [B]); gaudi_amd.similarity.fingerprints is the interface on top."""
+        if n_bins not in _lib.FP_BINS:
+            raise GaudiError(f"n_bins must be one of {_lib.FP_BINS}, got {n_bins}")
+        out = _lib.fp_outputs(elem.shape[0], n_bins)
+        rc = self.lib.gaudi_circular_fingerprint(self.h, *_lib.fp_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, radius,
+                                                                       n_bins, out))
+        self._check(rc, "gaudi_circular_fingerprint")
+        return out
+
+    def fp_library_set(self, fp=None):
+        """gaudi_fp_library_set: keep fp [M,n_bins] uint8 on the device as THE resident library of this engine (None: free it)."""
+        if fp is None:
+            self._check(self.lib.gaudi_fp_library_set(self.h, 0, 0, None), "gaudi_fp_library_set")
+            return
+        fp = _lib.fp_rows(fp)
+        self._check(self.lib.gaudi_fp_library_set(self.h, fp.shape[1], fp.shape[0], fp.ctypes.data_as(_lib.U8P)), "gaudi_fp_library_set")
+
+    def fp_nearest(self, q, lib=None, k=1, M=None):
+        """gaudi_fp_nearest: q [B,n_bins] against lib [M,n_bins], or against the resident library of M rows when lib is None ->
+        dict(idx, common, union), each int32 [B,k]."""
+        q = _lib.fp_rows(q)
+        lib = None if lib is None else _lib.fp_rows(lib)
+        out = _lib.nearest_outputs(q.shape[0], k)
+        rc = self.lib.gaudi_fp_nearest(self.h, q.shape[1], q.shape[0], q.ctypes.data_as(_lib.U8P), int(M if lib is None else lib.shape[0]),
+                                       None if lib is None else lib.ctypes.data_as(_lib.U8P), int(k),
+                                       *(out[n].ctypes.data_as(_lib.IP) for n in ("idx", "common", "union")))
+        self._check(rc, "gaudi_fp_nearest")
+        return out
+
+    def fp_common(self, q, lib=None, M=None):
+        """gaudi_fp_common: the sum of the byte-wise minimum for every pair -> int32 [B,M]."""
+        q = _lib.fp_rows(q)
+        lib = None if lib is None else _lib.fp_rows(lib)
+        M = int(M if lib is None else lib.shape[0])
+        out = np.zeros((q.shape[0], max(M, 0)), np.int32)
+        rc = self.lib.gaudi_fp_common(self.h, q.shape[1], q.shape[0], q.ctypes.data_as(_lib.U8P), M,
+                                      None if lib is None else lib.ctypes.data_as(_lib.U8P), out.ctypes.data_as(_lib.IP))
+        self._check(rc, "gaudi_fp_common")
+        return out
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -575,6 +575,41 @@ int gaudi_canonical_order(gaudi_handle* h, int n_elems, int h_elem, int c_elem, 
 /* Number of gaudi_canonical_order launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_canon_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Circular count fingerprints and their similarity (csrc/fp.inc). ----
+ * How ALIKE two built molecules are, where the canonical code says whether they are the same.  The graph is the one of
+ * gaudi_canonical_order: label(v) = element * 8 + H count, deg(v) = non-hydrogen neighbours; bond orders are no part of it, and a
+ * molecule has the same fingerprint with and without placed hydrogens.  With uint32_t arithmetic that wraps and
+ *   mix(x):  x ^= x >> 16;  x *= 0x85ebca6b;  x ^= x >> 13;  x *= 0xc2b2ae35;  x ^= x >> 16
+ *   id_0(v) = mix(0x9e3779b9 + label(v) * 16 + deg(v))
+ *   id_r(v), r = 1..radius:  h = mix(r);  h = mix(h ^ id_{r-1}(v));  for the neighbours' id_{r-1} in ascending order: h = mix(h ^ id)
+ * the features are the multiset { id_r(v) : v, r = 0..radius }, fp[bin] = min(255, features with (id & (n_bins - 1)) == bin) and
+ * total = the sum of the stored bytes.  radius 0..3, n_bins 256, 512 or 1024 (GAUDI_E_INVALID otherwise).  Inputs as
+ * gaudi_canonical_order takes them; one 64-lane wave per molecule, integer arithmetic only, one launch.  fp_out [B][n_bins],
+ * total_out [B], status_out [B]: GAUDI_CANON_OK, or GAUDI_CANON_BAD_INPUT / OVERFLOW / EMPTY with their meaning there, a zero row
+ * and total 0.  The outputs are a function of the molecule's own arrays (never of its place in the batch) and bit for bit what
+ * gaudi_host_circular_fingerprint returns.  A molecule that fails never disturbs the others of the batch. */
+int gaudi_circular_fingerprint(gaudi_handle* h, int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                               const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int radius, int n_bins,
+                               uint8_t* fp_out, int32_t* total_out, int32_t* status_out);
+/* Similarity of rows a, b: common = sum min(a_i, b_i), union = total_a + total_b - common, similarity = common / union, and 0 when
+ * union = 0.  The entry points return the two INTEGERS; the caller forms the quotient.  The total order of library rows for one
+ * query, used everywhere: x is ahead of y when common_x * union_y > common_y * union_x in 64-bit integers, a union of 0 counting
+ * as similarity 0; equal similarity goes to the smaller library index.
+ * gaudi_fp_library_set keeps lib [M][n_bins] on the device, replacing the previous library; M = 0 frees it. */
+int gaudi_fp_library_set(gaudi_handle* h, int n_bins, int M, const uint8_t* lib);
+/* The k (1..16) library rows most similar to each of the B queries q [B][n_bins], in that order.  lib [M][n_bins], or NULL for the
+ * resident library (then M and n_bins must be its; GAUDI_E_STATE without one).  idx_out, common_out, union_out: each [B][k];
+ * entries beyond M rows are -1, 0, 0.  The result does not depend on how the library is split over workgroups (GAUDI_FP_SPLITS,
+ * read per call, forces the number of splits: a test knob) nor on the query's place in the batch, and is exactly what
+ * gaudi_host_fp_nearest returns. */
+int gaudi_fp_nearest(gaudi_handle* h, int n_bins, int B, const uint8_t* q, int M, const uint8_t* lib, int k, int32_t* idx_out,
+                     int32_t* common_out, int32_t* union_out);
+/* common_out [B][M] for every pair; B * M <= 2^28 (GAUDI_E_CAPACITY beyond).  lib as for gaudi_fp_nearest. */
+int gaudi_fp_common(gaudi_handle* h, int n_bins, int B, const uint8_t* q, int M, const uint8_t* lib, int32_t* common_out);
+/* Number of fingerprint / nearest / common calls since gaudi_profile_reset(h, 1) and the summed duration of their kernels (HIP
+ * events; uploads and downloads are outside). */
+int gaudi_fp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -603,6 +638,15 @@ int gaudi_host_canonical_order(int n_elems, int h_elem, int c_elem, int B, int A
                                const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int32_t* rank_out,
                                int32_t* n_heavy_out, uint8_t* label_out, int32_t* n_hbonds_out, uint16_t* cbonds_out,
                                int32_t* nodes_out, int32_t* status_out);
+/* gaudi_circular_fingerprint without a handle: the same source text (csrc/fp.inc: circular_fingerprint) compiled for the host and
+ * run serially.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_circular_fingerprint(int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                                    const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int radius, int n_bins,
+                                    uint8_t* fp_out, int32_t* total_out, int32_t* status_out);
+/* gaudi_fp_nearest without a handle: plain loops over every pair with the same comparison function (csrc/fp.inc: fp_ahead).  Test
+ * surface for the CPU suite, not a CPU fallback. */
+int gaudi_host_fp_nearest(int n_bins, int B, const uint8_t* q, int M, const uint8_t* lib, int k, int32_t* idx_out,
+                          int32_t* common_out, int32_t* union_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),
