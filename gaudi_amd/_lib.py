@@ -82,6 +82,9 @@ FP_BINS = (256, 512, 1024)  # include/gaudi_hip.h: gaudi_circular_fingerprint
 # include/gaudi_hip.h: GAUDI_CANON_*
 CANON_MAX_ATOMS, CANON_MAX_HEAVY, CANON_MAX_BONDS, CANON_MAX_DEGREE, CANON_MAX_NODES, CANON_MAX_DEPTH = 384, 192, 384, 8, 4096, 16
 CANON_OK, CANON_GAVE_UP, CANON_BAD_INPUT, CANON_OVERFLOW, CANON_EMPTY = range(5)
+# include/gaudi_hip.h: GAUDI_SUB_*
+SUB_MAX_QUERY, SUB_MAX_PATTERNS, SUB_MAX_STEPS, SUB_H_EXACT, SUB_CLOSED = 32, 64, 8192, 1, 2
+SUB_OK, SUB_GAVE_UP, SUB_BAD_INPUT, SUB_OVERFLOW, SUB_EMPTY, SUB_BAD_PATTERN = range(6)
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
@@ -154,6 +157,10 @@ EXPORTS = {
     "gaudi_fp_common": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, U8P, IP]),
     "gaudi_host_fp_nearest": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, U8P, C.c_int, IP, IP, IP]),
     "gaudi_fp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_substructure_search": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [IP] * 4 + [C.c_int] * 3 + [IP] * 5 + [IP, IP, U8P, IP, IP]),
+    "gaudi_host_substructure_search": (C.c_int, [C.c_int] * 6 + [IP] * 4 + [C.c_int] * 3 + [IP] * 5 + [IP, IP, U8P, IP, IP]),
+    "gaudi_host_substructure_root_steps": (C.c_int, [C.c_int]),
+    "gaudi_substructure_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -231,6 +238,7 @@ _BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bon
 _CANON_EXPORTS = ("gaudi_canonical_order", "gaudi_canon_profile_get")  # ... and the canonical numbering
 _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_nearest", "gaudi_fp_common",
                "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
+_SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -259,7 +267,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -423,6 +431,44 @@ def host_fp_nearest(q, lib_rows, k=1) -> dict:
     if rc != 0:
         raise GaudiError(f"gaudi_host_fp_nearest failed ({rc})")
     return out
+
+
+def sub_outputs(B: int, P: int, A: int, QA: int) -> dict:
+    """The five output arrays of gaudi_substructure_search / gaudi_host_substructure_search, in argument order."""
+    return dict(count=np.zeros((B, P), np.int32), first=np.full((B, P, QA), -1, np.int32), covered=np.zeros((B, P, A), np.uint8),
+                steps=np.zeros((B, P), np.int32), status=np.zeros((B, P), np.int32))
+
+
+def sub_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, p_elem, p_n_atoms, p_bonds, p_n_bonds, p_flags, out):
+    """The arguments both entry points share: the molecules, then the patterns in the same layout, then the outputs."""
+    for a in (elem, n_atoms, bonds, n_bonds, p_elem, p_n_atoms, p_bonds, p_n_bonds, p_flags):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    P, QA, QM = p_elem.shape[0], p_elem.shape[1], p_bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert p_elem.shape == (P, QA) and p_bonds.shape == (P, QM, 2) and p_n_atoms.shape == (P,) and p_n_bonds.shape == (P,)
+    assert p_flags.shape == (P,) and out["count"].shape == (B, P) and out["first"].shape == (B, P, QA) and out["covered"].shape == (B, P, A)
+    ip = lambda a: a.ctypes.data_as(IP)
+    return (int(n_elems), int(h_elem), int(c_elem), B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), P, QA, QM, ip(p_elem),
+            ip(p_n_atoms), ip(p_bonds), ip(p_n_bonds), ip(p_flags), ip(out["count"]), ip(out["first"]),
+            out["covered"].ctypes.data_as(U8P), ip(out["steps"]), ip(out["status"]))
+
+
+def host_substructure_search(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, p_elem, p_n_atoms, p_bonds, p_n_bonds,
+                             p_flags) -> dict:
+    """gaudi_host_substructure_search (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = sub_outputs(elem.shape[0], p_elem.shape[0], elem.shape[1], p_elem.shape[1])
+    rc = lib.gaudi_host_substructure_search(*sub_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, p_elem, p_n_atoms,
+                                                      p_bonds, p_n_bonds, p_flags, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_substructure_search failed ({rc})")
+    return out
+
+
+def host_substructure_root_steps(reset=False) -> int:
+    """gaudi_host_substructure_root_steps: the largest per-root step count of the host build since the last reset."""
+    return int(load_library().gaudi_host_substructure_root_steps(int(bool(reset))))
 
 
 def fptr(a: np.ndarray | None):

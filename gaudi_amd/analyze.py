@@ -167,7 +167,8 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
-                                exact=False, train_keys=None, similarity=False, train_library=None):
+                                exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
+                                pattern_options=None):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -197,7 +198,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     two).  With ``train_library`` (a gaudi_amd.similarity.Library of fingerprints of radius 2, resident on the engine used here)
     also ``nearest_train_similarity`` and ``nearest_train_index``, one per molecule: how close the nearest training molecule is
     and which it is, 0.0 and -1 where the molecule was not built.  Membership (``train_keys``) says novel or not; this says how
-    novel."""
+    novel.
+
+    patterns: a list of patterns for gaudi_amd.substructure.search (one more launch per 64 patterns, and
+    one for their symmetry), with ``pattern_options`` = its keywords ``hydrogens`` / ``closed``.  The dict gains ``pattern_hits``
+    bool [n,P] (rows of unbuilt molecules False) and ``pattern_fraction`` [P] = built molecules that contain the pattern / built
+    molecules (0.0 when none was built).  With ``patterns=None`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -241,6 +247,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
             d["mol_novel_valid"] = sum(k not in train for k in valid_keys) / float(n_valid) if n_valid else 0.0
     if similarity:
         d.update(_similarity(recs, built, dataset, _engine(engine), train_library))
+    if patterns is not None:
+        from .substructure import search
+        hits = search(recs, patterns, dataset, engine=_engine(engine), **(pattern_options or {}))["hit"]
+        hits = hits & np.asarray(built, bool)[:, None]
+        d["pattern_hits"] = hits
+        d["pattern_fraction"] = hits.sum(0) / float(n_built) if n_built else np.zeros(hits.shape[1])
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

@@ -832,6 +832,23 @@ class Engine:
         self._check(rc, "gaudi_circular_fingerprint")
         return out
 
+    def substructure_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_substructure_search since profile_reset(True)."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_substructure_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_substructure_profile_get")
+        return int(n.value), float(ms.value)
+
+    def substructure_search(self, n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, p_elem, p_n_atoms, p_bonds, p_n_bonds,
+                            p_flags):
+        """gaudi_substructure_search on packed arrays: the molecules as bond_orders takes them, at most 64 patterns in the same
+        layout and their flags -> dict of the raw output arrays (count [B,P] int32, first [B,P,QA] int32, covered [B,P,A] uint8,
+        steps [B,P] int32, status [B,P] int32).  gaudi_amd.substructure.search is the interface on top."""
+        out = _lib.sub_outputs(elem.shape[0], p_elem.shape[0], elem.shape[1], p_elem.shape[1])
+        rc = self.lib.gaudi_substructure_search(self.h, *_lib.sub_args(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bonds, p_elem,
+                                                                       p_n_atoms, p_bonds, p_n_bonds, p_flags, out))
+        self._check(rc, "gaudi_substructure_search")
+        return out
+
     def fp_library_set(self, fp=None):
         """gaudi_fp_library_set: keep fp [M,n_bins] uint8 on the device as THE resident library of this engine (None: free it)."""
         if fp is None:

@@ -53,7 +53,7 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 
 
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
-           valence_check=False, exact=False, similarity=False, train_library=None):
+           valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -66,7 +66,10 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     search gave up) instead of fingerprints, and with valence_check the dict gains ``smiles``.  similarity (with with_atoms): the
     dict gains ``diversity`` -- what a stronger guidance scale costs when the batch collapses onto a few skeletons -- and, with
     ``train_library`` (a gaudi_amd.similarity.Library on the model's engine), ``nearest_train_similarity`` and
-    ``nearest_train_index`` per molecule, as analyze_atoms_for_molecules returns them."""
+    ``nearest_train_index`` per molecule, as analyze_atoms_for_molecules returns them.  patterns (with with_atoms): a list of
+    patterns for gaudi_amd.substructure.search (``pattern_options``: its ``hydrogens`` / ``closed``), and the dict gains
+    ``contains`` bool [B,P] -- which designed molecules hold which motif, False where the molecule was not built.  With
+    ``patterns=None`` no search is launched."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
@@ -76,11 +79,12 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-                     with_atoms, valence_check, exact, similarity, train_library)
+                     with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
-                 n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None):
+                 n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None, patterns=None,
+                 pattern_options=None):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -89,7 +93,8 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     ValueTargets with shared ([K]) arrays (each with its own centres / curvatures / scale; ``scale`` multiplies them all).
     The guidance window is one per call: settings whose windows differ are refused.  Returns one design()-shaped dict per setting, evaluated
     as design() does; ``seconds`` is the ONE call's time, ``molecules_per_second`` the whole call's rate.  similarity /
-    train_library: as design takes them; every setting gets its own ``diversity``."""
+    train_library: as design takes them; every setting gets its own ``diversity``.  patterns / pattern_options: as design takes
+    them; every setting gets its own ``contains``."""
     from .models_edm import ValueTarget
     model.eval()
     cond_predictor.eval()
@@ -139,19 +144,21 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     for j, (t, mult) in enumerate(settings):
         lo, hi = j * bs, (j + 1) * bs
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
-                      em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library)
+                      em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library, patterns,
+                      pattern_options)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
 
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
-           prop_dist=None, with_atoms=False, valence_check=False, similarity=False):
+           prop_dist=None, with_atoms=False, valence_check=False, similarity=False, patterns=None, pattern_options=None):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought.  similarity (with with_atoms): the seeds go
     through rings_to_atoms as well, and the dict gains ``diversity`` and ``similarity_to_seed`` [B], the similarity of every
-    refined molecule with its own seed (0.0 where either was not built): how far the refinement moved."""
+    refined molecule with its own seed (0.0 where either was not built): how far the refinement moved.  patterns /
+    pattern_options: as design takes them, on the refined molecules."""
     model.eval()
     cond_predictor.eval()
     bs, n_nodes = _to_numpy(x).shape[0], _to_numpy(x).shape[1]
@@ -164,7 +171,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     seconds = time() - start_time
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
-                    seconds, with_atoms, valence_check, False, similarity)
+                    seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     if similarity:
         from .similarity import fingerprints, rowwise_similarity
@@ -175,7 +182,8 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     return out
 
 
-def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None):
+def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None,
+           patterns=None, pattern_options=None):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -201,12 +209,18 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
     if similarity:
         from .analyze import _similarity
         out.update(_similarity(recs, [r["status"] == 0 for r in recs], dataset, engine, train_library))
+    if patterns is not None:
+        from .substructure import search
+        out["contains"] = search(recs, patterns, dataset, engine=engine, **(pattern_options or {}))["hit"]
     return out
 
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-              with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None):
+              with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None, patterns=None,
+              pattern_options=None):
     """The part of design after sampling (generation_guidance.py:96-184)."""
+    if patterns is not None and not with_atoms:
+        raise ValueError("patterns need with_atoms=True")
     if (similarity or train_library is not None) and not with_atoms:
         raise ValueError("similarity / train_library need with_atoms=True")
     if train_library is not None and not similarity:
@@ -228,7 +242,8 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
     out = dict(stability=stability_dict, best_stable=order[stable[order]], x=x, one_hot=one_hot, node_mask=node_mask, edge_mask=edge_mask, target_function_values=_like_ref(tvals),
                pred=_like_ref(pred), best=order, seconds=seconds, molecules_per_second=x.shape[0] / seconds)
     if with_atoms:
-        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library))
+        out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library,
+                          patterns, pattern_options))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

@@ -20,6 +20,8 @@ strings (gor2goa.py:264-324).  The fingerprint is a hash: equal fingerprints do 
 ``canon_key`` values do.  There is no CPU implementation behind these functions: without the HIP library they raise GaudiError."""
 from __future__ import annotations
 
+import re
+
 import numpy as np
 
 from ._lib import (ATOMS_FINGERPRINT, ATOMS_MAX_ATOMS, ATOMS_MAX_BONDS, ATOMS_PLACE_H, BONDS_EMPTY, CANON_GAVE_UP, CANON_OK,
@@ -450,3 +452,120 @@ def write_smiles(path_or_file, records, dataset="cata"):
         if close:
             f.close()
     return n
+
+
+_READ_BRACKET = re.compile(r"\[([A-Z][a-z]?)(H\d*)?([+-]\d*)?\]")
+
+
+def read_smiles(text, dataset="cata"):
+    """The inverse of smiles() for the dialect that function writes -> (atom_types [n], bonds [m,2], orders [m], charges [n]): the
+    heavy atoms in the order they are written, then their hydrogens -- those a bare B C N O S implies for the sum of its bond
+    orders and those a bracket atom names -- in ascending parent order, every one an atom of its own with a single bond.
+    Understood: upper-case bare B C N O S, bracket atoms [Sym], [SymH], [SymHn] with an optional charge (+, -, +n, -n), "=",
+    branches, ring closures 1..9 and %nn, "." between components.  Lower-case aromatic atoms, stereo marks (@ / \\), isotopes, "#",
+    "-", ":" and anything else raise GaudiError naming the position."""
+    names = atoms_list(dataset)
+
+    def bad(i, what):
+        raise GaudiError(f"read_smiles: {what} at position {i} of {text!r}")
+
+    syms, given_h, charges, heavy_bonds, bare = [], [], [], [], []
+    prev, pending, stack, ring = -1, 1, [], {}
+
+    def atom(i, sym, n_h, charge):
+        nonlocal prev, pending
+        if sym not in names or sym == "H":
+            bad(i, f"element {sym!r} outside the {dataset} atom list")
+        syms.append(sym)
+        given_h.append(n_h)
+        charges.append(charge)
+        a = len(syms) - 1
+        if prev >= 0:
+            heavy_bonds.append((prev, a, pending))
+        elif pending != 1:
+            bad(i, "a bond symbol with no atom before it")
+        prev, pending = a, 1
+
+    def closure(i, k):
+        nonlocal pending
+        if prev < 0:
+            bad(i, "a ring closure with no atom before it")
+        if k in ring:
+            j = ring.pop(k)
+            if j == prev or any({a, b} == {j, prev} for a, b, _ in heavy_bonds):
+                bad(i, "a ring closure that repeats a bond or joins an atom to itself")
+            heavy_bonds.append((j, prev, pending))
+        else:
+            if pending != 1:
+                bad(i, "'=' before an opening ring digit (the dialect writes it before the closing one)")
+            ring[k] = prev
+        pending = 1
+
+    i = 0
+    while i < len(text):
+        ch = text[i]
+        if ch == ".":
+            if stack or pending != 1:
+                bad(i, "'.' inside a branch or after a bond symbol")
+            prev = -1
+        elif ch == "(":
+            if prev < 0:
+                bad(i, "a branch with no atom before it")
+            stack.append(prev)
+        elif ch == ")":
+            if not stack or pending != 1:
+                bad(i, "an unmatched ')'")
+            prev = stack.pop()
+        elif ch == "=":
+            if pending != 1 or prev < 0:
+                bad(i, "a misplaced '='")
+            pending = 2
+        elif ch.isdigit():
+            if ch == "0":
+                bad(i, "ring closure 0")
+            closure(i, int(ch))
+        elif ch == "%":
+            if not text[i + 1:i + 3].isdigit() or len(text[i + 1:i + 3]) != 2 or int(text[i + 1:i + 3]) < 10:
+                bad(i, "'%' without two digits")
+            closure(i, int(text[i + 1:i + 3]))
+            i += 2
+        elif ch == "[":
+            m = _READ_BRACKET.match(text, i)
+            if not m:
+                bad(i, "a bracket atom outside [Sym], [SymHn], [SymHn+q]")
+            n_h = 0 if not m.group(2) else int(m.group(2)[1:] or 1)
+            q = 0 if not m.group(3) else int(m.group(3)[1:] or 1) * (1 if m.group(3)[0] == "+" else -1)
+            atom(i, m.group(1), n_h, q)
+            i = m.end() - 1
+        elif ch in _SMILES_VALENCES:
+            atom(i, ch, None, 0)
+            bare.append(prev)
+        elif ch.islower():
+            bad(i, f"lower-case (aromatic) atom {ch!r}")
+        elif ch in "@/\\":
+            bad(i, f"stereo mark {ch!r}")
+        else:
+            bad(i, f"unsupported character {ch!r}")
+        i += 1
+    if ring:
+        bad(len(text), f"ring closure {sorted(ring)[0]} never closed")
+    if stack or pending != 1:
+        bad(len(text), "an open branch or a trailing bond symbol")
+    total = [0] * len(syms)
+    for a, b, o in heavy_bonds:
+        total[a] += o
+        total[b] += o
+    for a in bare:
+        fit = [v for v in _SMILES_VALENCES[syms[a]] if v >= total[a]]
+        given_h[a] = fit[0] - total[a] if fit else 0
+    H = len(syms)
+    types = [names.index(s) for s in syms]
+    bonds, orders = [(a, b) for a, b, _ in heavy_bonds], [o for _, _, o in heavy_bonds]
+    for a in range(H):
+        for _ in range(given_h[a]):
+            bonds.append((a, len(types)))
+            orders.append(1)
+            types.append(names.index("H"))
+            charges.append(0)
+    return (np.array(types, np.int64), np.array(bonds, np.int64).reshape(-1, 2), np.array(orders, np.int64),
+            np.array(charges, np.int64))

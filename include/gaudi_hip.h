@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -610,6 +610,59 @@ int gaudi_fp_common(gaudi_handle* h, int n_bins, int B, const uint8_t* q, int M,
  * events; uploads and downloads are outside). */
 int gaudi_fp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Substructure search over graphs of atoms (csrc/sub.inc). ----
+ * Does a molecule contain a motif, where, and how often: what a SMARTS match without bond primitives answers.
+ * Graphs, on both sides, are the one of gaudi_canonical_order: vertices = the non-hydrogen atoms; a vertex carries its element and
+ * its H count (the listed H neighbours plus one for a carbon with exactly two bonds); edges = the bonds between non-hydrogen atoms,
+ * unlabelled.  Bond orders and charges are no part of it.
+ * A PATTERN is such a graph with 1..GAUDI_SUB_MAX_QUERY vertices, connected, given as (elem, bonds) arrays exactly as molecules
+ * are (p_elem [P][QA], p_n_atoms [P], p_bonds [P][QM][2], p_n_bonds [P]).  Anything else -- empty, no non-hydrogen atom, not
+ * connected, more than 32 vertices, n_atoms > QA or n_bonds > QM, a bad index or element, a self bond, a duplicate bond, more than
+ * 8 bonds at an atom, an unknown flag -- gives GAUDI_SUB_BAD_PATTERN in every cell of that pattern's column (whatever the molecule
+ * is) and never disturbs the other patterns.
+ * Per-pattern flags p_flags [P]: GAUDI_SUB_H_EXACT -- the target vertex's H count equals the pattern vertex's; GAUDI_SUB_CLOSED --
+ * the target vertex's heavy degree equals the pattern vertex's (nothing else is attached).  With neither only elements and edges
+ * count.
+ * An EMBEDDING is an injective map of pattern vertices to target vertices with equal elements, every pattern edge on a target edge
+ * and the flags holding at every vertex: a monomorphism, not an induced subgraph.
+ * Outputs per (molecule b, pattern p):
+ *   count_out [B][P]: the embeddings found.
+ *   first_out [B][P][QA] (or NULL: not wanted): the embedding that is lexicographically smallest when written as target ATOM indices
+ *     in the pattern's own atom order; -1 at pattern hydrogens and padding, and everywhere when count is 0.
+ *   covered_out [B][P][A] (or NULL): 1 for every target atom some embedding found uses.
+ *   steps_out [B][P]: candidate tests spent, summed over roots, saturating at 2^31 - 1.
+ *   status_out [B][P]: GAUDI_SUB_OK; GAUDI_SUB_GAVE_UP -- the budget ran out: count is a lower bound, first the smallest among
+ *     those found, covered a subset, and a count of 0 means undecided; GAUDI_SUB_BAD_INPUT / OVERFLOW / EMPTY with the meaning of
+ *     their GAUDI_CANON_* namesakes for the molecule; GAUDI_SUB_BAD_PATTERN.  Where the molecule or the pattern was refused the
+ *     other outputs are zero and -1.
+ * The budget is counted per ROOT (a target vertex tried as the image of the first pattern vertex of the match order; the test of
+ * the root itself is the first step): GAUDI_SUB_MAX_STEPS candidate tests.  A root that needs more is abandoned with what it found
+ * and the status becomes GAVE_UP.  The budget never depends on which lane ran the root, so the device and the host build cut a
+ * search at the same step and agree bit for bit even when they give up.  The match order is fixed per pattern by host code
+ * (csrc/sub.inc: sub_plan states the rule); count, first and covered do not depend on it when the status is OK.
+ * One 64-lane wave per molecule, integer arithmetic only, one launch.  P <= GAUDI_SUB_MAX_PATTERNS per call and B * P * max(A, QA)
+ * <= 2^31 (GAUDI_E_CAPACITY beyond).  The outputs are a function of the molecule's and the patterns' own arrays (never of the
+ * molecule's place in the batch) and bit for bit what gaudi_host_substructure_search returns. */
+#define GAUDI_SUB_MAX_QUERY 32      /* vertices of a pattern */
+#define GAUDI_SUB_MAX_PATTERNS 64   /* patterns of one call */
+#define GAUDI_SUB_MAX_STEPS 8192    /* candidate tests per root: DESIGN.md section 8k has the measurement behind it */
+#define GAUDI_SUB_H_EXACT 1
+#define GAUDI_SUB_CLOSED 2
+#define GAUDI_SUB_OK 0
+#define GAUDI_SUB_GAVE_UP 1
+#define GAUDI_SUB_BAD_INPUT 2
+#define GAUDI_SUB_OVERFLOW 3
+#define GAUDI_SUB_EMPTY 4
+#define GAUDI_SUB_BAD_PATTERN 5
+int gaudi_substructure_search(gaudi_handle* h, int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                              const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int P, int QA, int QM,
+                              const int32_t* p_elem, const int32_t* p_n_atoms, const int32_t* p_bonds, const int32_t* p_n_bonds,
+                              const int32_t* p_flags, int32_t* count_out, int32_t* first_out, uint8_t* covered_out,
+                              int32_t* steps_out, int32_t* status_out);
+/* Number of gaudi_substructure_search launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events; uploads and
+ * downloads are outside). */
+int gaudi_substructure_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
@@ -643,6 +696,16 @@ int gaudi_host_canonical_order(int n_elems, int h_elem, int c_elem, int B, int A
 int gaudi_host_circular_fingerprint(int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
                                     const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int radius, int n_bins,
                                     uint8_t* fp_out, int32_t* total_out, int32_t* status_out);
+/* gaudi_substructure_search without a handle: the same source text (csrc/sub.inc: substructure_search) compiled for the host, every
+ * root walked in turn through the same step function.  Test surface for the CPU suite, not a CPU fallback. */
+int gaudi_host_substructure_search(int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem,
+                                   const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int P, int QA, int QM,
+                                   const int32_t* p_elem, const int32_t* p_n_atoms, const int32_t* p_bonds,
+                                   const int32_t* p_n_bonds, const int32_t* p_flags, int32_t* count_out, int32_t* first_out,
+                                   uint8_t* covered_out, int32_t* steps_out, int32_t* status_out);
+/* The largest number of candidate tests ONE root took in gaudi_host_substructure_search since the last call with reset != 0: the
+ * figure GAUDI_SUB_MAX_STEPS is sized with.  A process-wide counter, not thread-safe: tooling only. */
+int gaudi_host_substructure_root_steps(int reset);
 /* gaudi_fp_nearest without a handle: plain loops over every pair with the same comparison function (csrc/fp.inc: fp_ahead).  Test
  * surface for the CPU suite, not a CPU fallback. */
 int gaudi_host_fp_nearest(int n_bins, int B, const uint8_t* q, int M, const uint8_t* lib, int k, int32_t* idx_out,
