@@ -399,6 +399,7 @@ struct V8T {
   __device__ __forceinline__ static Graph8Args gargs(const Graph& mg) {
     return Graph8Args{mg.N, mg.D, mg.S, mg.NC, mg.ntiles, mg.pubx, mg.pub_ch, mg.hk};
   }
+  __device__ __forceinline__ static int slot_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
   static constexpr bool kGlobalNodes = GN != 0 || PG;  // (the kernel passes its slice of the global scratch)
   template <int HP>
   __device__ __forceinline__ static void edm(const EdmDev& W, const Graph& mg, float* net, const float* sZ, float* sEps,
@@ -410,7 +411,12 @@ struct V8T {
     w8::edm_forward<HP, SP, GN>(W, mg, sm, sZ, sEps, sMean, t_val, tid STAMP_ARGS);
 #else
     (void)net; (void)sZ; (void)sEps; (void)sMean; (void)tid;
-    edm8_call<HP, SP, GN, kFL>(W, gargs(mg), t_val, gnode);
+    if constexpr (N1 && w8::node_uneven_slots<HP>()) {  // (w8_nodes_f16.h: tile-slot classes)
+      if (slot_wave() + w8::kWaves < HP / 16) edm8_call<HP, SP, GN, kFL + w8::kNodeSlots2>(W, gargs(mg), t_val, gnode);
+      else edm8_call<HP, SP, GN, kFL + w8::kNodeSlots1>(W, gargs(mg), t_val, gnode);
+    } else {
+      edm8_call<HP, SP, GN, kFL>(W, gargs(mg), t_val, gnode);
+    }
 #endif
   }
   template <int HP>
@@ -428,13 +434,27 @@ struct V8T {
     (void)sTmp;
     w8::PredSmem<HP, SP, GN, PG> sm;
     sm.carve(net, mg.N, mg.S, mg.pubx, gnode);
-    if (phase != 2) pred_fwd8_call<HP, SP, MR, GN, kFL, PG, SD>(W, gargs(mg), t_val, stash, readout_div, gnode, SD != 0 ? mg.side : 0);
+    constexpr bool kClasses = N1 && w8::node_uneven_slots<HP>();  // (w8_nodes_f16.h: tile-slot classes)
+    const bool two_slots = kClasses && slot_wave() + w8::kWaves < HP / 16;
+    if (phase != 2) {
+      if constexpr (kClasses) {
+        if (two_slots) pred_fwd8_call<HP, SP, MR, GN, kFL + w8::kNodeSlots2, PG, SD>(W, gargs(mg), t_val, stash, readout_div, gnode, SD != 0 ? mg.side : 0);
+        else pred_fwd8_call<HP, SP, MR, GN, kFL + w8::kNodeSlots1, PG, SD>(W, gargs(mg), t_val, stash, readout_div, gnode, SD != 0 ? mg.side : 0);
+      } else {
+        pred_fwd8_call<HP, SP, MR, GN, kFL, PG, SD>(W, gargs(mg), t_val, stash, readout_div, gnode, SD != 0 ? mg.side : 0);
+      }
+    }
     // (a value target takes out-of-line helpers around the unchanged affine code; vt is a compile-time nullptr in every
     // instantiation but the VT ones, so these branches exist in those alone)
     if (vt != nullptr) vt_seed8(vt, b, srow, W.K, (int)(sm.pred - lds_base()));
     else w8::guidance_seed(W, sm, target_w, scale, pred_out, tid, phase, dpred_ext);
     if (phase == 1) return;
-    pred_bwd8_call<HP, SP, MR, GN, kFL, PG>(W, gargs(mg), stash, readout_div, phase == 2 ? 1 : 0, gnode);
+    if constexpr (kClasses) {
+      if (two_slots) pred_bwd8_call<HP, SP, MR, GN, kFL + w8::kNodeSlots2, PG>(W, gargs(mg), stash, readout_div, phase == 2 ? 1 : 0, gnode);
+      else pred_bwd8_call<HP, SP, MR, GN, kFL + w8::kNodeSlots1, PG>(W, gargs(mg), stash, readout_div, phase == 2 ? 1 : 0, gnode);
+    } else {
+      pred_bwd8_call<HP, SP, MR, GN, kFL, PG>(W, gargs(mg), stash, readout_div, phase == 2 ? 1 : 0, gnode);
+    }
     if (dz_ext != nullptr) {  // + the target's direct dependence on z (callback launches are never packed: slot n = node n)
       for (int e = tid; e < mg.N * mg.D; e += kThreads) sGrad[e] += dz_ext[e];
       __syncthreads();

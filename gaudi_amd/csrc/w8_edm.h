@@ -188,7 +188,7 @@ __device__ __forceinline__ void edm_forward(const EdmDev& W, const MolGraph& mg,
   float* const xs1 = sm.ring + stage_stride(N * LD);
   if constexpr (!RI) er_start<HP>(ring, wbe, lay.gcl(0, 0) + 2 * PK, wave, lane);  // first edge GEMM: W2 of block 0's first GCL
   typename NodePFSel<HP, NH>::type pf;  // first weight tiles of the next node GEMM, loaded ahead of it
-  node_prefetch_x<HP, NH, kAheadOne>(pf, wb, wbe, lay.gcl(0, 0), mg.NC, wave, lane, tw);
+  node_prefetch_x<HP, NH, kAheadOne, FL>(pf, wb, wbe, lay.gcl(0, 0), mg.NC, wave, lane, tw);
   // split-copy region of the node GEMMs of this phase (NH)
   auto hctx = [&]() {
     if constexpr (NH) {

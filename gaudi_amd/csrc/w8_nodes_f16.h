@@ -34,12 +34,15 @@
 // Schedule.  Output tile t -> wave t & 7 (as the fp32 form).  The activations of a GEMM input are split ONCE by all waves into
 // LDS (wave w: rows w, w + 8, ...; one DPP max-scan per row, no cross-wave step) in B-operand order -- two conflict-free
 // ds_read_b128 per chunk and column tile; the weight stream runs kDepthH chunks ahead in registers, across the two sources of
-// a GEMM and across calls (the next matrix's first chunks travel while this one drains).  ONE body serves every wave and every
-// column-tile count: the registers of the weight stream are defined at one program point per chunk (a wave without a second tile
-// loads with out-of-range lanes, which fetch nothing); with one body per case hipcc joined the cases through register copies of
-// loads in flight, i.e. a wait for the whole stream at every call.  Accumulation order per output element: K chunks in order,
-// per chunk w_hi x_lo, w_hi x_hi, w_lo x_hi; then the fp32 tail steps; sources in order -- independent of the column-tile count
-// and of the wave's tile count (packed launches stay bit-identical to unpacked ones).
+// a GEMM and across calls (the next matrix's first chunks travel while this one drains).  Inside a phase ONE body serves every
+// column-tile count: the registers of the weight stream are defined at one program point per chunk; with one body per case and a
+// branch per CALL hipcc joined the cases through register copies of loads in flight, i.e. a wait for the whole stream at every call.
+// A wave without a second tile (12 / 13 tiles: waves 4-7 / 5-7) loads its empty slot with out-of-range lanes, which fetch nothing
+// but occupy the CU's vector-memory path like any load -- except in the N1 kernels, where such a wave runs the whole PHASE in a
+// body of its own that has one slot (tile-slot classes below; round 13): no loads, matrix instructions, bias, fold or epilogue
+// test for the other.  Accumulation order per output element: bias, then the fp32 tail steps, then K chunks in order, per chunk
+// w_hi x_lo, w_hi x_hi, w_lo x_hi; sources in order -- independent of the column-tile count, of the wave's tile count and of its
+// class (packed launches stay bit-identical to unpacked ones).
 #pragma once
 #include "w8_split.h"
 
@@ -49,8 +52,7 @@ namespace w8 {
 
 constexpr float kLoScale = 2048.f;  // 2^11
 #ifndef GAUDI_NODE_ABLATE
-#define GAUDI_NODE_ABLATE 0  // microbenchmark only (timing, wrong results): 1 = no split pass, 2 = no matrix instructions, 4 = no weight loads,
-                             // 8 = waves without a second output tile run a one-tile body (tools/node_gemm_h_microbench.hip; node_gemm_h: NU)
+#define GAUDI_NODE_ABLATE 0  // microbenchmark only (timing, wrong results): 1 = no split pass, 2 = no matrix instructions, 4 = no weight loads
 #endif
 constexpr int kAblateH = GAUDI_NODE_ABLATE;
 // microbenchmark only (-DGAUDI_NODE_STAMPS=1): cycle sums of the parts of a node GEMM, per wave (s_memtime waits for lgkmcnt(0): shares, not
@@ -225,18 +227,6 @@ __device__ __forceinline__ void lds_barrier() {
 #ifndef GAUDI_NODE_DEPTH
 #define GAUDI_NODE_DEPTH 3
 #endif
-// Of the next matrix's chunks that a call loads ahead, the last GAUDI_NODE_LATE are issued AFTER its K loop -- one behind the
-// loop, one behind the fold -- instead of inside it: the K loop is bound by the CU's vector-memory pipe (its waves sit in
-// buffer_load issue), the split pass and the epilogue leave that pipe idle, so loads moved there cost nothing.
-#ifndef GAUDI_NODE_LATE
-#define GAUDI_NODE_LATE 0
-#endif
-// The fp32 tail steps of a source (odd tile counts) ahead of its K loop instead of in the fold behind it: they need the bias, the tail
-// weights (loaded in the prologue) and the split copy, not the loop -- y then reaches the fold complete.  Same order of operations per
-// output element (bias, tail steps, descaled chunk sums).  Measured: DESIGN section 8, round 9.
-#ifndef GAUDI_NODE_TAIL_EARLY
-#define GAUDI_NODE_TAIL_EARLY 0
-#endif
 template <int HP>
 struct NodeGeoH {
   static constexpr int T = HP / 16;
@@ -283,13 +273,14 @@ __device__ __forceinline__ void nh_load(NodeSetH<NodeGeoH<HP>::NTW>& s, const WB
 // ONE chunk (8-16 registers: across the register-tight edge phases; the call issues the others itself, and they fly while its
 // input is split).
 constexpr int kAheadOne = 1, kAheadAll = 99;
-template <int HP, int AHEAD = kAheadAll>
+// NU: the tile slots this body loads (node_gemm_h below), 0 = the geometry's
+template <int HP, int AHEAD = kAheadAll, int NU = 0>
 __device__ __forceinline__ void node_prefetch_h(NodePFH<HP>& pf, const WBuf& wh, int W /* fp32 float offset */, int wave, int lane) {
   constexpr int nd = AHEAD < NodeGeoH<HP>::D ? AHEAD : NodeGeoH<HP>::D;
   const TileLanesH<HP> tl(wave, lane);
   static_for<nd>([&](auto d_tag) {
     constexpr int d = decltype(d_tag)::value;
-    nh_load<HP>(pf.s[d], wh, 2 * W + d * nh_chunk_floats(HP), tl);
+    nh_load<HP, (NU > 0 ? NU : NodeGeoH<HP>::NTW)>(pf.s[d], wh, 2 * W + d * nh_chunk_floats(HP), tl);
   });
 }
 
@@ -298,6 +289,18 @@ constexpr int kNodePlain = 0;    // lane addresses of the split passes and epilo
 constexpr int kNodeFresh = 1;    // ... recomputed per call (node_gemm_x below)
 constexpr int kNodeOneTile = 2;  // kNodePlain for workgroups of at most 16 node slots: ONE column tile and, at a width with a tail
                                  // block, ONE tail k-step (H % 16 == 4) are compile-time facts -- the host guarantees both
+// Tile-slot classes (round 13).  At 12 or 13 output tiles waves 4-7 / 5-7 own ONE tile of their two slots.  An N1 kernel calls each of
+// its out-of-line phases (sampler_kernel.h: edm8_call, pred_fwd8_call, pred_bwd8_call) in the instantiation of the wave's class --
+// FL = kNodeOneTile + kNodeSlots2 for the waves with a second tile, + kNodeSlots1 for the others, whose node GEMMs and loads ahead
+// then issue nothing for the slot they do not own (node_gemm_h: NU).  The branch is wave-uniform and lies around the WHOLE phase:
+// the classes share no register allocation, and inside a body no load sits behind a branch.  Barriers count waves, not places.
+constexpr int kNodeSlots1 = 4, kNodeSlots2 = 8;
+__host__ __device__ constexpr bool node_one_tile(int FL) { return (FL & 3) == kNodeOneTile; }
+template <int HP>
+__host__ __device__ constexpr bool node_uneven_slots() { return NodeGeoH<HP>::NTW == 2 && NodeGeoH<HP>::T < 2 * kWaves; }
+// NU of node_gemm_h / node_prefetch_h for a kernel form (0 = the geometry's: every wave runs NTW slots)
+template <int HP>
+__host__ __device__ constexpr int node_slots(int FL) { return node_one_tile(FL) && node_uneven_slots<HP>() ? FL >> 2 : 0; }
 // TAIL of node_gemm_h: how many k-steps of the fp32 tail block hold weights
 constexpr int kTailRuntime = 0;  // NodeCtxH::ktail says: one or four
 constexpr int kTailOne = 1;      // one (H % 16 == 4): steps 1-3 are neither loaded nor compiled
@@ -324,7 +327,7 @@ struct YInitRows {
 // The caller guarantees that nobody still reads the split regions when the call starts (a barrier since their last use) and
 // places a barrier between this call's stores to sY and their readers, as for the fp32 form.
 // sXb: the second source's rows, a pointer or a row source (RowsOne / RowsSum above).
-// NU (microbenchmark only, GAUDI_NODE_ABLATE & 8): the output tiles this body loads and multiplies, 0 = the geometry's.
+// NU: the tile slots this body loads, multiplies and stores (tile-slot classes above), 0 = the geometry's.
 // sXa: the first source's rows, a pointer or a row source too.  yinit (YInitRows): y starts from the rows of an LDS array [N][HP + 4]
 // instead of the bias -- a first source's whole contribution computed elsewhere (side_job_h below), bias and tail step included.
 template <int HP, int EPI, bool TWO, int MAXNT, int PIN = kAheadOne, int POUT = kAheadOne, int FL = kNodePlain, int TAIL = kTailRuntime,
@@ -339,7 +342,6 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
   using G = NodeGeoH<HP>;
   constexpr int T = G::T, LD = HP + 4, NTW = NU > 0 ? NU : G::NTW, nc = G::nc, D = G::D;
   constexpr int kIn = PIN < D ? PIN : D, kOut = POUT < D ? POUT : D;
-  constexpr int kLate = nc < D ? 0 : (GAUDI_NODE_LATE < kOut ? GAUDI_NODE_LATE : kOut);  // (matrices of fewer chunks than sets: all in the loop)
   constexpr int TQ = TAIL == kTailOne ? 1 : 4;                 // tail k-steps that exist in this instantiation
   const bool ktail = TAIL == kTailOne ? true : cx.ktail;
   constexpr bool kFresh = FL == kNodeFresh;
@@ -434,19 +436,12 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
       }
     }
   };
-  constexpr bool kTailEarly = GAUDI_NODE_TAIL_EARLY != 0;
-  auto tail_early = [&](const SplitBufH& s_, const float (&tw)[NTW][TQ]) {
-    if constexpr (kTailEarly && G::odd)
-      static_for<MAXNT>([&](auto j_tag) {
-        if (decltype(j_tag)::value < nt) tail_steps(s_, tw, j_tag);
-      });
-  };
   // descale and fold the accumulators of one source into y
   auto fold = [&](const SplitBufH& s_, const float (&tw)[NTW][TQ]) {
     static_for<MAXNT>([&](auto j_tag) {
       constexpr int j = decltype(j_tag)::value;
       if (j < nt) {
-        if constexpr (!kTailEarly) tail_steps(s_, tw, j_tag);
+        tail_steps(s_, tw, j_tag);
         const float sc = s_.scale(HP)[j * 16 + c] * cx.winv;
 #pragma unroll
         for (int u = 0; u < NTW; ++u) {
@@ -484,20 +479,11 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
       if (!(kAblateH & 4)) {
         if constexpr (i + D < nc) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wcur + (i + D) * nh_chunk_floats(HP), tl);
         else if constexpr (!last_src) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wb + d * nh_chunk_floats(HP), tl);
-        else if constexpr (d < kOut - kLate) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
+        else if constexpr (d < kOut) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       }
       __builtin_amdgcn_sched_barrier(0);
       bcur = bnext;
     });
-  };
-  // the next matrix's chunk d, issued behind the K loop (its set's last use lies behind: chunk nc - D + d .. of the last source)
-  auto late = [&](auto d_tag) {
-    constexpr int d = decltype(d_tag)::value;
-    if constexpr (d >= kOut - kLate && d < kOut) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (!(kAblateH & 4)) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
-      __builtin_amdgcn_sched_barrier(0);
-    }
   };
   NSTAMP(3);
 #if GAUDI_NODE_PRIO
@@ -509,10 +495,8 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
   if constexpr (!kFresh)
     if ((GAUDI_NODE_PRIO == 1 && wave >= kWaves / 2) || (GAUDI_NODE_PRIO == 2 && wave < kWaves / 2)) __builtin_amdgcn_s_setprio(1);
 #endif
-  tail_early(sa, ta);
   source(std::integral_constant<int, 0>{}, sa);
   NSTAMP(4);
-  if constexpr (!TWO) late(std::integral_constant<int, kOut - kLate>{});
   fold(sa, ta);
   NSTAMP(5);
   if constexpr (TWO) {
@@ -521,14 +505,9 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
       split_rows_h<HP>(sb, sXb, N, wave, kFresh ? fresh(lane) : lane);
       lds_barrier();
     }
-    tail_early(sb, tb);
     source(std::integral_constant<int, 1>{}, sb);
-    late(std::integral_constant<int, kOut - kLate>{});
     fold(sb, tb);
   }
-  static_for<D>([&](auto d_tag) {
-    if constexpr (decltype(d_tag)::value > kOut - kLate) late(d_tag);
-  });
 #if GAUDI_NODE_PRIO
   if constexpr (!kFresh) __builtin_amdgcn_s_setprio(0);
 #endif
@@ -706,9 +685,9 @@ template <int HP>
 struct NodePFSel<HP, true> {
   using type = NodePFH<HP>;
 };
-template <int HP, bool NH, int AHEAD, class PF>
+template <int HP, bool NH, int AHEAD, int FL = kNodePlain, class PF>
 __device__ __forceinline__ void node_prefetch_x(PF& pf, const WBuf& wb, const WBuf& wbe, int W, int N, int wave, int lane, bool tw) {
-  if constexpr (NH) node_prefetch_h<HP, AHEAD>(pf, wbe, W, wave, lane);
+  if constexpr (NH) node_prefetch_h<HP, AHEAD, node_slots<HP>(FL)>(pf, wbe, W, wave, lane);
   else node_prefetch<HP>(pf, wb, W, wave, lane, tw);
 }
 // Xa / Xb: the input rows where they live (LDS, or global memory for the GN kernels); XaS / XbS: their staged copies in the idle
@@ -730,14 +709,15 @@ __device__ __forceinline__ void node_gemm_x(const WBuf& wb, const WBuf& wbe, int
                                             const float* Xb1 = nullptr, float xb_div = 1.f) {
   static_assert(XBS == 0 || (NH && GN == 0 && TWO), "summed second sources: the fp16-pair form of the resident kernels");
   if constexpr (NH) {
-    constexpr int MAXNT = GN ? 3 : FL == kNodeOneTile ? 1 : 2;
-    constexpr int TAIL = FL == kNodeOneTile && nh_odd(HP) ? kTailOne : kTailRuntime;
+    constexpr int MAXNT = GN ? 3 : node_one_tile(FL) ? 1 : 2;
+    constexpr int TAIL = node_one_tile(FL) && nh_odd(HP) ? kTailOne : kTailRuntime;
+    constexpr int NU = node_slots<HP>(FL);
     if constexpr (XBS == 0)
-      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL>(wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW,
-                                                            gPre, sMaxOut);
+      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL, NU>(wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW,
+                                                                gPre, sMaxOut);
     else
-      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL>(wbe, Wa, Xa, split_a, Wb, RowsSum<XBS == 2>{Xb, Xb1, xb_div}, sBias, sY, sRes, sMask, N,
-                                                            wave, lane, cx, pf, nextW, gPre, sMaxOut);
+      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL, NU>(wbe, Wa, Xa, split_a, Wb, RowsSum<XBS == 2>{Xb, Xb1, xb_div}, sBias, sY, sRes, sMask,
+                                                                N, wave, lane, cx, pf, nextW, gPre, sMaxOut);
   } else if constexpr (GN != 0) {
     node_gemm_n<HP, EPI, true, 3>(wb, Wa, XaS, Wb, XbS, sBias, sY, sRes, sMask, N, wave, lane, tw, &pf, nextW, gPre);
   } else {

@@ -151,7 +151,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
   float* const xs1 = sm.ring + stage_stride(N * LD);
   if constexpr (!RI) er_start<HP>(ring, wbe, lay.layer(0) + 2 * HP * HP, wave, lane);  // W2 of layer 0
   typename NodePFSel<HP, NH>::type pf;
-  node_prefetch_x<HP, NH, kAheadOne>(pf, wb, wbe, lay.layer(0), mg.NC, wave, lane, tw);
+  node_prefetch_x<HP, NH, kAheadOne, FL>(pf, wb, wbe, lay.layer(0), mg.NC, wave, lane, tw);
   auto hctx = [&]() {
     if constexpr (NH) {
       if constexpr (RI) return node_ctx_h<HP>(sm.ring, EdgeRing<HP, SP>::kFloats, mg.NC, W.hinv, tw, sm.hsc);
@@ -163,7 +163,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
   // a kept split copy of h: P splits it, Q and the node MLP's first Linear read the same copy (w8_nodes_f16.h: node_ctx_keep)
   const bool keep = NH && sm.hk != nullptr;
   constexpr bool kSideA = (SD & 1) != 0;
-  static_assert(!kSideA || (NH && !MR && GN == 0 && !RI && FL == kNodeOneTile), "the side job is a form of the resident N1 kernel");
+  static_assert(!kSideA || (NH && !MR && GN == 0 && !RI && node_one_tile(FL)), "the side job is a form of the resident N1 kernel");
   constexpr int NV = (PredLayerW::vec_count(HP) + kThreads - 1) / kThreads;
   VecPF<NV> vpf;  // the next layer's vectors, loaded one node GEMM ahead
   vec_prefetch<NV, kThreads>(vpf, wb, PredLayerW::vec_off(lay.layer(0), HP), PredLayerW::vec_count(HP), tid);
@@ -305,7 +305,7 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
     STAMP(ST_MISC);
     if constexpr (kSideA) {
       if (side_l)
-        node_gemm_h<HP, EPI_SILU, false, 1, kAheadOne, kAheadOne, FL, nh_odd(HP) ? kTailOne : kTailRuntime>(
+        node_gemm_h<HP, EPI_SILU, false, 1, kAheadOne, kAheadOne, FL, nh_odd(HP) ? kTailOne : kTailRuntime, node_slots<HP>(FL)>(
             wbe, Lw.Wn1a, RowsSum<false>{agg, agg1, 1.f}, true, -1, (const float*)nullptr, nullptr, p, nullptr, nullptr, mg.NC, wave, lane,
             hctx(), pf, Lw.Wn2, st + 2 * N * HP /* npre -> stash */, nullptr, nullptr, YInitRows{sm.side});
     }
@@ -417,7 +417,7 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
     er_start<HP>(ring, wbe, L0 + 9 * HP * HP /* W2^T of the last layer (its coordinate branch is skipped) */, wave, lane);
   }
   typename NodePFSel<HP, NH>::type pf;
-  node_prefetch_x<HP, NH, kAheadOne>(pf, wb, wbe, lay.layer(W.L - 1) + 13 * HP * HP /* Wn2^T of the last layer */, mg.NC, wave, lane, tw);
+  node_prefetch_x<HP, NH, kAheadOne, FL>(pf, wb, wbe, lay.layer(W.L - 1) + 13 * HP * HP /* Wn2^T of the last layer */, mg.NC, wave, lane, tw);
   auto hctx = [&]() {
     if constexpr (NH) {
       if constexpr (RI) return node_ctx_h<HP>(sm.ring, EdgeRing<HP, SP>::kFloats, mg.NC, W.hinv, tw, sm.hsc);
@@ -671,7 +671,7 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
       }
       if (SP != 0 && !RI && l > 0)
         er_start<HP>(ring, wbe, lay.layer(l - 1) + 10 * HP * HP /* Wc1^T of the layer below */, wave, lane);
-      node_prefetch_x<HP, NH, kAheadOne>(pf, wb, wbe, Lw.At, mg.NC, wave, lane, tw);
+      node_prefetch_x<HP, NH, kAheadOne, FL>(pf, wb, wbe, Lw.At, mg.NC, wave, lane, tw);
       STAMP(ST_BWD_COL);
     }
     // dx <- dx*mask + sum_{e: i=n} ddiff_e - sum_{e: j=n} ddiff_e, in slot order

@@ -99,7 +99,9 @@ def step_mfma_counts(edge_units, ncols, edm, pred=None, variant="w4", max_col_ti
             # fp16-pair node GEMMs (w8_nodes_f16.h, round 5): three v_mfma_f32_16x16x32_f16 per chunk of 32 inputs, column tile and
             # output-tile SLOT -- every wave runs the slots of the widest wave (two for more than 8 tiles; a slot without a tile
             # multiplies zeros) -- and, for an odd tile count, the last 16 inputs as fp32 steps (one when H % 16 == 4, else four)
-            slots = waves * (2 if T > waves else 1)
+            # ... except in the N1 kernels (one column tile at the default widths: lean below), where a wave issues nothing for a
+            # slot without a tile (w8_nodes_f16.h: tile-slot classes, round 13): T slots, not 16
+            slots = T if lean else waves * (2 if T > waves else 1)
             mats = kt // T
             tail = (1 if _has_ktail(nf, 16 * T) else 4) if T % 2 else 0
             return mats * slots * tail * nt, mats * (T // 2) * 3 * slots * nt
@@ -118,6 +120,10 @@ def step_mfma_counts(edge_units, ncols, edm, pred=None, variant="w4", max_col_ti
 
     f32 = bf = 0
     Te = _pad_hidden_kernel(edm["nf"]) // 16
+    # the host's kernel choice as far as the arguments tell it (gaudi_hip.hip; kern8s1_*.hip): at most 16 node columns on the
+    # resident kernels (max_col_tiles = 3 means V8G), EDM 192 and, if guided, a predictor padded to 208 whose tail holds one k-step
+    lean = (variant == "w8s" and ncols <= 16 and max_col_tiles < 3 and 16 * Te == 192 and
+            (pred is None or (_pad_hidden_kernel(pred["nf"]) == 208 and _has_ktail(pred["nf"], 208))))
     L, S = edm["n_layers"], edm.get("inv_sublayers", 1)
     e32, ebf = edge(Te, edm["nf"])
     n32, n16 = node(Te, (5 * S + 2) * Te, edm["nf"])  # 5 node-level matrices per GCL, 2 per EquivariantUpdate

@@ -15,7 +15,10 @@ using namespace gaudi;
 #define GAUDI_MB_AHEAD w8::kAheadAll  // chunks that travel ahead of a call; w8::kAheadOne: what most call sites of the kernels use
 #endif
 #ifndef GAUDI_MB_FL
-#define GAUDI_MB_FL 0  // 1: the FL form (lane addresses recomputed per call: the MR / GN / FR kernels); 2 = 0 here (w8::kNodeOneTile)
+#define GAUDI_MB_FL 0  // 1: the FL form (lane addresses recomputed per call: the MR / GN / FR kernels); 2: w8::kNodeOneTile (with MAXNT=1, TAIL=kTailOne)
+#endif
+#ifndef GAUDI_MB_LEAN
+#define GAUDI_MB_LEAN 1  // with GAUDI_MB_FL=2 at 12 / 13 output tiles: the N1 kernels' tile-slot classes (0: every wave runs both slots)
 #endif
 #ifndef GAUDI_MB_TAIL
 #define GAUDI_MB_TAIL w8::kTailRuntime  // w8::kTailOne: one tail k-step compiled in (the N1 kernels; timings only -- the numerics' tail = 0 cases need four)
@@ -29,8 +32,9 @@ struct Sel;
 template <int HP>
 struct Sel<HP, 0> {
   using PF = w8::NodePF<HP>;
+  template <int FL>
   static __device__ __forceinline__ void prefetch(PF& pf, const WBuf& wb, int W, int wave, int lane, bool tw, int) { w8::node_prefetch<HP>(pf, wb, W, wave, lane, tw); }
-  template <int EPI>
+  template <int EPI, int FL>
   static __device__ __forceinline__ void gemm(const WBuf& wb, int Wa, const float* sXa, int Wb, const float* sXb, const float* sB, float* sY, int N,
                                               int wave, int lane, bool tw, PF* pf, int nextW, float*, float, bool, w8::NodeStampH* = nullptr) {
     w8::node_gemm<HP, EPI, true>(wb, Wa, sXa, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, tw, pf, nextW);
@@ -39,30 +43,50 @@ struct Sel<HP, 0> {
 template <int HP>
 struct Sel<HP, 3> {
   using PF = w8::NodePFH<HP>;
-  static __device__ __forceinline__ void prefetch(PF& pf, const WBuf& wb, int W, int wave, int lane, bool tw, int N) { w8::node_prefetch_h<HP, GAUDI_MB_AHEAD>(pf, wb, W, wave, lane); }
-  template <int EPI>
+  template <int FL>
+  static __device__ __forceinline__ void prefetch(PF& pf, const WBuf& wb, int W, int wave, int lane, bool tw, int N) {
+    w8::node_prefetch_h<HP, GAUDI_MB_AHEAD, w8::node_slots<HP>(FL)>(pf, wb, W, wave, lane);
+  }
+  template <int EPI, int FL>
   static __device__ __forceinline__ void gemm(const WBuf& wb, int Wa, const float* sXa, int Wb, const float* sXb, const float* sB, float* sY, int N,
                                               int wave, int lane, bool tw, PF* pf, int nextW, float* split, float winv, bool seq,
                                               w8::NodeStampH* ns = nullptr) {
     const int nct = N <= 16 ? 1 : N <= 32 ? 2 : 3;
     w8::NodeCtxH cx{winv, split + 96, seq ? split + 96 : split + 96 + w8::nh_split_floats(HP, nct), tw, split};
-    // GAUDI_NODE_ABLATE & 8 (timings only): a wave without a second output tile (13 tiles: waves 5-7; 12: waves 4-7) runs a body
-    // with ONE tile -- no second-tile loads (all lanes out of range in the shipped form) and no second-tile matrix instructions
-    if ((GAUDI_NODE_ABLATE & 8) && HP / 16 > 8 && wave + 8 >= HP / 16) {
-      if (Wb >= 0)
-        w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL, 1>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx,
-                                                                                                          *pf, nextW, nullptr, nullptr, ns);
-      else
-        w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL, 1>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane,
-                                                                                                           cx, *pf, nextW, nullptr, nullptr, ns);
-    } else if (Wb >= 0)
-      w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
-                                                                                    nullptr, nullptr, ns);
+    constexpr int NU = w8::node_slots<HP>(FL);  // (the tile slots of the wave's class: run_gemms below)
+    if (Wb >= 0)
+      w8::node_gemm_h<HP, EPI, true, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, FL, GAUDI_MB_TAIL, NU>(wb, Wa, sXa, true, Wb, sXb, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf,
+                                                                                                          nextW, nullptr, nullptr, ns);
     else
-      w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, GAUDI_MB_FL, GAUDI_MB_TAIL>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane, cx, *pf, nextW,
-                                                                                     nullptr, nullptr, ns);
+      w8::node_gemm_h<HP, EPI, false, GAUDI_MB_MAXNT, GAUDI_MB_AHEAD, GAUDI_MB_AHEAD, FL, GAUDI_MB_TAIL, NU>(wb, Wa, sXa, true, -1, nullptr, sB, sY, nullptr, nullptr, N, wave, lane, cx,
+                                                                                                           *pf, nextW, nullptr, nullptr, ns);
   }
 };
+
+template <int HP, int V, int FL>
+__device__ __forceinline__ void run_gemms(const WBuf& wb, int nmat, int gemms, int N, int tail, int two, float* sX, float* sY, float* sSplit, int wave,
+                                          int lane, w8::NodeStampH& st) {
+  constexpr int T = HP / 16;
+  const int MS = T * T * 256;  // matrix stride in fp32-offset units (the f16 images sit at 2 W)
+  typename Sel<HP, V>::PF pf;
+  Sel<HP, V>::template prefetch<FL>(pf, wb, 0, wave, lane, tail != 0, N);
+  st.start();
+  w8::NodeStampH* ns = GAUDI_NODE_STAMPS ? &st : nullptr;
+#pragma unroll 1
+  for (int m = 0; m < gemms; ++m) {
+    const int W = (m % nmat) * MS, nextW = ((m + 1) % nmat) * MS;
+    if (two) {
+      const int m2 = (m + nmat / 2) % nmat;
+      Sel<HP, V>::template gemm<EPI_SILU, FL>(wb, W, (m & 1) ? sY : sX, m2 * MS, (m & 1) ? sY : sX, nullptr, (m & 1) ? sX : sY, N, wave, lane, tail != 0, &pf,
+                                              nextW, sSplit, 1.0f, two == 2, ns);
+    } else {
+      Sel<HP, V>::template gemm<EPI_SILU, FL>(wb, W, (m & 1) ? sY : sX, -1, nullptr, nullptr, (m & 1) ? sX : sY, N, wave, lane, tail != 0, &pf, nextW, sSplit,
+                                              1.0f, false, ns);
+    }
+    __syncthreads();
+    if (GAUDI_NODE_STAMPS) st.mark(7);
+  }
+}
 
 template <int HP, int V>
 __global__ __launch_bounds__(512) void k(const float* w, unsigned wbytes, int nmat, float* out, unsigned long long* cyc, int gemms,
@@ -77,27 +101,15 @@ __global__ __launch_bounds__(512) void k(const float* w, unsigned wbytes, int nm
   for (int i = tid; i < 2 * R * LD; i += 512) sX[i] = 0.01f * ((i * 7) % 13) - 0.05f;
   __syncthreads();
   const WBuf wb = make_wbuf(w, wbytes);
-  const int MS = (V == 3 ? 1 : 1) * T * T * 256;  // matrix stride in fp32-offset units (the f16 images sit at 2 W)
-  typename Sel<HP, V>::PF pf;
-  Sel<HP, V>::prefetch(pf, wb, 0, wave, lane, tail != 0, N);
   w8::NodeStampH st;
   for (int i = 0; i < 8; ++i) st.sum[i] = 0;
-  st.start();
-  w8::NodeStampH* ns = GAUDI_NODE_STAMPS ? &st : nullptr;
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#pragma unroll 1
-  for (int m = 0; m < gemms; ++m) {
-    const int W = (m % nmat) * MS, nextW = ((m + 1) % nmat) * MS;
-    if (two) {
-      const int m2 = (m + nmat / 2) % nmat;
-      Sel<HP, V>::template gemm<EPI_SILU>(wb, W, (m & 1) ? sY : sX, m2 * MS, (m & 1) ? sY : sX, nullptr, (m & 1) ? sX : sY, N, wave, lane, tail != 0, &pf,
-                                          nextW, sSplit, 1.0f, two == 2, ns);
-    } else {
-      Sel<HP, V>::template gemm<EPI_SILU>(wb, W, (m & 1) ? sY : sX, -1, nullptr, nullptr, (m & 1) ? sX : sY, N, wave, lane, tail != 0, &pf, nextW, sSplit,
-                                          1.0f, false, ns);
-    }
-    __syncthreads();
-    if (GAUDI_NODE_STAMPS) st.mark(7);
+  // as the N1 kernels call their phases: the whole sequence in the body of the wave's tile-slot class (w8_nodes_f16.h)
+  if constexpr (V == 3 && GAUDI_MB_FL == w8::kNodeOneTile && GAUDI_MB_LEAN != 0 && w8::node_uneven_slots<HP>()) {
+    if (wave + w8::kWaves < T) run_gemms<HP, V, GAUDI_MB_FL + w8::kNodeSlots2>(wb, nmat, gemms, N, tail, two, sX, sY, sSplit, wave, lane, st);
+    else run_gemms<HP, V, GAUDI_MB_FL + w8::kNodeSlots1>(wb, nmat, gemms, N, tail, two, sX, sY, sSplit, wave, lane, st);
+  } else {
+    run_gemms<HP, V, GAUDI_MB_FL>(wb, nmat, gemms, N, tail, two, sX, sY, sSplit, wave, lane, st);
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
   out[blockIdx.x * 512 + tid] = sX[tid % (R * LD)];
@@ -130,8 +142,8 @@ __global__ __launch_bounds__(512) void k_num(const float* w, unsigned wbytes, co
   __syncthreads();
   const WBuf wb = make_wbuf(w, wbytes);
   typename Sel<HP, V>::PF pf;
-  Sel<HP, V>::prefetch(pf, wb, 0, wave, lane, tail != 0, N);
-  Sel<HP, V>::template gemm<EPI_NONE>(wb, 0, sXa, two ? T * T * 256 : -1, sXb, sB, sY, N, wave, lane, tail != 0, &pf, -1, sSplit, winv, two == 2);
+  Sel<HP, V>::template prefetch<GAUDI_MB_FL>(pf, wb, 0, wave, lane, tail != 0, N);
+  Sel<HP, V>::template gemm<EPI_NONE, GAUDI_MB_FL>(wb, 0, sXa, two ? T * T * 256 : -1, sXb, sB, sY, N, wave, lane, tail != 0, &pf, -1, sSplit, winv, two == 2);
   __syncthreads();
   for (int i = tid; i < N * HP; i += 512) y[i] = sY[(i / HP) * LD + i % HP];
 }
@@ -344,8 +356,9 @@ void timing() {
 }
 
 int main(int argc, char**) {
-  printf("depth %d, column tiles <= %d, tail %s, ablation %d\n", GAUDI_NODE_DEPTH, GAUDI_MB_MAXNT,
-         GAUDI_MB_TAIL == w8::kTailOne ? "one step compiled in" : "run time", GAUDI_NODE_ABLATE);
+  printf("depth %d, column tiles <= %d, tail %s, ablation %d, form %d, tile-slot classes %s\n", GAUDI_NODE_DEPTH, GAUDI_MB_MAXNT,
+         GAUDI_MB_TAIL == w8::kTailOne ? "one step compiled in" : "run time", GAUDI_NODE_ABLATE, GAUDI_MB_FL,
+         GAUDI_MB_FL == w8::kNodeOneTile && GAUDI_MB_LEAN != 0 ? "on" : "off");
   if (argc > 1) {  // any argument: the fp16 form's timings only
     timing<3>();
     return 0;
