@@ -85,6 +85,16 @@ CANON_OK, CANON_GAVE_UP, CANON_BAD_INPUT, CANON_OVERFLOW, CANON_EMPTY = range(5)
 # include/gaudi_hip.h: GAUDI_SUB_*
 SUB_MAX_QUERY, SUB_MAX_PATTERNS, SUB_MAX_STEPS, SUB_H_EXACT, SUB_CLOSED = 32, 64, 8192, 1, 2
 SUB_OK, SUB_GAVE_UP, SUB_BAD_INPUT, SUB_OVERFLOW, SUB_EMPTY, SUB_BAD_PATTERN = range(6)
+# include/gaudi_hip.h: GAUDI_HUCKEL_*
+HUCKEL_MAX_PI, HUCKEL_MAX_CLASSES, HUCKEL_MAX_SWEEPS, HUCKEL_OPEN_SHELL, HUCKEL_DEGENERATE = 128, 16, 30, 1, 2
+HUCKEL_OK, HUCKEL_NOT_CONVERGED, HUCKEL_BAD_INPUT, HUCKEL_OVERFLOW, HUCKEL_EMPTY, HUCKEL_NO_PI, HUCKEL_BAD_TABLE = range(7)
+
+
+class HuckelTables(C.Structure):
+    """gaudi_huckel_tables (include/gaudi_hip.h)."""
+    _fields_ = [("n_elems", C.c_int32), ("h_elem", C.c_int32), ("c_elem", C.c_int32), ("n_classes", C.c_int32),
+                ("site_class", (C.c_int32 * 5) * 8), ("h", C.c_float * 16), ("n_e", C.c_int32 * 16), ("k", C.c_float * 16),
+                ("k_pair", (C.c_float * 16) * 16)]
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
@@ -161,6 +171,9 @@ EXPORTS = {
     "gaudi_host_substructure_search": (C.c_int, [C.c_int] * 6 + [IP] * 4 + [C.c_int] * 3 + [IP] * 5 + [IP, IP, U8P, IP, IP]),
     "gaudi_host_substructure_root_steps": (C.c_int, [C.c_int]),
     "gaudi_substructure_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_huckel": (C.c_int, [C.c_void_p, C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [FP, U8P] + [IP] * 6 + [FP] * 6 + [C.POINTER(C.c_int8)]),
+    "gaudi_host_huckel": (C.c_int, [C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [FP, U8P] + [IP] * 6 + [FP] * 6 + [C.POINTER(C.c_int8)]),
+    "gaudi_huckel_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -239,6 +252,7 @@ _CANON_EXPORTS = ("gaudi_canonical_order", "gaudi_canon_profile_get")  # ... and
 _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_nearest", "gaudi_fp_common",
                "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
+_HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -267,7 +281,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -469,6 +483,46 @@ def host_substructure_search(n_elems, h_elem, c_elem, elem, n_atoms, bonds, n_bo
 def host_substructure_root_steps(reset=False) -> int:
     """gaudi_host_substructure_root_steps: the largest per-root step count of the host build since the last reset."""
     return int(load_library().gaudi_host_substructure_root_steps(int(bool(reset))))
+
+
+HUCKEL_ARRAYS = ("levels", "occupation", "n_pi", "n_electrons", "n_excluded", "sweeps", "flags", "status", "homo", "lumo", "gap",
+                 "e_pi", "pi_charge", "pi_bond_order", "site_class")
+
+
+def huckel_outputs(B: int, A: int, M: int) -> dict:
+    """The fifteen output arrays of gaudi_huckel / gaudi_host_huckel, in argument order."""
+    i32, f32_ = (lambda: np.zeros(B, np.int32)), (lambda: np.zeros(B, np.float32))
+    return dict(levels=np.zeros((B, HUCKEL_MAX_PI), np.float32), occupation=np.zeros((B, HUCKEL_MAX_PI), np.uint8), n_pi=i32(),
+                n_electrons=i32(), n_excluded=i32(), sweeps=i32(), flags=i32(), status=i32(), homo=f32_(), lumo=f32_(), gap=f32_(),
+                e_pi=f32_(), pi_charge=np.zeros((B, A), np.float32), pi_bond_order=np.zeros((B, M), np.float32),
+                site_class=np.zeros((B, A), np.int8))
+
+
+def huckel_args(tables, elem, n_atoms, bonds, n_bonds, charge, out):
+    """The arguments both entry points share: the table, the molecules as bond_orders takes them, charge [B] int32 or None, the
+    outputs."""
+    for a in (elem, n_atoms, bonds, n_bonds) + (() if charge is None else (charge,)):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert charge is None or charge.shape == (B,)
+    assert out["levels"].shape == (B, HUCKEL_MAX_PI) and out["pi_charge"].shape == (B, A) and out["pi_bond_order"].shape == (B, M)
+    ip = lambda a: a.ctypes.data_as(IP)
+    fp = lambda a: a.ctypes.data_as(FP)
+    return (C.byref(tables), B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), None if charge is None else ip(charge),
+            fp(out["levels"]), out["occupation"].ctypes.data_as(U8P), ip(out["n_pi"]), ip(out["n_electrons"]), ip(out["n_excluded"]),
+            ip(out["sweeps"]), ip(out["flags"]), ip(out["status"]), fp(out["homo"]), fp(out["lumo"]), fp(out["gap"]), fp(out["e_pi"]),
+            fp(out["pi_charge"]), fp(out["pi_bond_order"]), out["site_class"].ctypes.data_as(C.POINTER(C.c_int8)))
+
+
+def host_huckel(tables, elem, n_atoms, bonds, n_bonds, charge=None) -> dict:
+    """gaudi_host_huckel (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = huckel_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_huckel(*huckel_args(tables, elem, n_atoms, bonds, n_bonds, charge, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_huckel failed ({rc})")
+    return out
 
 
 def fptr(a: np.ndarray | None):

@@ -168,7 +168,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
-                                pattern_options=None):
+                                pattern_options=None, huckel=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -203,7 +203,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     patterns: a list of patterns for gaudi_amd.substructure.search (one more launch per 64 patterns, and
     one for their symmetry), with ``pattern_options`` = its keywords ``hydrogens`` / ``closed``.  The dict gains ``pattern_hits``
     bool [n,P] (rows of unbuilt molecules False) and ``pattern_fraction`` [P] = built molecules that contain the pattern / built
-    molecules (0.0 when none was built).  With ``patterns=None`` nothing changes and no launch is made."""
+    molecules (0.0 when none was built).  With ``patterns=None`` nothing changes and no launch is made.
+
+    huckel: one more call (gaudi_amd.huckel) solves the Hueckel problem of every built molecule.  The dict
+    gains ``huckel_gap``, an array over the BUILT molecules in list order with their HOMO-LUMO gap in |beta| (NaN where the status
+    is not OK), and ``huckel_open_shell_fraction`` = built molecules with an odd pi electron count / built molecules (0.0 when
+    none was built).  With ``huckel=False`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -211,6 +216,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     extra = {"bond_orders": True} if valence_check else {}
     if exact:
         extra["canonical"] = True
+    if huckel:
+        extra["huckel"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -253,6 +260,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         hits = hits & np.asarray(built, bool)[:, None]
         d["pattern_hits"] = hits
         d["pattern_fraction"] = hits.sum(0) / float(n_built) if n_built else np.zeros(hits.shape[1])
+    if huckel:
+        from ._lib import HUCKEL_OPEN_SHELL
+        rows = [r for r, ok in zip(recs, built) if ok]
+        d["huckel_gap"] = np.array([r["huckel_gap"] if r["huckel_status"] == 0 else np.nan for r in rows], np.float64)
+        d["huckel_open_shell_fraction"] = (sum(r["huckel_status"] == 0 and bool(r["huckel_flags"] & HUCKEL_OPEN_SHELL) for r in rows)
+                                           / float(n_built) if n_built else 0.0)
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

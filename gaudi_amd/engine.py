@@ -849,6 +849,23 @@ class Engine:
         self._check(rc, "gaudi_substructure_search")
         return out
 
+    def huckel_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_huckel since profile_reset(True): one launch per capacity tier present."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_huckel_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_huckel_profile_get")
+        return int(n.value), float(ms.value)
+
+    def huckel(self, tables, elem, n_atoms, bonds, n_bonds, charge=None):
+        """gaudi_huckel on packed arrays: a HuckelTables (gaudi_amd.huckel.c_huckel_tables), the molecules as bond_orders takes
+        them, charge [B] int32 or None -> dict of the raw output arrays (_lib.HUCKEL_ARRAYS: levels [B,128] float32, occupation
+        [B,128] uint8, n_pi / n_electrons / n_excluded / sweeps / flags / status [B] int32, homo / lumo / gap / e_pi [B] float32,
+        pi_charge [B,A] float32, pi_bond_order [B,M] float32, site_class [B,A] int8).  gaudi_amd.huckel.orbitals is the interface
+        on top."""
+        out = _lib.huckel_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_huckel(self.h, *_lib.huckel_args(tables, elem, n_atoms, bonds, n_bonds, charge, out))
+        self._check(rc, "gaudi_huckel")
+        return out
+
     def fp_library_set(self, fp=None):
         """gaudi_fp_library_set: keep fp [M,n_bins] uint8 on the device as THE resident library of this engine (None: free it)."""
         if fp is None:

@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -662,6 +662,73 @@ int gaudi_substructure_search(gaudi_handle* h, int n_elems, int h_elem, int c_el
 /* Number of gaudi_substructure_search launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events; uploads and
  * downloads are outside). */
 int gaudi_substructure_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
+/* ---- Hueckel molecular-orbital levels, gap, pi charges and pi bond orders (csrc/huckel.inc). ----
+ * The graph is the one of gaudi_canonical_order: vertices = the non-hydrogen atoms, each with its element, its H count (the listed H
+ * neighbours plus one for a carbon with exactly two bonds) and its heavy degree.  coordination = heavy degree + H count.
+ * tables->site_class[element][coordination 0..4] names a site class or -1: not a pi centre (left out of the matrix, counted in
+ * n_excluded; a coordination above 4 is never one).  A class has a Coulomb term h, an electron count n_e in {0, 1, 2} and a bond
+ * factor k.  In units of |beta| with alpha = 0, over the pi centres in ascending atom index: M_rr = h_r and, for bonded centres,
+ * M_rs = k_pair[class r][class s] where that is not NaN, else k_r * k_s.  An orbital's energy is alpha + x beta with beta < 0: the
+ * larger x, the lower the level.  n_electrons = sum of n_e - charge[b] (charge NULL: all zero); levels fill from the lowest energy,
+ * two to a level.
+ * Outputs per molecule b:
+ *   levels_out [B][GAUDI_HUCKEL_MAX_PI] fp32: x by ascending energy (descending x), zero padded; occupation_out the same shape, uint8.
+ *   n_pi_out, n_electrons_out, n_excluded_out, sweeps_out (Jacobi sweeps run), flags_out, status_out: [B] int32.
+ *   homo_out, lumo_out: for an even count, x of the last doubly occupied level and of the level after it; gap_out = homo - lumo in
+ *     |beta| (>= 0);
+ *     e_pi_out = sum of occupation * x.  An odd count leaves one singly occupied level: homo = lumo = that level, gap = 0,
+ *     GAUDI_HUCKEL_OPEN_SHELL.  With no electron at all both names go to the lowest level, with no empty level both to the highest.
+ *   GAUDI_HUCKEL_DEGENERATE: the last level holding an electron and the next level (which holds fewer) are closer than 1e-3: charges
+ *     and bond orders are returned but not unique.
+ *   pi_charge_out [B][A] fp32: n_e(r) - sum of occupation * v_r^2; zero on hydrogens and excluded atoms.
+ *   pi_bond_order_out [B][M] fp32: sum of occupation * v_r * v_s per listed bond; zero on bonds not between pi centres.
+ *   site_class_out [B][A] int8: -1 on hydrogens and excluded atoms.
+ * status: GAUDI_HUCKEL_OK; NOT_CONVERGED -- GAUDI_HUCKEL_MAX_SWEEPS sweeps left an off-diagonal element above 2^-24 (the results are
+ * what the last sweep left); BAD_INPUT / OVERFLOW / EMPTY with the meaning of their GAUDI_CANON_* namesakes, BAD_INPUT also for a
+ * charge that leaves fewer than 0 or more than 2 n_pi electrons, OVERFLOW also for more than GAUDI_HUCKEL_MAX_PI pi centres; NO_PI --
+ * no atom is a pi centre; BAD_TABLE -- n_classes outside 1..GAUDI_HUCKEL_MAX_CLASSES, a class index outside -1..n_classes-1, an n_e
+ * outside 0..2, a non-finite h or k, or k_pair[i][j] != k_pair[j][i] (every molecule of the call gets it).  Where a molecule is
+ * refused (every status but OK and NOT_CONVERGED) its rows are zero.
+ * One 64-lane wave per molecule; capacity tiers of 32, 64 and 128 pi centres by the molecule's heavy-atom count, one launch per tier
+ * present.  Individually rounded fp32 in a fixed order: the outputs are a function of the molecule's own arrays (never of the tier,
+ * the batch or its place in it) and bit for bit what gaudi_host_huckel returns.  B * max(A, M, 128) <= 2^31. */
+#define GAUDI_HUCKEL_MAX_PI 128
+#define GAUDI_HUCKEL_MAX_CLASSES 16
+#define GAUDI_HUCKEL_MAX_SWEEPS 30
+#define GAUDI_HUCKEL_OK 0
+#define GAUDI_HUCKEL_NOT_CONVERGED 1
+#define GAUDI_HUCKEL_BAD_INPUT 2
+#define GAUDI_HUCKEL_OVERFLOW 3
+#define GAUDI_HUCKEL_EMPTY 4
+#define GAUDI_HUCKEL_NO_PI 5
+#define GAUDI_HUCKEL_BAD_TABLE 6
+#define GAUDI_HUCKEL_OPEN_SHELL 1
+#define GAUDI_HUCKEL_DEGENERATE 2
+typedef struct gaudi_huckel_tables {
+  int32_t n_elems, h_elem, c_elem; /* the element list of the call's elem arrays; which entries are H and C */
+  int32_t n_classes;
+  int32_t site_class[8][5];        /* [element][coordination] -> class, -1: not a pi centre */
+  float h[GAUDI_HUCKEL_MAX_CLASSES];
+  int32_t n_e[GAUDI_HUCKEL_MAX_CLASSES];
+  float k[GAUDI_HUCKEL_MAX_CLASSES];
+  float k_pair[GAUDI_HUCKEL_MAX_CLASSES][GAUDI_HUCKEL_MAX_CLASSES]; /* NaN: use k[i] * k[j] */
+} gaudi_huckel_tables;
+int gaudi_huckel(gaudi_handle* h, const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem,
+                 const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, const int32_t* charge, float* levels_out,
+                 uint8_t* occupation_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                 int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out, float* gap_out,
+                 float* e_pi_out, float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out);
+/* gaudi_huckel without a handle: the same source text (csrc/huckel.inc: huckel_molecule) compiled for the host and run serially.
+ * Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_huckel(const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                      const int32_t* bonds, const int32_t* n_bonds, const int32_t* charge, float* levels_out,
+                      uint8_t* occupation_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                      int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out,
+                      float* gap_out, float* e_pi_out, float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out);
+/* Number of gaudi_huckel launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed
+ * duration (HIP events; uploads and downloads are outside). */
+int gaudi_huckel_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
