@@ -95,6 +95,16 @@ class HuckelTables(C.Structure):
     _fields_ = [("n_elems", C.c_int32), ("h_elem", C.c_int32), ("c_elem", C.c_int32), ("n_classes", C.c_int32),
                 ("site_class", (C.c_int32 * 5) * 8), ("h", C.c_float * 16), ("n_e", C.c_int32 * 16), ("k", C.c_float * 16),
                 ("k_pair", (C.c_float * 16) * 16)]
+# include/gaudi_hip.h: GAUDI_PPP_*
+PPP_MAX_ITERATIONS, PPP_OPEN_SHELL, PPP_BAD_GEOMETRY, PPP_DEGENERATE, PPP_SCF_CAP, PPP_JACOBI_CAP = 64, 7, 8, 2, 4, 8
+PPP_MATAGA_NISHIMOTO, PPP_OHNO = 0, 1
+
+
+class PPPTables(C.Structure):
+    """gaudi_ppp_tables (include/gaudi_hip.h)."""
+    _fields_ = [("n_elems", C.c_int32), ("h_elem", C.c_int32), ("c_elem", C.c_int32), ("n_classes", C.c_int32),
+                ("site_class", (C.c_int32 * 5) * 8), ("I", C.c_float * 16), ("gamma", C.c_float * 16), ("z", C.c_int32 * 16),
+                ("k", C.c_float * 16), ("beta0", C.c_float), ("beta_pair", (C.c_float * 16) * 16)]
 
 FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
@@ -174,6 +184,9 @@ EXPORTS = {
     "gaudi_huckel": (C.c_int, [C.c_void_p, C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [FP, U8P] + [IP] * 6 + [FP] * 6 + [C.POINTER(C.c_int8)]),
     "gaudi_host_huckel": (C.c_int, [C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [FP, U8P] + [IP] * 6 + [FP] * 6 + [C.POINTER(C.c_int8)]),
     "gaudi_huckel_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_ppp": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
+    "gaudi_host_ppp": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
+    "gaudi_ppp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -253,6 +266,7 @@ _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_n
                "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
+_PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get")  # ... and the PPP levels
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -281,7 +295,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -522,6 +536,47 @@ def host_huckel(tables, elem, n_atoms, bonds, n_bonds, charge=None) -> dict:
     rc = lib.gaudi_host_huckel(*huckel_args(tables, elem, n_atoms, bonds, n_bonds, charge, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_huckel failed ({rc})")
+    return out
+
+
+PPP_ARRAYS = ("levels", "occupation", "pi_charge", "pi_bond_order", "site_class", "n_pi", "n_electrons", "n_excluded", "iterations",
+              "sweeps", "flags", "status", "homo", "lumo", "gap", "e_electronic", "e_core", "delta_p")
+
+
+def ppp_outputs(B: int, A: int, M: int) -> dict:
+    """The eighteen output arrays of gaudi_ppp / gaudi_host_ppp, in argument order."""
+    out = dict(levels=np.zeros((B, HUCKEL_MAX_PI), np.float32), occupation=np.zeros((B, HUCKEL_MAX_PI), np.uint8),
+               pi_charge=np.zeros((B, A), np.float32), pi_bond_order=np.zeros((B, M), np.float32), site_class=np.zeros((B, A), np.int8))
+    out.update({k: np.zeros(B, np.int32) for k in PPP_ARRAYS[5:12]})
+    out.update({k: np.zeros(B, np.float32) for k in PPP_ARRAYS[12:]})
+    return out
+
+
+def ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out):
+    """The arguments both entry points share: the table, the molecules as bond_orders takes them, xyz [B,A,3] float32, charge [B]
+    int32 or None, the repulsion formula (PPP_MATAGA_NISHIMOTO / PPP_OHNO), the damping, the outputs."""
+    for a in (elem, n_atoms, bonds, n_bonds) + (() if charge is None else (charge,)):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.shape == (B, A, 3)
+    assert charge is None or charge.shape == (B,)
+    assert out["levels"].shape == (B, HUCKEL_MAX_PI) and out["pi_charge"].shape == (B, A) and out["pi_bond_order"].shape == (B, M)
+    ip = lambda a: a.ctypes.data_as(IP)
+    fp = lambda a: a.ctypes.data_as(FP)
+    return ((C.byref(tables), B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), fp(xyz), None if charge is None else ip(charge),
+             int(repulsion), float(damping), fp(out["levels"]), out["occupation"].ctypes.data_as(U8P), fp(out["pi_charge"]),
+             fp(out["pi_bond_order"]), out["site_class"].ctypes.data_as(C.POINTER(C.c_int8)))
+            + tuple(ip(out[k]) for k in PPP_ARRAYS[5:12]) + tuple(fp(out[k]) for k in PPP_ARRAYS[12:]))
+
+
+def host_ppp(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=PPP_MATAGA_NISHIMOTO, damping=0.25) -> dict:
+    """gaudi_host_ppp (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = ppp_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_ppp(*ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_ppp failed ({rc})")
     return out
 
 

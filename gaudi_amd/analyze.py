@@ -168,7 +168,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
-                                pattern_options=None, huckel=False):
+                                pattern_options=None, huckel=False, ppp=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -208,7 +208,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     huckel: one more call (gaudi_amd.huckel) solves the Hueckel problem of every built molecule.  The dict
     gains ``huckel_gap``, an array over the BUILT molecules in list order with their HOMO-LUMO gap in |beta| (NaN where the status
     is not OK), and ``huckel_open_shell_fraction`` = built molecules with an odd pi electron count / built molecules (0.0 when
-    none was built).  With ``huckel=False`` nothing changes and no launch is made."""
+    none was built).  With ``huckel=False`` nothing changes and no launch is made.
+
+    ppp: one more call (gaudi_amd.ppp) runs the PPP SCF of every built molecule on its built geometry.  The
+    dict gains ``ppp_gap``, an array over the BUILT molecules in list order with their HOMO-LUMO gap in eV (NaN where the status
+    is not OK), and ``ppp_not_converged_fraction`` = built molecules whose SCF did not converge / built molecules (0.0 when none
+    was built).  With ``ppp=False`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -218,6 +223,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["canonical"] = True
     if huckel:
         extra["huckel"] = True
+    if ppp:
+        extra["ppp"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -266,6 +273,10 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         d["huckel_gap"] = np.array([r["huckel_gap"] if r["huckel_status"] == 0 else np.nan for r in rows], np.float64)
         d["huckel_open_shell_fraction"] = (sum(r["huckel_status"] == 0 and bool(r["huckel_flags"] & HUCKEL_OPEN_SHELL) for r in rows)
                                            / float(n_built) if n_built else 0.0)
+    if ppp:
+        rows = [r for r, ok in zip(recs, built) if ok]
+        d["ppp_gap"] = np.array([r["ppp_gap"] if r["ppp_status"] == 0 else np.nan for r in rows], np.float64)
+        d["ppp_not_converged_fraction"] = sum(r["ppp_status"] == 1 for r in rows) / float(n_built) if n_built else 0.0
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

@@ -16,7 +16,7 @@
 //      pairs with the dummy index idle.  Per round one lane per pair computes the rotation from a_pp, a_qq, a_pq; all lanes apply
 //      the row updates; after a fence the column updates of A and V.  Every element is written by exactly one lane from values the
 //      phase before completed.  A sweep starts while max |off-diagonal| > 2^-24 (a maximum has no order); kHuckelSweeps sweeps
-//      without getting there is NOT_CONVERGED;
+//      without getting there is NOT_CONVERGED (jacobi_sweeps below: ppp.inc runs the same routine inside its SCF loop);
 //   3. levels are NOT read off the Jacobi diagonal (it drifts with every rotation): lane i takes the Rayleigh quotient of column i
 //      of V with the sparse matrix the molecule started from, rows ascending, a row's bonds in adjacency order, and normalises
 //      the column;
@@ -81,11 +81,101 @@ struct HuckelParams {
 
 __host__ __device__ __forceinline__ int huckel_bits(float f) { return __builtin_bit_cast(int, f); }
 
+// Cyclic two-sided Jacobi on the symmetric n x n matrix in s.a, the rotations accumulated into s.v (the caller sets it to I),
+// on the round-robin schedule of the header; S is any work space with a, v and the rotation arrays of HuckelSmem (ppp.inc has
+// one).  A sweep starts while max |off-diagonal| > threshold; true: it got there within kHuckelSweeps sweeps.  `sweeps` gains
+// the sweeps run.  Every lane of the wave calls it with the same n and threshold.
+template <int P, class S>
+__host__ __device__ inline bool jacobi_sweeps(S& s, int n, int lane, float threshold, int& sweeps) {
+#pragma clang fp contract(off)
+  static_assert((P & (P - 1)) == 0 && P <= kHuckelMaxPi, "a work item splits into (pair, index) by a shift");
+  const int m = n + (n & 1), half = m >> 1, rounds = m - 1;
+  constexpr int kShift = P == 128 ? 7 : P == 64 ? 6 : P == 32 ? 5 : P == 16 ? 4 : -1;
+  static_assert(kShift > 0, "capacity tiers are 16, 32, 64, 128");
+  int done = 0;
+  bool converged = false;
+  for (;;) {
+    float off = 0.0f;
+    for (int r = lane; r < n; r += kRwLanes)
+      for (int c = 0; c < r; ++c) {
+        const float t = fabsf(s.a[r][c]);
+        off = t > off ? t : off;
+      }
+    const int worst = -rw_min(-huckel_bits(off));  // non-negative floats order as their bits
+    if (worst <= huckel_bits(threshold)) {
+      converged = true;
+      break;
+    }
+    if (done == kHuckelSweeps) break;
+    for (int rd = 0; rd < rounds; ++rd) {
+      for (int j = lane; j < half; j += kRwLanes) {
+        const int pa = j == 0 ? m - 1 : (rd + j) % rounds, pb = j == 0 ? rd : (rd - j + rounds) % rounds;
+        const int p = pa < pb ? pa : pb, q = pa < pb ? pb : pa;
+        float c = 1.0f, sn = 0.0f, npp = 0.0f, nqq = 0.0f;
+        if (q < n) {
+          const float app = s.a[p][p], aqq = s.a[q][q], apq = s.a[p][q];
+          npp = app;
+          nqq = aqq;
+          if (apq != 0.0f) {
+            const float theta = (aqq - app) / (2.0f * apq);
+            float t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
+            t = theta < 0.0f ? -t : t;
+            c = 1.0f / sqrtf(t * t + 1.0f);
+            sn = t * c;
+            const float d = t * apq;
+            npp = app - d;
+            nqq = aqq + d;
+          }
+        }
+        s.rp[j] = (unsigned char)p;
+        s.rq[j] = (unsigned char)(q < n ? q : kCanonNone);
+        s.rc[j] = c;
+        s.rs[j] = sn;
+        s.rpp[j] = npp;
+        s.rqq[j] = nqq;
+      }
+      rw_fence();
+      for (int it = lane; it < half * P; it += kRwLanes) {  // rows p and q of J^T A
+        const int j = it >> kShift, k = it & (P - 1), q = s.rq[j];
+        if (k >= n || q == kCanonNone) continue;
+        const int p = s.rp[j];
+        const float c = s.rc[j], sn = s.rs[j], x = s.a[p][k], y = s.a[q][k];
+        s.a[p][k] = c * x - sn * y;
+        s.a[q][k] = sn * x + c * y;
+      }
+      rw_fence();
+      for (int it = lane; it < half * P; it += kRwLanes) {  // columns p and q of (J^T A) J and of V J
+        const int j = it >> kShift, k = it & (P - 1), q = s.rq[j];
+        if (k >= n || q == kCanonNone) continue;
+        const int p = s.rp[j];
+        const float c = s.rc[j], sn = s.rs[j], x = s.a[k][p], y = s.a[k][q];
+        float nx = c * x - sn * y, ny = sn * x + c * y;
+        if (k == p) {  // the pair's own 2 x 2 block in closed form: the element rotated away is zero, not rounding noise
+          nx = s.rpp[j];
+          ny = 0.0f;
+        }
+        if (k == q) {
+          nx = 0.0f;
+          ny = s.rqq[j];
+        }
+        s.a[k][p] = nx;
+        s.a[k][q] = ny;
+        const float vx = s.v[k][p], vy = s.v[k][q];
+        s.v[k][p] = c * vx - sn * vy;
+        s.v[k][q] = sn * vx + c * vy;
+      }
+      rw_fence();
+    }
+    ++done;
+  }
+  sweeps += done;
+  return converged;
+}
+
 // One molecule.  Every branch around a fence or a reduction is lane-uniform.
 template <int P>
 __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSmem<P>& s, int b, int lane) {
 #pragma clang fp contract(off)
-  static_assert((P & (P - 1)) == 0 && P <= kHuckelMaxPi, "a work item splits into (pair, index) by a shift");
   const int A = Q.in.A, M = Q.in.M;
   int H = 0, E = 0;
   const int gstatus = canon_graph(Q.in, s.g, b, lane, H, E);
@@ -163,85 +253,8 @@ __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSme
   }
   rw_fence();
   // ---- 2. Jacobi sweeps
-  const int m = n + (n & 1), half = m >> 1, rounds = m - 1;
-  constexpr int kShift = P == 128 ? 7 : P == 64 ? 6 : P == 32 ? 5 : P == 16 ? 4 : -1;
-  static_assert(kShift > 0, "capacity tiers are 16, 32, 64, 128");
   int sweeps = 0;
-  bool converged = false;
-  for (;;) {
-    float off = 0.0f;
-    for (int r = lane; r < n; r += kRwLanes)
-      for (int c = 0; c < r; ++c) {
-        const float t = fabsf(s.a[r][c]);
-        off = t > off ? t : off;
-      }
-    const int worst = -rw_min(-huckel_bits(off));  // non-negative floats order as their bits
-    if (worst <= huckel_bits(kHuckelOff)) {
-      converged = true;
-      break;
-    }
-    if (sweeps == kHuckelSweeps) break;
-    for (int rd = 0; rd < rounds; ++rd) {
-      for (int j = lane; j < half; j += kRwLanes) {
-        const int pa = j == 0 ? m - 1 : (rd + j) % rounds, pb = j == 0 ? rd : (rd - j + rounds) % rounds;
-        const int p = pa < pb ? pa : pb, q = pa < pb ? pb : pa;
-        float c = 1.0f, sn = 0.0f, npp = 0.0f, nqq = 0.0f;
-        if (q < n) {
-          const float app = s.a[p][p], aqq = s.a[q][q], apq = s.a[p][q];
-          npp = app;
-          nqq = aqq;
-          if (apq != 0.0f) {
-            const float theta = (aqq - app) / (2.0f * apq);
-            float t = 1.0f / (fabsf(theta) + sqrtf(theta * theta + 1.0f));
-            t = theta < 0.0f ? -t : t;
-            c = 1.0f / sqrtf(t * t + 1.0f);
-            sn = t * c;
-            const float d = t * apq;
-            npp = app - d;
-            nqq = aqq + d;
-          }
-        }
-        s.rp[j] = (unsigned char)p;
-        s.rq[j] = (unsigned char)(q < n ? q : kCanonNone);
-        s.rc[j] = c;
-        s.rs[j] = sn;
-        s.rpp[j] = npp;
-        s.rqq[j] = nqq;
-      }
-      rw_fence();
-      for (int it = lane; it < half * P; it += kRwLanes) {  // rows p and q of J^T A
-        const int j = it >> kShift, k = it & (P - 1), q = s.rq[j];
-        if (k >= n || q == kCanonNone) continue;
-        const int p = s.rp[j];
-        const float c = s.rc[j], sn = s.rs[j], x = s.a[p][k], y = s.a[q][k];
-        s.a[p][k] = c * x - sn * y;
-        s.a[q][k] = sn * x + c * y;
-      }
-      rw_fence();
-      for (int it = lane; it < half * P; it += kRwLanes) {  // columns p and q of (J^T A) J and of V J
-        const int j = it >> kShift, k = it & (P - 1), q = s.rq[j];
-        if (k >= n || q == kCanonNone) continue;
-        const int p = s.rp[j];
-        const float c = s.rc[j], sn = s.rs[j], x = s.a[k][p], y = s.a[k][q];
-        float nx = c * x - sn * y, ny = sn * x + c * y;
-        if (k == p) {  // the pair's own 2 x 2 block in closed form: the element rotated away is zero, not rounding noise
-          nx = s.rpp[j];
-          ny = 0.0f;
-        }
-        if (k == q) {
-          nx = 0.0f;
-          ny = s.rqq[j];
-        }
-        s.a[k][p] = nx;
-        s.a[k][q] = ny;
-        const float vx = s.v[k][p], vy = s.v[k][q];
-        s.v[k][p] = c * vx - sn * vy;
-        s.v[k][q] = sn * vx + c * vy;
-      }
-      rw_fence();
-    }
-    ++sweeps;
-  }
+  const bool converged = jacobi_sweeps<P>(s, n, lane, kHuckelOff, sweeps);
   // ---- 3. Rayleigh quotients with the matrix the molecule started from; columns normalised
   for (int i = lane; i < n; i += kRwLanes) {
     float num = 0.0f, den = 0.0f;
@@ -363,24 +376,31 @@ static int huckel_tier(int h_elem, int A, const int32_t* elem, int n) {
   return heavy <= 32 ? 0 : heavy <= 64 ? 1 : 2;
 }
 
-// the arguments both entry points share, checked; the table; the molecules of each tier, tier after tier in `mol`
+// the arguments the entry points share, checked; the molecules of each tier, tier after tier in `mol` (ppp.inc routes the same way)
+static int huckel_route(int n_elems, int h_elem, int c_elem, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                        const int32_t* bonds, const int32_t* n_bonds, std::vector<int>& mol, int (&tier_n)[3], const char** why) {
+  if (int rc = canon_prepare(n_elems, h_elem, c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, why)) return rc;
+  if ((long long)B * (A > M ? A : M) > (1ll << 31) || (long long)B * kHuckelMaxPi > (1ll << 31)) {
+    *why = "B * max(A, M, 128) beyond 2^31";
+    return GAUDI_E_CAPACITY;
+  }
+  std::vector<int> tier(B);
+  tier_n[0] = tier_n[1] = tier_n[2] = 0;
+  for (int b = 0; b < B; ++b) ++tier_n[tier[b] = huckel_tier(h_elem, A, elem + (size_t)b * A, n_atoms[b])];
+  int at[3] = {0, tier_n[0], tier_n[0] + tier_n[1]};
+  mol.resize(B);
+  for (int b = 0; b < B; ++b) mol[at[tier[b]]++] = b;
+  return GAUDI_OK;
+}
+
+// ... and the table
 static int huckel_prepare(const gaudi_huckel_tables* t, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
                           const int32_t* bonds, const int32_t* n_bonds, HuckelTab& tab, bool& table_ok, std::vector<int>& mol,
                           int (&tier_n)[3], const char** why) {
   *why = "invalid argument";
   if (!t) return GAUDI_E_INVALID;
-  if (int rc = canon_prepare(t->n_elems, t->h_elem, t->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, why)) return rc;
-  if ((long long)B * (A > M ? A : M) > (1ll << 31) || (long long)B * kHuckelMaxPi > (1ll << 31)) {
-    *why = "B * max(A, M, 128) beyond 2^31";
-    return GAUDI_E_CAPACITY;
-  }
+  if (int rc = huckel_route(t->n_elems, t->h_elem, t->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol, tier_n, why)) return rc;
   table_ok = huckel_table(t, tab);
-  std::vector<int> tier(B);
-  tier_n[0] = tier_n[1] = tier_n[2] = 0;
-  for (int b = 0; b < B; ++b) ++tier_n[tier[b] = huckel_tier(t->h_elem, A, elem + (size_t)b * A, n_atoms[b])];
-  int at[3] = {0, tier_n[0], tier_n[0] + tier_n[1]};
-  mol.resize(B);
-  for (int b = 0; b < B; ++b) mol[at[tier[b]]++] = b;
   return GAUDI_OK;
 }
 

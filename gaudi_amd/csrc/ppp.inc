@@ -1,0 +1,636 @@
+// ppp.inc -- Pariser-Parr-Pople self-consistent pi levels, gap, charges and bond orders in eV of a graph of atoms with coordinates
+// (included after huckel.inc at the end of gaudi_hip.hip; DESIGN.md section 8m; the model is spelled out in include/gaudi_hip.h).
+//
+// The pi centres are huckel.inc's: canon_graph, coordination = heavy degree + H count, the table's site classes, the centres
+// numbered in ascending atom index.  ONE text, two builds, as huckel.inc: a 64-lane wave per molecule on the device, one lane that
+// walks every index on the host (kRwLanes).  Per molecule:
+//   1. canon_graph; sites classified and compacted; per centre its coordinates, I, gamma, z and its (at most four) bonds with
+//      their beta in LDS; the geometry checked; H_rr and the core repulsion (both functions of the geometry alone);
+//   2. the SCF loop.  a = F(P), v = I; jacobi_sweeps (huckel.inc) diagonalises; the columns are normalised and ranked by the
+//      rotated diagonal; P_new = 2 sum over the occupied columns, delta_p = max |P_new - P|, P = (1 - damping) P_new + damping P;
+//   3. after the loop P = P_new of the last eigenvectors, a = F(P); the levels are the dense Rayleigh quotients v^T F v, ranked
+//      again; occupations, frontier, energies, charges and bond orders from these ranks.
+// gamma_rs is recomputed from the coordinates wherever it is needed (a sqrt and a division: n^2 per iteration against the solver's
+// n^3), and it is the same bits for (r, s) and (s, r): every operand pair enters a commutative operation.
+// WHERE P LIVES: a and v are 132 KB of the CU's 160 KB in the 128 tier, so P is a row of global scratch per workgroup, P * P floats.
+// Every loop that writes P_rc and every loop that reads it runs c over the lane's own columns (c = lane, lane + 64, ...), so a lane
+// only ever reads what it wrote itself and global memory needs no cross-lane ordering.  What every lane needs of P, its diagonal,
+// is kept in LDS (s.pd) behind rw_fence.  On the host the scratch is a vector.
+// Every fp32 operation is individually rounded (contraction off, correctly rounded / and sqrtf) and every sum runs in one fixed
+// order; delta_p and the diagonal maximum are reduced through their bits.  No atomics.  Every branch around a fence or a reduction
+// is lane-uniform.
+
+namespace gaudi {
+
+constexpr int kPppIterations = GAUDI_PPP_MAX_ITERATIONS;
+constexpr float kPppCoulomb = 14.397f;         // e^2 / (4 pi eps0) in eV Angstrom
+constexpr float kPppDeltaP = 1.52587890625e-5f;  // 2^-16
+constexpr float kPppTooClose2 = 0.25f;         // (0.5 Angstrom)^2
+constexpr float kPppDegenerate = 1e-3f;        // eV
+static_assert(GAUDI_PPP_OPEN_SHELL > GAUDI_HUCKEL_BAD_TABLE && GAUDI_PPP_BAD_GEOMETRY > GAUDI_HUCKEL_BAD_TABLE &&
+                  GAUDI_PPP_DEGENERATE == GAUDI_HUCKEL_DEGENERATE,
+              "the shared statuses and flags keep gaudi_huckel's values");
+
+// the table as the kernel reads it (ppp_table builds it from gaudi_ppp_tables)
+struct PppTab {
+  int site_class[kCanonMaxElems][kHuckelCoords];  // -1: not a pi centre
+  int z[kHuckelMaxClasses];
+  float ion[kHuckelMaxClasses], gam[kHuckelMaxClasses];
+  float beta[kHuckelMaxClasses][kHuckelMaxClasses];  // the resonance integral of a bonded pair of classes
+};
+
+template <int P>
+struct PppSmem {
+  CanonSmem g;
+  float a[P][P + 1], v[P][P + 1];
+  float xyz[P][3], ion[P], gam[P], zc[P];  // per centre: coordinates, I, gamma, z
+  float hd[P], pd[P];                      // H_rr; P_rr
+  float bn[P][kHuckelNbr];                 // beta of a centre's bonds
+  float x[P], lev[P];                      // levels by column (and per-column partial sums); by rank
+  float rc[P / 2], rs[P / 2], rpp[P / 2], rqq[P / 2];  // jacobi_sweeps' rotations
+  unsigned char rp[P / 2], rq[P / 2];
+  unsigned char nb[P][kHuckelNbr];   // a centre's bonded centres, none-padded
+  unsigned char vert[P];             // pi centre -> vertex
+  unsigned char ord[P];              // rank -> column
+  signed char cls[P];
+  unsigned char pidx[kCanonMaxHeavy];  // vertex -> pi centre, none for an excluded atom
+  signed char vcls[kCanonMaxHeavy];    // vertex -> site class, -1 for an excluded atom
+};
+static_assert(sizeof(PppSmem<128>) <= 160 * 1024, "the largest tier fits the LDS of a CU");
+
+struct PppParams {
+  CanonParams in;  // the input fields only
+  const int* mol;  // the molecules of this launch (one capacity tier)
+  const int* charge;
+  const float* xyz;  // [B][A][3]
+  const PppTab* tab;
+  float* scratch;    // [workgroups of the launch][P * P]: the density matrix
+  int repulsion;
+  float damping;
+  float* levels;              // [B][kHuckelMaxPi]
+  unsigned char* occupation;  // [B][kHuckelMaxPi]
+  float* pi_charge;           // [B][A]
+  float* pi_bond_order;       // [B][M]
+  signed char* site_class;    // [B][A]
+  int *n_pi, *n_electrons, *n_excluded, *iterations, *sweeps, *flags, *status;  // [B]
+  float *homo, *lumo, *gap, *e_electronic, *e_core, *delta_p;                   // [B]
+};
+
+// gamma_rs, r != s: symmetric in its bits
+template <int P>
+__host__ __device__ __forceinline__ float ppp_gamma(const PppSmem<P>& s, int r, int c, int repulsion) {
+#pragma clang fp contract(off)
+  const float dx = s.xyz[r][0] - s.xyz[c][0], dy = s.xyz[r][1] - s.xyz[c][1], dz = s.xyz[r][2] - s.xyz[c][2];
+  const float d2 = (dx * dx + dy * dy) + dz * dz;
+  const float a = (2.0f * kPppCoulomb) / (s.gam[r] + s.gam[c]);
+  return repulsion == GAUDI_PPP_OHNO ? kPppCoulomb / sqrtf(d2 + a * a) : kPppCoulomb / (sqrtf(d2) + a);
+}
+
+// beta_rc: the bond list of centre c searched for r
+template <int P>
+__host__ __device__ __forceinline__ float ppp_beta(const PppSmem<P>& s, int r, int c) {
+  float b = 0.0f;
+  for (int d = 0; d < kHuckelNbr; ++d) b = s.nb[c][d] == r ? s.bn[c][d] : b;
+  return b;
+}
+
+// a = F(P) from the scratch row and s.pd.  The lane's own columns; the column's diagonal element from the same trip.
+template <int P>
+__host__ __device__ inline void ppp_fock(PppSmem<P>& s, const float* pm, int n, int lane, int repulsion) {
+#pragma clang fp contract(off)
+  for (int c = lane; c < n; c += kRwLanes) {
+    float coul = 0.0f;
+    for (int r = 0; r < n; ++r) {
+      if (r == c) continue;
+      const float g = ppp_gamma(s, r, c, repulsion);
+      coul = coul + (s.pd[r] - s.zc[r]) * g;
+      s.a[r][c] = ppp_beta(s, r, c) - 0.5f * pm[r * P + c] * g;
+    }
+    s.a[c][c] = (0.5f * s.pd[c] * s.gam[c] - s.ion[c]) + coul;
+  }
+}
+
+// One molecule; `pm` is its scratch row.  Every branch around a fence or a reduction is lane-uniform.
+template <int P>
+__host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, float* pm, int b, int lane) {
+#pragma clang fp contract(off)
+  const int A = Q.in.A, M = Q.in.M;
+  int H = 0, E = 0;
+  const int gstatus = canon_graph(Q.in, s.g, b, lane, H, E);
+  if (gstatus != GAUDI_CANON_OK) {
+    if (lane == 0) Q.status[b] = gstatus;
+    return;
+  }
+  const PppTab& T = *Q.tab;
+  // ---- 1. site classes; the pi centres numbered in ascending atom index (huckel.inc, step 1)
+  const int per = (H + kRwLanes - 1) / kRwLanes, lo = lane * per, hi = lo + per < H ? lo + per : H;
+  int cnt = 0, el = 0;
+  for (int v = lo; v < hi; ++v) {
+    const int label = s.g.label[v];
+    int coord = label & 7;
+    for (int k = 0; k < kCanonDeg; ++k) coord += s.g.adj[v][k] != kCanonNone;
+    const int c = coord < kHuckelCoords ? T.site_class[label >> 3][coord] : -1;
+    s.vcls[v] = (signed char)c;
+    cnt += c >= 0;
+    el += c >= 0 ? T.z[c] : 0;
+  }
+  int n, n_el;
+  int pos = rw_scan(cnt, lane, n);
+  (void)rw_scan(el, lane, n_el);
+  n_el -= Q.charge[b];
+  for (int v = lo; v < hi; ++v) {
+    const int c = s.vcls[v];
+    s.pidx[v] = (unsigned char)(c >= 0 && pos < P ? pos : kCanonNone);
+    if (c >= 0) {
+      if (pos < P) {
+        s.vert[pos] = (unsigned char)v;
+        s.cls[pos] = (signed char)c;
+      }
+      ++pos;
+    }
+  }
+  int refused = GAUDI_HUCKEL_OK;
+  if (n == 0) refused = GAUDI_HUCKEL_NO_PI;
+  else if (n > P) refused = GAUDI_HUCKEL_OVERFLOW;  // (the host sends a molecule to a tier that holds its heavy atoms: P is 128 here)
+  else if (n_el < 0 || n_el > 2 * n) refused = GAUDI_HUCKEL_BAD_INPUT;  // a charge the pi system cannot carry
+  else if (n_el & 1) refused = GAUDI_PPP_OPEN_SHELL;
+  if (refused != GAUDI_HUCKEL_OK) {
+    if (lane == 0) Q.status[b] = refused;
+    return;
+  }
+  rw_fence();
+  // ---- per centre: coordinates, parameters, bonds
+  bool bad = false;
+  for (int r = lane; r < n; r += kRwLanes) {
+    const int v = s.vert[r], cr = s.cls[r];
+    const float* at = Q.xyz + ((size_t)b * A + s.g.hv[v]) * 3;
+    for (int k = 0; k < 3; ++k) {
+      const float t = at[k];
+      bad = bad || (huckel_bits(t) & 0x7f800000) == 0x7f800000;  // infinite or not a number
+      s.xyz[r][k] = t;
+    }
+    s.ion[r] = T.ion[cr];
+    s.gam[r] = T.gam[cr];
+    s.zc[r] = (float)T.z[cr];
+    s.pd[r] = (float)T.z[cr];  // P starts as diag(z)
+    int d = 0;
+    for (int k = 0; k < kCanonDeg; ++k) {
+      const int o = s.g.adj[v][k];
+      if (o == kCanonNone) continue;
+      const int ps = s.pidx[o];
+      if (ps == kCanonNone) continue;
+      if (d < kHuckelNbr) {
+        s.nb[r][d] = (unsigned char)ps;
+        s.bn[r][d] = T.beta[cr][s.cls[ps]];
+      }
+      ++d;
+    }
+    for (; d < kHuckelNbr; ++d) {
+      s.nb[r][d] = (unsigned char)kCanonNone;
+      s.bn[r][d] = 0.0f;
+    }
+  }
+  rw_fence();
+  if (!rw_any(bad)) {
+    for (int c = lane; c < n; c += kRwLanes)
+      for (int r = 0; r < c; ++r) {
+        const float dx = s.xyz[r][0] - s.xyz[c][0], dy = s.xyz[r][1] - s.xyz[c][1], dz = s.xyz[r][2] - s.xyz[c][2];
+        bad = bad || !((dx * dx + dy * dy) + dz * dz >= kPppTooClose2);  // (an overflow to infinity passes: gamma_rs is then 0)
+      }
+    bad = rw_any(bad);
+  } else {
+    bad = true;
+  }
+  if (bad) {
+    if (lane == 0) Q.status[b] = GAUDI_PPP_BAD_GEOMETRY;
+    return;
+  }
+  // ---- H_rr and the core repulsion; P = diag(z) in the scratch row
+  const int repulsion = Q.repulsion;
+  for (int c = lane; c < n; c += kRwLanes) {
+    float att = 0.0f, rep = 0.0f;
+    for (int r = 0; r < n; ++r) {
+      pm[r * P + c] = r == c ? s.zc[c] : 0.0f;
+      if (r == c) continue;
+      const float g = ppp_gamma(s, r, c, repulsion);
+      att = att + s.zc[r] * g;
+      if (r < c) rep = rep + (s.zc[r] * s.zc[c]) * g;
+    }
+    s.hd[c] = -s.ion[c] - att;
+    s.x[c] = rep;
+  }
+  rw_fence();
+  float e_core = 0.0f;
+  if (lane == 0)
+    for (int c = 0; c < n; ++c) e_core = e_core + s.x[c];
+  rw_fence();
+  // ---- 2. the SCF loop
+  const int n_occ = n_el >> 1;
+  const float damping = Q.damping, fresh = 1.0f - damping;
+  float threshold = 0.0f, delta = 0.0f;
+  int iterations = 0, sweeps = 0;
+  bool converged = false, jacobi_ok = true;
+  for (;;) {
+    ppp_fock(s, pm, n, lane, repulsion);
+    for (int r = 0; r < n; ++r)
+      for (int c = lane; c < n; c += kRwLanes) s.v[r][c] = r == c ? 1.0f : 0.0f;
+    rw_fence();
+    if (iterations == 0) {  // the solver's threshold: 2^-24 of the largest |F_rr|, rounded up to a power of two
+      float big = 0.0f;
+      for (int r = lane; r < n; r += kRwLanes) {
+        const float t = fabsf(s.a[r][r]);
+        big = t > big ? t : big;
+      }
+      const int bits = -rw_min(-huckel_bits(big));
+      int e = (bits >> 23) + ((bits & 0x7fffff) != 0) - 24;  // the biased exponent of 2^-24 times that power of two
+      e = e < 1 ? 1 : e > 254 ? 254 : e;
+      threshold = __builtin_bit_cast(float, e << 23);
+    }
+    jacobi_ok = jacobi_sweeps<P>(s, n, lane, threshold, sweeps) && jacobi_ok;
+    ++iterations;
+    for (int i = lane; i < n; i += kRwLanes) {  // columns normalised; the level of a column: the rotated diagonal
+      float den = 0.0f;
+      for (int r = 0; r < n; ++r) {
+        const float vr = s.v[r][i];
+        den = den + vr * vr;
+      }
+      const float norm = sqrtf(den);
+      for (int r = 0; r < n; ++r) s.v[r][i] = s.v[r][i] / norm;
+      s.x[i] = s.a[i][i];
+    }
+    rw_fence();
+    for (int i = lane; i < n; i += kRwLanes) {
+      const float xi = s.x[i];
+      int rk = 0;
+      for (int j = 0; j < n; ++j) {
+        const float xj = s.x[j];
+        rk += xj < xi || (xj == xi && j < i);
+      }
+      s.ord[rk] = (unsigned char)i;
+    }
+    rw_fence();
+    float worst = 0.0f;
+    for (int c = lane; c < n; c += kRwLanes)
+      for (int r = 0; r < n; ++r) {
+        float acc = 0.0f;
+        for (int k = 0; k < n_occ; ++k) {
+          const int i = s.ord[k];
+          acc = acc + s.v[r][i] * s.v[c][i];
+        }
+        const float fresh_p = 2.0f * acc, old = pm[r * P + c], d = fabsf(fresh_p - old);
+        worst = d > worst ? d : worst;
+        const float mixed = fresh * fresh_p + damping * old;
+        pm[r * P + c] = mixed;
+        if (r == c) s.pd[c] = mixed;
+      }
+    delta = __builtin_bit_cast(float, -rw_min(-huckel_bits(worst)));
+    rw_fence();
+    converged = delta <= kPppDeltaP;
+    if (converged || iterations == kPppIterations) break;
+  }
+  // ---- 3. P = P_new of the last eigenvectors; a = F(P); levels = v^T F v
+  for (int c = lane; c < n; c += kRwLanes)
+    for (int r = 0; r < n; ++r) {
+      float acc = 0.0f;
+      for (int k = 0; k < n_occ; ++k) {
+        const int i = s.ord[k];
+        acc = acc + s.v[r][i] * s.v[c][i];
+      }
+      pm[r * P + c] = 2.0f * acc;
+      if (r == c) s.pd[c] = 2.0f * acc;
+    }
+  rw_fence();
+  ppp_fock(s, pm, n, lane, repulsion);
+  rw_fence();
+  for (int i = lane; i < n; i += kRwLanes) {
+    float num = 0.0f;
+    for (int r = 0; r < n; ++r) {
+      float row = 0.0f;
+      for (int c = 0; c < n; ++c) row = row + s.a[r][c] * s.v[c][i];
+      num = num + s.v[r][i] * row;
+    }
+    s.x[i] = num;
+  }
+  rw_fence();
+  for (int i = lane; i < n; i += kRwLanes) {
+    const float xi = s.x[i];
+    int rk = 0;
+    for (int j = 0; j < n; ++j) {
+      const float xj = s.x[j];
+      rk += xj < xi || (xj == xi && j < i);
+    }
+    const int oc = rk < n_occ ? 2 : 0;
+    s.ord[rk] = (unsigned char)i;
+    s.lev[rk] = xi;
+    Q.levels[(size_t)b * kHuckelMaxPi + rk] = xi;
+    Q.occupation[(size_t)b * kHuckelMaxPi + rk] = (unsigned char)oc;
+  }
+  rw_fence();
+  // the density of these ranks: the energy by columns, the charges from its diagonal
+  for (int c = lane; c < n; c += kRwLanes) {
+    float e = 0.0f;
+    for (int r = 0; r < n; ++r) {
+      float acc = 0.0f;
+      for (int k = 0; k < n_occ; ++k) {
+        const int i = s.ord[k];
+        acc = acc + s.v[r][i] * s.v[c][i];
+      }
+      const float p = 2.0f * acc, f = s.a[r][c];
+      e = e + p * ((r == c ? s.hd[c] : ppp_beta(s, r, c)) + f);
+      if (r == c) Q.pi_charge[(size_t)b * A + s.g.hv[s.vert[c]]] = s.zc[c] - p;
+    }
+    s.x[c] = e;
+  }
+  rw_fence();
+  if (lane == 0) {
+    int ih = n_occ - 1, il = n_occ;
+    if (ih < 0) ih = il;   // no electron: both names go to the lowest level
+    if (il >= n) il = ih;  // no empty level: both to the highest
+    int flags = 0;
+    if (n_occ >= 1 && n_occ < n && s.lev[n_occ] - s.lev[n_occ - 1] < kPppDegenerate) flags |= GAUDI_PPP_DEGENERATE;
+    if (!converged) flags |= GAUDI_PPP_SCF_CAP;
+    if (!jacobi_ok) flags |= GAUDI_PPP_JACOBI_CAP;
+    float e = 0.0f;
+    for (int c = 0; c < n; ++c) e = e + s.x[c];
+    Q.homo[b] = s.lev[ih];
+    Q.lumo[b] = s.lev[il];
+    Q.gap[b] = s.lev[il] - s.lev[ih];
+    Q.e_electronic[b] = 0.5f * e;
+    Q.e_core[b] = e_core;
+    Q.delta_p[b] = delta;
+    Q.n_pi[b] = n;
+    Q.n_electrons[b] = n_el;
+    Q.n_excluded[b] = H - n;
+    Q.iterations[b] = iterations;
+    Q.sweeps[b] = sweeps;
+    Q.flags[b] = flags;
+    Q.status[b] = converged && jacobi_ok ? GAUDI_HUCKEL_OK : GAUDI_HUCKEL_NOT_CONVERGED;
+  }
+  const int n_atoms = Q.in.n_atoms[b], n_bonds = Q.in.n_bonds[b];
+  for (int a = lane; a < n_atoms; a += kRwLanes) {
+    const int hv = s.g.hidx[a];
+    Q.site_class[(size_t)b * A + a] = (signed char)(hv == kCanonNone ? -1 : (int)s.vcls[hv]);
+  }
+  for (int k = lane; k < n_bonds; k += kRwLanes) {
+    const int hi_ = s.g.hidx[s.g.bl[k][0]], hj = s.g.hidx[s.g.bl[k][1]];
+    if (hi_ == kCanonNone || hj == kCanonNone) continue;
+    const int pr = s.pidx[hi_], ps = s.pidx[hj];
+    if (pr == kCanonNone || ps == kCanonNone) continue;
+    float acc = 0.0f;
+    for (int q = 0; q < n_occ; ++q) {
+      const int i = s.ord[q];
+      acc = acc + s.v[pr][i] * s.v[ps][i];
+    }
+    Q.pi_bond_order[(size_t)b * M + k] = 2.0f * acc;
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void ppp_kernel(const PppParams Q) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ppp_lds[];
+  ppp_molecule<P>(Q, *reinterpret_cast<PppSmem<P>*>(ppp_lds), Q.scratch + (size_t)blockIdx.x * (P * P), Q.mol[blockIdx.x],
+                  (int)threadIdx.x);
+}
+
+// The table and the call's two numbers checked and turned into what the kernel reads.  false: GAUDI_HUCKEL_BAD_TABLE.
+static bool ppp_table(const gaudi_ppp_tables* t, int repulsion, float damping, PppTab& out) {
+  memset(&out, 0, sizeof(out));
+  if (repulsion != GAUDI_PPP_MATAGA_NISHIMOTO && repulsion != GAUDI_PPP_OHNO) return false;
+  if (!(damping >= 0.0f && damping < 1.0f)) return false;
+  if (t->n_classes < 1 || t->n_classes > kHuckelMaxClasses || !std::isfinite(t->beta0)) return false;
+  for (int c = 0; c < t->n_classes; ++c) {
+    if (t->z[c] < 0 || t->z[c] > 2 || !std::isfinite(t->I[c]) || !std::isfinite(t->k[c]) || !std::isfinite(t->gamma[c]) ||
+        !(t->gamma[c] > 0.0f))
+      return false;
+    out.z[c] = t->z[c];
+    out.ion[c] = t->I[c];
+    out.gam[c] = t->gamma[c];
+  }
+  for (int e = 0; e < kCanonMaxElems; ++e)
+    for (int d = 0; d < kHuckelCoords; ++d) {
+      const int c = e < t->n_elems ? t->site_class[e][d] : -1;
+      if (c < -1 || c >= t->n_classes) return false;
+      out.site_class[e][d] = c;
+    }
+  for (int i = 0; i < t->n_classes; ++i)
+    for (int j = 0; j < t->n_classes; ++j) {
+#pragma clang fp contract(off)
+      const float ij = t->beta_pair[i][j], ji = t->beta_pair[j][i];
+      const bool hij = !std::isnan(ij), hji = !std::isnan(ji);
+      if ((hij && std::isinf(ij)) || (hij && hji && ij != ji)) return false;  // a listed pair is finite and the same both ways
+      out.beta[i][j] = hij ? ij : hji ? ji : t->beta0 * (t->k[i] * t->k[j]);
+    }
+  return true;
+}
+
+struct PppOut {
+  float* levels;
+  uint8_t* occupation;
+  float *pi_charge, *pi_bond_order;
+  int8_t* site_class;
+  int32_t *n_pi, *n_electrons, *n_excluded, *iterations, *sweeps, *flags, *status;
+  float *homo, *lumo, *gap, *e_electronic, *e_core, *delta_p;
+};
+constexpr int kPppOuts = 18, kPppStatusOut = 11;
+
+static void ppp_out_list(const PppOut& o, int B, int A, int M, void* (&p)[kPppOuts], size_t (&sz)[kPppOuts]) {
+  const size_t nB = (size_t)B;
+  void* ptrs[kPppOuts] = {o.levels, o.occupation, o.pi_charge, o.pi_bond_order, o.site_class, o.n_pi, o.n_electrons, o.n_excluded,
+                          o.iterations, o.sweeps, o.flags, o.status, o.homo, o.lumo, o.gap, o.e_electronic, o.e_core, o.delta_p};
+  const size_t sizes[kPppOuts] = {4 * nB * kHuckelMaxPi, nB * kHuckelMaxPi, 4 * nB * A, 4 * nB * M, nB * A, 4 * nB, 4 * nB, 4 * nB, 4 * nB,
+                                  4 * nB, 4 * nB, 4 * nB, 4 * nB, 4 * nB, 4 * nB, 4 * nB, 4 * nB, 4 * nB};
+  for (int i = 0; i < kPppOuts; ++i) {
+    p[i] = ptrs[i];
+    sz[i] = sizes[i];
+  }
+}
+
+static void ppp_params(PppParams& Q, const gaudi_ppp_tables* t, int B, int A, int M, int repulsion, float damping,
+                       void* (&outs)[kPppOuts]) {
+  Q.in.B = B;
+  Q.in.A = A;
+  Q.in.M = M;
+  Q.in.n_elems = t->n_elems;
+  Q.in.h_elem = t->h_elem;
+  Q.in.c_elem = t->c_elem;
+  Q.repulsion = repulsion;
+  Q.damping = damping;
+  Q.levels = (float*)outs[0];
+  Q.occupation = (unsigned char*)outs[1];
+  Q.pi_charge = (float*)outs[2];
+  Q.pi_bond_order = (float*)outs[3];
+  Q.site_class = (signed char*)outs[4];
+  Q.n_pi = (int*)outs[5];
+  Q.n_electrons = (int*)outs[6];
+  Q.n_excluded = (int*)outs[7];
+  Q.iterations = (int*)outs[8];
+  Q.sweeps = (int*)outs[9];
+  Q.flags = (int*)outs[10];
+  Q.status = (int*)outs[kPppStatusOut];
+  Q.homo = (float*)outs[12];
+  Q.lumo = (float*)outs[13];
+  Q.gap = (float*)outs[14];
+  Q.e_electronic = (float*)outs[15];
+  Q.e_core = (float*)outs[16];
+  Q.delta_p = (float*)outs[17];
+}
+
+template <int P>
+static int ppp_launch(gaudi_handle* h, PppParams Q, const int* mol, int count) {
+  if (count == 0) return GAUDI_OK;
+  Q.mol = mol;
+  constexpr int lds = (int)sizeof(PppSmem<P>);
+  {
+    // the attribute belongs to the function: one process-wide record per device (see the sampler's launch)
+    static std::mutex mu;
+    static std::map<int, bool> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!raised[h->device]) {
+      HIPCHECK(h, hipFuncSetAttribute((const void*)ppp_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      raised[h->device] = true;
+    }
+  }
+  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  if (h->prof) HIPCHECK(h, h->ppp_log.begin(h->stream, ev));
+  hipLaunchKernelGGL(ppp_kernel<P>, dim3(count), dim3(64), lds, h->stream, Q);
+  HIPCHECK(h, hipGetLastError());
+  if (h->prof) HIPCHECK(h, h->ppp_log.end(h->stream, ev));
+  return GAUDI_OK;
+}
+
+template <int P>
+static void ppp_host_tier(const PppParams& Q, const int* mol, int count) {
+  if (count == 0) return;
+  std::vector<PppSmem<P>> W(1);
+  std::vector<float> pm((size_t)P * P);
+  for (int i = 0; i < count; ++i) ppp_molecule<P>(Q, W[0], pm.data(), mol[i], 0);
+}
+
+}  // namespace gaudi
+
+#define GAUDI_PPP_ARGS                                                                                                           \
+  const gaudi_ppp_tables *tables, int B, int A, int M, const int32_t *elem, const int32_t *n_atoms, const int32_t *bonds,        \
+      const int32_t *n_bonds, const float *xyz, const int32_t *charge, int repulsion, float damping, float *levels_out,          \
+      uint8_t *occupation_out, float *pi_charge_out, float *pi_bond_order_out, int8_t *site_class_out, int32_t *n_pi_out,        \
+      int32_t *n_electrons_out, int32_t *n_excluded_out, int32_t *iterations_out, int32_t *sweeps_out, int32_t *flags_out,       \
+      int32_t *status_out, float *homo_out, float *lumo_out, float *gap_out, float *e_electronic_out, float *e_core_out,         \
+      float *delta_p_out
+#define GAUDI_PPP_OUT                                                                                                            \
+  gaudi::PppOut {                                                                                                                \
+    levels_out, occupation_out, pi_charge_out, pi_bond_order_out, site_class_out, n_pi_out, n_electrons_out, n_excluded_out,     \
+        iterations_out, sweeps_out, flags_out, status_out, homo_out, lumo_out, gap_out, e_electronic_out, e_core_out,            \
+        delta_p_out                                                                                                              \
+  }
+
+extern "C" int gaudi_ppp(gaudi_handle* h, GAUDI_PPP_ARGS) {
+  if (!h) return GAUDI_E_INVALID;
+  void* outs[gaudi::kPppOuts];
+  size_t osz[gaudi::kPppOuts];
+  gaudi::ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
+  for (void* p : outs)
+    if (!p) return fail(h, GAUDI_E_INVALID, "every output array is required");
+  if (!tables || !xyz) return fail(h, GAUDI_E_INVALID, "invalid argument");
+  const char* why = "";
+  std::vector<int> mol;
+  int tier_n[3];
+  if (int rc = gaudi::huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
+                                   tier_n, &why))
+    return fail(h, rc, why);
+  if (B == 0) return GAUDI_OK;
+  std::vector<gaudi::PppTab> tab(1);
+  if (!gaudi::ppp_table(tables, repulsion, damping, tab[0])) {  // nothing runs on a table that cannot be read: every row zero
+    for (int i = 0; i < gaudi::kPppOuts; ++i) memset(outs[i], 0, osz[i]);
+    for (int b = 0; b < B; ++b) status_out[b] = GAUDI_HUCKEL_BAD_TABLE;
+    return GAUDI_OK;
+  }
+  HIPCHECK(h, hipSetDevice(h->device));
+  const size_t nB = (size_t)B;
+  std::vector<int32_t> zero;
+  if (!charge) zero.assign(nB, 0);
+  constexpr int kIn = 8;
+  const size_t isz[kIn] = {sizeof(int) * nB * A, sizeof(int) * nB, sizeof(int) * nB * M * 2, sizeof(int) * nB, sizeof(int) * nB,
+                           sizeof(int) * nB,     sizeof(gaudi::PppTab), sizeof(float) * nB * A * 3};
+  const void* ins[kIn] = {elem, n_atoms, bonds, n_bonds, charge ? charge : zero.data(), mol.data(), tab.data(), xyz};
+  for (int i = 0; i < kIn; ++i) {
+    HIPCHECK(h, h->d_ppp[i].reserve(isz[i]));
+    HIPCHECK(h, hipMemcpyAsync(h->d_ppp[i].p, ins[i], isz[i], hipMemcpyHostToDevice, h->stream));
+  }
+  void* douts[gaudi::kPppOuts];
+  for (int i = 0; i < gaudi::kPppOuts; ++i) {  // a refused molecule writes its status only: zero everywhere else
+    HIPCHECK(h, h->d_ppp[kIn + i].reserve(osz[i]));
+    HIPCHECK(h, hipMemsetAsync(h->d_ppp[kIn + i].p, 0, osz[i], h->stream));
+    douts[i] = h->d_ppp[kIn + i].p;
+  }
+  // the density rows: the launches follow one another on the stream, so they share the largest tier's
+  size_t rows = 0;
+  const int cap[3] = {32, 64, 128};
+  for (int k = 0; k < 3; ++k) rows = std::max(rows, (size_t)tier_n[k] * cap[k] * cap[k]);
+  DevBuf& scratch = h->d_ppp[kIn + gaudi::kPppOuts];
+  HIPCHECK(h, scratch.reserve(sizeof(float) * rows));
+  gaudi::PppParams Q{};
+  gaudi::ppp_params(Q, tables, B, A, M, repulsion, damping, douts);
+  Q.in.elem = h->d_ppp[0].as<int>();
+  Q.in.n_atoms = h->d_ppp[1].as<int>();
+  Q.in.bonds = h->d_ppp[2].as<int>();
+  Q.in.n_bonds = h->d_ppp[3].as<int>();
+  Q.charge = h->d_ppp[4].as<int>();
+  Q.tab = h->d_ppp[6].as<gaudi::PppTab>();
+  Q.xyz = h->d_ppp[7].as<float>();
+  Q.scratch = scratch.as<float>();
+  const int* dmol = h->d_ppp[5].as<int>();
+  if (int rc = gaudi::ppp_launch<32>(h, Q, dmol, tier_n[0])) return rc;
+  if (int rc = gaudi::ppp_launch<64>(h, Q, dmol + tier_n[0], tier_n[1])) return rc;
+  if (int rc = gaudi::ppp_launch<128>(h, Q, dmol + tier_n[0] + tier_n[1], tier_n[2])) return rc;
+  for (int i = 0; i < gaudi::kPppOuts; ++i)
+    HIPCHECK(h, hipMemcpyAsync(outs[i], douts[i], osz[i], hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(h, hipStreamSynchronize(h->stream));
+  return GAUDI_OK;
+}
+
+extern "C" int gaudi_host_ppp(GAUDI_PPP_ARGS) {
+  void* outs[gaudi::kPppOuts];
+  size_t osz[gaudi::kPppOuts];
+  gaudi::ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
+  for (void* p : outs)
+    if (!p) return GAUDI_E_INVALID;
+  if (!tables || !xyz) return GAUDI_E_INVALID;
+  const char* why = "";
+  std::vector<int> mol;
+  int tier_n[3];
+  if (int rc = gaudi::huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
+                                   tier_n, &why))
+    return rc;
+  if (B == 0) return GAUDI_OK;
+  for (int i = 0; i < gaudi::kPppOuts; ++i) memset(outs[i], 0, osz[i]);
+  std::vector<gaudi::PppTab> tab(1);
+  if (!gaudi::ppp_table(tables, repulsion, damping, tab[0])) {
+    for (int b = 0; b < B; ++b) status_out[b] = GAUDI_HUCKEL_BAD_TABLE;
+    return GAUDI_OK;
+  }
+  std::vector<int32_t> zero;
+  if (!charge) zero.assign((size_t)B, 0);
+  gaudi::PppParams Q{};
+  gaudi::ppp_params(Q, tables, B, A, M, repulsion, damping, outs);
+  Q.in.elem = elem;
+  Q.in.n_atoms = n_atoms;
+  Q.in.bonds = bonds;
+  Q.in.n_bonds = n_bonds;
+  Q.charge = charge ? charge : zero.data();
+  Q.xyz = xyz;
+  Q.tab = tab.data();
+  gaudi::ppp_host_tier<32>(Q, mol.data(), tier_n[0]);
+  gaudi::ppp_host_tier<64>(Q, mol.data() + tier_n[0], tier_n[1]);
+  gaudi::ppp_host_tier<128>(Q, mol.data() + tier_n[0] + tier_n[1], tier_n[2]);
+  return GAUDI_OK;
+}
+#undef GAUDI_PPP_ARGS
+#undef GAUDI_PPP_OUT
+
+extern "C" int gaudi_ppp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms) {
+  if (!h || !n_launches || !total_ms) return GAUDI_E_INVALID;
+  HIPCHECK(h, hipStreamSynchronize(h->stream));
+  HIPCHECK(h, h->ppp_log.fold(0));
+  *n_launches = (int32_t)h->ppp_log.n;
+  *total_ms = h->ppp_log.ms;
+  return GAUDI_OK;
+}

@@ -866,6 +866,24 @@ class Engine:
         self._check(rc, "gaudi_huckel")
         return out
 
+    def ppp_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_ppp since profile_reset(True): one launch per capacity tier present."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_ppp_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_ppp_profile_get")
+        return int(n.value), float(ms.value)
+
+    def ppp(self, tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=0, damping=0.25):
+        """gaudi_ppp on packed arrays: a PPPTables (gaudi_amd.ppp.c_ppp_tables), the molecules as bond_orders takes them, xyz
+        [B,A,3] float32 in Angstrom, charge [B] int32 or None, the repulsion formula (0 Mataga-Nishimoto, 1 Ohno) and the damping
+        -> dict of the raw output arrays (_lib.PPP_ARRAYS: levels [B,128] float32 in eV, occupation [B,128] uint8, pi_charge [B,A],
+        pi_bond_order [B,M] float32, site_class [B,A] int8, n_pi / n_electrons / n_excluded / iterations / sweeps / flags / status
+        [B] int32, homo / lumo / gap / e_electronic / e_core / delta_p [B] float32).  gaudi_amd.ppp.orbitals is the interface on
+        top."""
+        out = _lib.ppp_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_ppp(self.h, *_lib.ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out))
+        self._check(rc, "gaudi_ppp")
+        return out
+
     def fp_library_set(self, fp=None):
         """gaudi_fp_library_set: keep fp [M,n_bins] uint8 on the device as THE resident library of this engine (None: free it)."""
         if fp is None:

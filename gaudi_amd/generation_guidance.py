@@ -53,7 +53,8 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 
 
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
-           valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None, huckel=False):
+           valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None, huckel=False,
+           ppp=False):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -71,7 +72,10 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     ``contains`` bool [B,P] -- which designed molecules hold which motif, False where the molecule was not built.  With
     ``patterns=None`` no search is launched.  huckel (with with_atoms): one more call (gaudi_amd.huckel.gap)
     and the dict gains ``huckel_gap`` float64 [B], the Hueckel HOMO-LUMO gap of every molecule in |beta| next to the predictor's
-    values (NaN where the molecule was not built or not solved).  With ``huckel=False`` nothing is launched."""
+    values (NaN where the molecule was not built or not solved).  With ``huckel=False`` nothing is launched.  ppp (with with_atoms):
+    one more call (gaudi_amd.ppp.frontier) and the dict gains ``ppp_gap``, ``ppp_ip`` and ``ppp_ea`` float64
+    [B]: the PPP HOMO-LUMO gap and the Koopmans ionisation potential and electron affinity of every molecule in eV, on its built
+    geometry (NaN where the molecule was not built or not solved).  With ``ppp=False`` nothing is launched."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
@@ -81,12 +85,12 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-                     with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel)
+                     with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel, ppp)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
                  n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None, patterns=None,
-                 pattern_options=None, huckel=False):
+                 pattern_options=None, huckel=False, ppp=False):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -96,7 +100,8 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     The guidance window is one per call: settings whose windows differ are refused.  Returns one design()-shaped dict per setting, evaluated
     as design() does; ``seconds`` is the ONE call's time, ``molecules_per_second`` the whole call's rate.  similarity /
     train_library: as design takes them; every setting gets its own ``diversity``.  patterns / pattern_options: as design takes
-    them; every setting gets its own ``contains``.  huckel: as design takes it; every setting gets its own ``huckel_gap``."""
+    them; every setting gets its own ``contains``.  huckel: as design takes it; every setting gets its own ``huckel_gap``.
+    ppp: as design takes it; every setting gets its own ``ppp_gap``, ``ppp_ip`` and ``ppp_ea``."""
     from .models_edm import ValueTarget
     model.eval()
     cond_predictor.eval()
@@ -147,7 +152,7 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
         lo, hi = j * bs, (j + 1) * bs
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
                       em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library, patterns,
-                      pattern_options, huckel)
+                      pattern_options, huckel, ppp)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
@@ -155,13 +160,13 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
            prop_dist=None, with_atoms=False, valence_check=False, similarity=False, patterns=None, pattern_options=None,
-           huckel=False):
+           huckel=False, ppp=False):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought.  similarity (with with_atoms): the seeds go
     through rings_to_atoms as well, and the dict gains ``diversity`` and ``similarity_to_seed`` [B], the similarity of every
     refined molecule with its own seed (0.0 where either was not built): how far the refinement moved.  patterns /
-    pattern_options: as design takes them, on the refined molecules.  huckel: as design takes it, on the refined molecules."""
+    pattern_options: as design takes them, on the refined molecules.  huckel, ppp: as design takes them, on the refined molecules."""
     model.eval()
     cond_predictor.eval()
     bs, n_nodes = _to_numpy(x).shape[0], _to_numpy(x).shape[1]
@@ -174,7 +179,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     seconds = time() - start_time
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
-                    seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel)
+                    seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel, ppp)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     if similarity:
         from .similarity import fingerprints, rowwise_similarity
@@ -186,7 +191,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
 
 
 def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None,
-           patterns=None, pattern_options=None, huckel=False):
+           patterns=None, pattern_options=None, huckel=False, ppp=False):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -218,17 +223,22 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
     if huckel:
         from .huckel import gap
         out["huckel_gap"] = gap(recs, dataset, engine=engine)
+    if ppp:
+        from .ppp import frontier
+        out.update({"ppp_" + k: v for k, v in frontier(recs, dataset, engine=engine).items()})
     return out
 
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
               with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None, patterns=None,
-              pattern_options=None, huckel=False):
+              pattern_options=None, huckel=False, ppp=False):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     if patterns is not None and not with_atoms:
         raise ValueError("patterns need with_atoms=True")
     if huckel and not with_atoms:
         raise ValueError("huckel needs with_atoms=True")
+    if ppp and not with_atoms:
+        raise ValueError("ppp needs with_atoms=True")
     if (similarity or train_library is not None) and not with_atoms:
         raise ValueError("similarity / train_library need with_atoms=True")
     if train_library is not None and not similarity:
@@ -251,7 +261,7 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
                pred=_like_ref(pred), best=order, seconds=seconds, molecules_per_second=x.shape[0] / seconds)
     if with_atoms:
         out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library,
-                          patterns, pattern_options, huckel))
+                          patterns, pattern_options, huckel, ppp))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

@@ -142,7 +142,7 @@ def _is_packed(molecules) -> bool:
 
 
 def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
-                   canonical=False, huckel=False):
+                   canonical=False, huckel=False, ppp=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -161,7 +161,9 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     canon_orders, canon_charges and canon_n_charged: the structure of the molecule in its canonical numbering, the same for
     every numbering of the input (empty / EMPTY for a molecule without a numbering).  The other keys are left as they are.
     huckel: a call of gaudi_huckel (gaudi_amd.huckel) adds huckel_gap, huckel_homo, huckel_lumo (|beta|),
-    huckel_flags and huckel_status (gaudi_amd.huckel.STATUS_NAMES; 4 for a molecule that was not built) to every record."""
+    huckel_flags and huckel_status (gaudi_amd.huckel.STATUS_NAMES; 4 for a molecule that was not built) to every record.
+    ppp: a call of gaudi_ppp (gaudi_amd.ppp) on the records' atoms3d adds ppp_gap, ppp_homo, ppp_lumo (eV),
+    ppp_flags and ppp_status (gaudi_amd.ppp.STATUS_NAMES; 4 for a molecule that was not built) to every record."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -201,6 +203,10 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     if huckel:
         from .huckel import record_fields
         for rec, extra in zip(out, record_fields(out, dataset, engine=eng)):
+            rec.update(extra)
+    if ppp:
+        from .ppp import record_fields as ppp_fields
+        for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng)):
             rec.update(extra)
     return out
 

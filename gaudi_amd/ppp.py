@@ -1,0 +1,202 @@
+"""Pariser-Parr-Pople self-consistent pi levels, the HOMO-LUMO gap, Koopmans IP and EA, pi charges and pi bond orders of built
+molecules on the GPU, in eV (csrc/ppp.inc): what ``gaudi_amd.huckel`` leaves out -- geometry and electron
+repulsion -- on the same pi centres.
+
+The sites are huckel's: the graph of ``canonical``, coordination = heavy degree + H count, and ``sites`` maps (element,
+coordination) to a class or to "not a pi centre".  ``data/ppp_tables.json`` gives every class a valence-state ionisation energy
+``I``, a one-centre repulsion ``gamma`` (both eV), a core charge ``z`` (the electrons it contributes) and a bond factor ``k``;
+beta_rs = beta0 * k_r * k_s for bonded centres (or the ``beta_pair`` value), gamma_rs from the distance by the Mataga-Nishimoto or
+the Ohno formula, and a closed-shell SCF with damping (include/gaudi_hip.h spells the model out).  The table is data and its
+values are recalled, not verified: ``parameters=`` replaces any of it, and no accuracy in eV is claimed --
+``gaudi_amd.huckel.calibrate`` fits the line to a user's own reference values."""
+from __future__ import annotations
+
+import copy
+import json
+import os
+
+import numpy as np
+
+from ._lib import HUCKEL_MAX_CLASSES, PPP_DEGENERATE, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, GaudiError, PPPTables
+from .analyze import _engine
+from .huckel import _charges
+
+STATUS_NAMES = {0: "solved", 1: "not converged: 64 SCF iterations left delta_p above 2^-16, or a diagonalisation used 30 Jacobi sweeps "
+                   "(flags says which)",
+                2: "a bond index outside the atom list, a repeated bond, an element outside the table, or a charge the pi system "
+                   "cannot carry",
+                3: "more than 128 pi centres, 384 atoms, 192 heavy atoms or 384 bonds, or an atom with more than 8 bonds",
+                4: "no atoms (not built)", 5: "no atom is a pi centre", 6: "the parameter table, the damping or the repulsion formula "
+                   "cannot be used",
+                7: "open shell: an odd number of pi electrons", 8: "bad geometry: a non-finite coordinate on a pi centre, or two pi "
+                   "centres closer than 0.5 Angstrom"}
+REPULSIONS = {"mataga-nishimoto": PPP_MATAGA_NISHIMOTO, "ohno": PPP_OHNO}
+_SECTIONS = ("classes", "sites", "beta_pair", "beta0")
+_DEFAULT = None
+
+
+def default_parameters() -> dict:
+    """data/ppp_tables.json: {"beta0": eV, "classes": {name: {I, gamma, z, k}}, "sites": {element: {coordination: class}},
+    "beta_pair": {"a|b": eV}}."""
+    global _DEFAULT
+    if _DEFAULT is None:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "ppp_tables.json")) as f:
+            _DEFAULT = json.load(f)
+    return _DEFAULT
+
+
+def tables(dataset="cata", parameters=None) -> dict:
+    """The table one call uses, as a plain dict: the default, with ``parameters`` laid over it -- ``beta0`` replaced, ``classes``
+    entries merged field by field (a new name adds a class), ``sites`` per element and coordination (None: not a pi centre),
+    ``beta_pair`` per "classA|classB" key (None: back to the product).  Only the elements of ``dataset`` are kept."""
+    from .gor2goa import atoms_list
+    T = copy.deepcopy({k: default_parameters()[k] for k in _SECTIONS})
+    P = parameters or {}
+    unknown = set(P) - set(_SECTIONS)
+    if unknown:
+        raise GaudiError(f"ppp parameters: unknown section(s) {sorted(unknown)}")
+    if "beta0" in P:
+        T["beta0"] = float(P["beta0"])
+    for name, fields in P.get("classes", {}).items():
+        T["classes"].setdefault(name, {"I": 11.16, "gamma": 11.13, "z": 1, "k": 1.0}).update(fields)
+    for sym, by_coord in P.get("sites", {}).items():
+        T["sites"].setdefault(sym, {}).update({str(c): v for c, v in by_coord.items()})
+    T["beta_pair"].update(P.get("beta_pair", {}))
+    atoms = atoms_list(dataset)
+    T["sites"] = {sym: {c: v for c, v in by.items() if v is not None} for sym, by in T["sites"].items() if sym in atoms}
+    T["beta_pair"] = {k: v for k, v in T["beta_pair"].items() if v is not None}
+    T["atoms"] = list(atoms)
+    return T
+
+
+def c_ppp_tables(dataset="cata", parameters=None) -> PPPTables:
+    """gaudi_ppp_tables for one dataset: ``tables(dataset, parameters)`` in the order of ATOMS_LIST[dataset]."""
+    T = tables(dataset, parameters)
+    names = list(T["classes"])
+    if len(names) > HUCKEL_MAX_CLASSES:
+        raise GaudiError(f"ppp parameters: {len(names)} classes, at most {HUCKEL_MAX_CLASSES}")
+    t = PPPTables()
+    atoms = T["atoms"]
+    t.n_elems, t.h_elem, t.c_elem, t.n_classes, t.beta0 = len(atoms), atoms.index("H"), atoms.index("C"), len(names), float(T["beta0"])
+    for e in range(8):
+        for c in range(5):
+            t.site_class[e][c] = -1
+    for sym, by_coord in T["sites"].items():
+        for coord, name in by_coord.items():
+            if not 0 <= int(coord) <= 4:
+                raise GaudiError(f"ppp parameters: coordination {coord} of {sym} outside 0..4")
+            if name not in names:
+                raise GaudiError(f"ppp parameters: site {sym}/{coord} names the unknown class {name!r}")
+            t.site_class[atoms.index(sym)][int(coord)] = names.index(name)
+    for i, name in enumerate(names):
+        c = T["classes"][name]
+        t.I[i], t.gamma[i], t.z[i], t.k[i] = float(c["I"]), float(c["gamma"]), int(c["z"]), float(c["k"])
+    for i in range(16):
+        for j in range(16):
+            t.beta_pair[i][j] = float("nan")
+    for key, value in T["beta_pair"].items():
+        a, _, b = key.partition("|")
+        if a not in names or b not in names:
+            raise GaudiError(f"ppp parameters: beta_pair {key!r} names an unknown class")
+        t.beta_pair[names.index(a)][names.index(b)] = t.beta_pair[names.index(b)][names.index(a)] = float(value)
+    return t
+
+
+def _repulsion(repulsion) -> int:
+    if repulsion not in REPULSIONS:
+        raise GaudiError(f"repulsion must be one of {sorted(REPULSIONS)}, got {repulsion!r}")
+    return REPULSIONS[repulsion]
+
+
+def _pack(molecules):
+    """Records (their atoms3d) or (atom_types, bonds, xyz) triples -> elem, n_atoms, bonds, n_bonds, xyz [B,A,3] float32."""
+    from .gor2goa import _np, _pack_atoms
+    graphs, coords = [], []
+    for i, mol in enumerate(molecules):
+        if isinstance(mol, dict):
+            if mol["status"] != 0:
+                graphs.append(mol)
+                coords.append(np.zeros((0, 3), np.float32))
+                continue
+            xyz = mol.get("atoms3d")
+            graphs.append(mol)
+        else:
+            xyz = mol[2] if len(mol) > 2 else None
+            graphs.append((mol[0], mol[1]))
+        if xyz is None:
+            raise GaudiError(f"molecule {i} has no coordinates: ppp needs atoms3d of a record or an (atom_types, bonds, xyz) triple")
+        coords.append(np.asarray(_np(xyz), np.float32).reshape(-1, 3))
+    elem, na, bonds, nb = _pack_atoms(graphs)
+    xyz = np.zeros(elem.shape + (3,), np.float32)
+    for i, c in enumerate(coords):
+        if len(c) != na[i]:
+            raise GaudiError(f"molecule {i}: {len(c)} coordinates for {na[i]} atoms")
+        xyz[i, :len(c)] = c
+    return elem, na, bonds, nb, xyz
+
+
+def _raw(molecules, dataset, charge, parameters, repulsion, damping, engine):
+    elem, na, bonds, nb, xyz = _pack(molecules)
+    raw = _engine(engine).ppp(c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)),
+                              _repulsion(repulsion), float(damping))
+    return raw, na, nb
+
+
+def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> list:
+    """One launch per capacity tier (32 / 64 / 128 pi centres) for the whole list.  ``molecules``: records of rings_to_atoms (their
+    ``atoms3d`` is the geometry) or ``(atom_types [n], bonds [m,2], xyz [n,3])`` triples in Angstrom, with or without placed
+    hydrogens; a molecule without coordinates raises.  ``charge``: one integer or one per molecule (n_electrons = sum of z - charge,
+    which must be even).  ``repulsion``: "mataga-nishimoto" or "ohno".  ``damping``: the share of the old density kept per
+    iteration, in [0, 1).  Returns one dict per molecule:
+      status         0 = solved (STATUS_NAMES); for every other status but 1 the values below are zero / empty
+      n_pi, n_electrons, n_excluded, iterations (SCF), sweeps (Jacobi, all iterations), delta_p (the last max |P_new - P|)
+      levels         [n_pi] float32, eV, ascending;  occupation: [n_pi] 0 or 2
+      homo, lumo, gap = lumo - homo, ip = -homo, ea = -lumo (Koopmans), e_electronic, e_core, e_total = their sum: eV
+      open_shell     status 7: an odd electron count, nothing solved
+      degenerate     the frontier levels are closer than 1e-3 eV: charges and bond orders are returned but not unique
+      flags          degenerate (2); why the status is 1: the iteration cap (4), a Jacobi solve at its cap (8)
+      pi_charge      [n] float32 = z - P_rr, zero on hydrogens and excluded atoms;  pi_bond_order: [m] float32, zero on bonds not
+                     between pi centres;  site_class: [n] index into ``tables(...)["classes"]``, -1 = none"""
+    molecules = list(molecules)
+    if not molecules:
+        return []
+    raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
+    out = []
+    for i in range(len(na)):
+        n = int(raw["n_pi"][i])
+        flags = int(raw["flags"][i])
+        rec = {k: int(raw[k][i]) for k in ("status", "n_pi", "n_electrons", "n_excluded", "iterations", "sweeps", "flags")}
+        rec.update({k: float(raw[k][i]) for k in ("homo", "lumo", "gap", "e_electronic", "e_core", "delta_p")})
+        rec.update(ip=-rec["homo"], ea=-rec["lumo"], e_total=rec["e_electronic"] + rec["e_core"],
+                   levels=raw["levels"][i, :n].copy(), occupation=raw["occupation"][i, :n].copy(),
+                   open_shell=rec["status"] == PPP_OPEN_SHELL, degenerate=bool(flags & PPP_DEGENERATE),
+                   pi_charge=raw["pi_charge"][i, :na[i]].copy(), pi_bond_order=raw["pi_bond_order"][i, :nb[i]].copy(),
+                   site_class=raw["site_class"][i, :na[i]].copy())
+        out.append(rec)
+    return out
+
+
+def gap(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> np.ndarray:
+    """float64 [B]: the HOMO-LUMO gap in eV, NaN where the status is not 0."""
+    return frontier(molecules, dataset, charge, parameters, repulsion, damping, engine)["gap"]
+
+
+def frontier(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
+    """One call -> {"gap", "ip", "ea"}: float64 [B] in eV (ip = -homo, ea = -lumo), NaN where the status is not 0."""
+    molecules = list(molecules)
+    if not molecules:
+        return dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
+    raw, _, _ = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
+    ok = raw["status"] == 0
+    return dict(gap=np.where(ok, raw["gap"].astype(np.float64), np.nan), ip=np.where(ok, -raw["homo"].astype(np.float64), np.nan),
+                ea=np.where(ok, -raw["lumo"].astype(np.float64), np.nan))
+
+
+def record_fields(molecules, dataset="cata", engine=None) -> list:
+    """What rings_to_atoms(..., ppp=True) adds to every record."""
+    molecules = list(molecules)
+    if not molecules:
+        return []
+    raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine)
+    return [dict(ppp_gap=float(raw["gap"][i]), ppp_homo=float(raw["homo"][i]), ppp_lumo=float(raw["lumo"][i]),
+                 ppp_flags=int(raw["flags"][i]), ppp_status=int(raw["status"][i])) for i in range(len(molecules))]

@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -729,6 +729,78 @@ int gaudi_host_huckel(const gaudi_huckel_tables* tables, int B, int A, int M, co
 /* Number of gaudi_huckel launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed
  * duration (HIP events; uploads and downloads are outside). */
 int gaudi_huckel_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
+/* ---- Pariser-Parr-Pople self-consistent pi levels, gap and charges in eV (csrc/ppp.inc). ----
+ * The pi centres are those of gaudi_huckel: the same graph, the same coordination rule, tables->site_class as there.  A class has a
+ * valence-state ionisation energy I (eV), a one-centre repulsion gamma (eV, > 0), a core charge z in {0, 1, 2} (the electrons it
+ * contributes) and a bond factor k.  Over the pi centres in ascending atom index, with xyz [B][A][3] fp32 in Angstrom:
+ *   beta_rs  = beta_pair[class r][class s] where that is not NaN, else beta0 * k_r * k_s, for bonded centres; 0 otherwise
+ *   gamma_rr = gamma_r;  a_rs = 2 * 14.397 / (gamma_r + gamma_s);  d2 = (dx * dx + dy * dy) + dz * dz
+ *   gamma_rs = 14.397 / (sqrt(d2) + a_rs)        repulsion = GAUDI_PPP_MATAGA_NISHIMOTO
+ *            = 14.397 / sqrt(d2 + a_rs * a_rs)   repulsion = GAUDI_PPP_OHNO
+ *   F_rr = -I_r + 1/2 P_rr gamma_rr + sum over s != r of (P_ss - z_s) gamma_rs;   F_rs = beta_rs - 1/2 P_rs gamma_rs
+ *   H_rr = -I_r - sum over s != r of z_s gamma_rs;   H_rs = beta_rs
+ * Closed shell: n_electrons = sum of z - charge[b] (charge NULL: all zero) must be even.  P starts as diag(z).  One iteration
+ * builds F(P), diagonalises it (the Jacobi routine of gaudi_huckel, its threshold 2^-24 times the largest |F_rr| of the first F
+ * rounded up to a power of two), ranks the levels by counting (ties: the smaller index first), fills the lowest n_electrons / 2,
+ * forms P_new = 2 sum over the occupied v v^T and delta_p = max |P_new - P|, and stops when delta_p <= 2^-16; otherwise
+ * P = (1 - damping) * P_new + damping * P.  GAUDI_PPP_MAX_ITERATIONS iterations without getting there is NOT_CONVERGED.
+ * Results, from the eigenvectors v of the last iteration (columns normalised) and F = F(their P_new):
+ *   levels_out [B][GAUDI_HUCKEL_MAX_PI] fp32: v^T F v in eV, ascending, zero padded; occupation_out the same shape, uint8 (0 or 2).
+ *   homo_out, lumo_out: the last filled level and the one after it (no electron: both the lowest level; no empty level: both the
+ *     highest); gap_out = lumo - homo >= 0.
+ *   e_electronic_out = 1/2 sum over r, s of P_rs (H_rs + F_rs);  e_core_out = sum over r < s of z_r z_s gamma_rs.
+ *   pi_charge_out [B][A] = z_r - P_rr, zero on hydrogens and excluded atoms; pi_bond_order_out [B][M] = P_rs per listed bond, zero
+ *     on bonds not between pi centres; site_class_out [B][A] int8, -1 on hydrogens and excluded atoms.
+ *   n_pi_out, n_electrons_out, n_excluded_out, iterations_out (SCF iterations run), sweeps_out (Jacobi sweeps, all iterations),
+ *     flags_out, status_out [B] int32; delta_p_out [B] fp32: the last iteration's.
+ *   flags: GAUDI_PPP_DEGENERATE -- lumo - homo below 1e-3 eV: charges and bond orders are returned but not unique;
+ *     GAUDI_PPP_SCF_CAP / GAUDI_PPP_JACOBI_CAP -- why the status is NOT_CONVERGED: the iteration cap, or a diagonalisation that
+ *     used GAUDI_HUCKEL_MAX_SWEEPS sweeps.
+ * status: the GAUDI_HUCKEL_* values with their meaning there, and GAUDI_PPP_OPEN_SHELL -- an odd electron count;
+ * GAUDI_PPP_BAD_GEOMETRY -- a non-finite coordinate on a pi centre, or two pi centres closer than 0.5 Angstrom (atoms that are
+ * not pi centres, template hydrogens at the origin among them, are not looked at).  BAD_TABLE (every molecule of the call) also for
+ * a non-finite or non-positive gamma, a non-finite I, k, beta0 or listed beta_pair, a z outside 0..2, damping outside [0, 1), and a
+ * repulsion that is neither formula.  Where a molecule is refused (every status but OK and NOT_CONVERGED) its rows are zero.
+ * One 64-lane wave per molecule, tiers and launches as gaudi_huckel; a, v in LDS, the density matrix in a per-workgroup row of
+ * global scratch that a lane reads only where it wrote.  Individually rounded fp32 in a fixed order: the outputs are a function
+ * of the molecule's own arrays and bit for bit what gaudi_host_ppp returns.  B * max(A, M, 128) <= 2^31. */
+#define GAUDI_PPP_MAX_ITERATIONS 64
+#define GAUDI_PPP_OPEN_SHELL 7
+#define GAUDI_PPP_BAD_GEOMETRY 8
+#define GAUDI_PPP_DEGENERATE 2
+#define GAUDI_PPP_SCF_CAP 4
+#define GAUDI_PPP_JACOBI_CAP 8
+#define GAUDI_PPP_MATAGA_NISHIMOTO 0
+#define GAUDI_PPP_OHNO 1
+typedef struct gaudi_ppp_tables {
+  int32_t n_elems, h_elem, c_elem; /* as gaudi_huckel_tables */
+  int32_t n_classes;
+  int32_t site_class[8][5];
+  float I[GAUDI_HUCKEL_MAX_CLASSES];
+  float gamma[GAUDI_HUCKEL_MAX_CLASSES];
+  int32_t z[GAUDI_HUCKEL_MAX_CLASSES];
+  float k[GAUDI_HUCKEL_MAX_CLASSES];
+  float beta0;
+  float beta_pair[GAUDI_HUCKEL_MAX_CLASSES][GAUDI_HUCKEL_MAX_CLASSES]; /* NaN: use beta0 * k[i] * k[j] */
+} gaudi_ppp_tables;
+int gaudi_ppp(gaudi_handle* h, const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+              const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge, int repulsion, float damping,
+              float* levels_out, uint8_t* occupation_out, float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out,
+              int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out, int32_t* iterations_out, int32_t* sweeps_out,
+              int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out, float* gap_out, float* e_electronic_out,
+              float* e_core_out, float* delta_p_out);
+/* gaudi_ppp without a handle: the same source text (csrc/ppp.inc: ppp_molecule) compiled for the host and run serially.  Test
+ * surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_ppp(const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                   const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge, int repulsion,
+                   float damping, float* levels_out, uint8_t* occupation_out, float* pi_charge_out, float* pi_bond_order_out,
+                   int8_t* site_class_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                   int32_t* iterations_out, int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out,
+                   float* lumo_out, float* gap_out, float* e_electronic_out, float* e_core_out, float* delta_p_out);
+/* Number of gaudi_ppp launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed duration
+ * (HIP events; uploads and downloads are outside). */
+int gaudi_ppp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
