@@ -98,6 +98,9 @@ class HuckelTables(C.Structure):
 # include/gaudi_hip.h: GAUDI_PPP_*
 PPP_MAX_ITERATIONS, PPP_OPEN_SHELL, PPP_BAD_GEOMETRY, PPP_DEGENERATE, PPP_SCF_CAP, PPP_JACOBI_CAP = 64, 7, 8, 2, 4, 8
 PPP_MATAGA_NISHIMOTO, PPP_OHNO = 0, 1
+PPP_CIS_MAX_WINDOW, PPP_CIS_MAX_STATES = 8, 64
+PPP_CIS_JACOBI_CAP, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE, PPP_CIS_TRIPLET_UNSTABLE = 16, 32, 64, 128
+PPP_CIS_FLAGS = PPP_CIS_JACOBI_CAP | PPP_CIS_TRUNCATED | PPP_CIS_WINDOW_EDGE | PPP_CIS_TRIPLET_UNSTABLE
 
 
 class PPPTables(C.Structure):
@@ -187,6 +190,9 @@ EXPORTS = {
     "gaudi_ppp": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
     "gaudi_host_ppp": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
     "gaudi_ppp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_ppp_cis": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
+    "gaudi_host_ppp_cis": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
+    "gaudi_ppp_cis_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -266,7 +272,7 @@ _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_n
                "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
-_PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get")  # ... and the PPP levels
+_PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -577,6 +583,39 @@ def host_ppp(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=
     rc = lib.gaudi_host_ppp(*ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_ppp failed ({rc})")
+    return out
+
+
+PPP_CIS_ARRAYS = ("singlet", "triplet", "osc", "dipole", "lead", "lead_weight", "n_states", "n_active_occ", "n_active_virt",
+                  "cis_sweeps")
+
+
+def ppp_cis_outputs(B: int) -> dict:
+    """The ten output arrays gaudi_ppp_cis / gaudi_host_ppp_cis add to gaudi_ppp's eighteen, in argument order."""
+    S = PPP_CIS_MAX_STATES
+    out = dict(singlet=np.zeros((B, S), np.float32), triplet=np.zeros((B, S), np.float32), osc=np.zeros((B, S), np.float32),
+               dipole=np.zeros((B, S, 3), np.float32), lead=np.zeros((B, S, 2), np.uint8), lead_weight=np.zeros((B, S), np.float32))
+    out.update({k: np.zeros(B, np.int32) for k in PPP_CIS_ARRAYS[6:]})
+    return out
+
+
+def ppp_cis_args(window, out):
+    """What follows ppp_args: the window and the ten CIS outputs."""
+    fp = lambda a: a.ctypes.data_as(FP)
+    return ((int(window),) + tuple(fp(out[k]) for k in PPP_CIS_ARRAYS[:4]) + (out["lead"].ctypes.data_as(U8P), fp(out["lead_weight"]))
+            + tuple(out[k].ctypes.data_as(IP) for k in PPP_CIS_ARRAYS[6:]))
+
+
+def host_ppp_cis(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=PPP_MATAGA_NISHIMOTO, damping=0.25,
+                 window=PPP_CIS_MAX_WINDOW) -> dict:
+    """gaudi_host_ppp_cis (needs no device): the two kernels' source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = ppp_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    out.update(ppp_cis_outputs(elem.shape[0]))
+    rc = lib.gaudi_host_ppp_cis(*(ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out)
+                                  + ppp_cis_args(window, out)))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_ppp_cis failed ({rc})")
     return out
 
 

@@ -168,7 +168,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
-                                pattern_options=None, huckel=False, ppp=False):
+                                pattern_options=None, huckel=False, ppp=False, ppp_cis=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -213,7 +213,13 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     ppp: one more call (gaudi_amd.ppp) runs the PPP SCF of every built molecule on its built geometry.  The
     dict gains ``ppp_gap``, an array over the BUILT molecules in list order with their HOMO-LUMO gap in eV (NaN where the status
     is not OK), and ``ppp_not_converged_fraction`` = built molecules whose SCF did not converge / built molecules (0.0 when none
-    was built).  With ``ppp=False`` nothing changes and no launch is made."""
+    was built).  With ``ppp=False`` nothing changes and no launch is made.
+
+    ppp_cis: the CIS stage on that ground state (gaudi_amd.ppp.excited_states; with ``ppp`` the same call).
+    The dict gains ``ppp_s1``, ``ppp_t1`` and ``ppp_bright``, arrays over the BUILT molecules in list order with the lowest singlet,
+    the lowest triplet and the lowest singlet with f >= 0.01 in eV (NaN where nothing was solved), and
+    ``ppp_triplet_unstable_fraction`` = built molecules whose lowest triplet lies at or below the closed-shell ground state / built
+    molecules (0.0 when none was built).  With ``ppp_cis=False`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -225,6 +231,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["huckel"] = True
     if ppp:
         extra["ppp"] = True
+    if ppp_cis:
+        extra["ppp_cis"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -277,6 +285,13 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         rows = [r for r, ok in zip(recs, built) if ok]
         d["ppp_gap"] = np.array([r["ppp_gap"] if r["ppp_status"] == 0 else np.nan for r in rows], np.float64)
         d["ppp_not_converged_fraction"] = sum(r["ppp_status"] == 1 for r in rows) / float(n_built) if n_built else 0.0
+    if ppp_cis:
+        from ._lib import PPP_CIS_TRIPLET_UNSTABLE
+        rows = [r for r, ok in zip(recs, built) if ok]
+        for k in ("ppp_s1", "ppp_t1", "ppp_bright"):
+            d[k] = np.array([r[k] for r in rows], np.float64)
+        d["ppp_triplet_unstable_fraction"] = (sum(bool(r["ppp_cis_flags"] & PPP_CIS_TRIPLET_UNSTABLE) for r in rows) / float(n_built)
+                                              if n_built else 0.0)
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

@@ -16,6 +16,8 @@
 // Every loop that writes P_rc and every loop that reads it runs c over the lane's own columns (c = lane, lane + 64, ...), so a lane
 // only ever reads what it wrote itself and global memory needs no cross-lane ordering.  What every lane needs of P, its diagonal,
 // is kept in LDS (s.pd) behind rw_fence.  On the host the scratch is a vector.
+// THE CIS STAGE (ppp_cis.inc, gaudi_ppp_cis) is a second kernel: with Q.cis set, a molecule that solved leaves what that stage
+// needs in a row of global scratch (ppp_cis_handover); with Q.cis null (gaudi_ppp) nothing is written and nothing changes.
 // Every fp32 operation is individually rounded (contraction off, correctly rounded / and sqrtf) and every sum runs in one fixed
 // order; delta_p and the diagonal maximum are reduced through their bits.  No atomics.  Every branch around a fence or a reduction
 // is lane-uniform.
@@ -27,6 +29,14 @@ constexpr float kPppCoulomb = 14.397f;         // e^2 / (4 pi eps0) in eV Angstr
 constexpr float kPppDeltaP = 1.52587890625e-5f;  // 2^-16
 constexpr float kPppTooClose2 = 0.25f;         // (0.5 Angstrom)^2
 constexpr float kPppDegenerate = 1e-3f;        // eV
+// The hand-over to the CIS stage (ppp_cis.inc): a row of global scratch per molecule, in floats.  n and n_occ as their bits, the
+// separation of the window's edge level from the level just outside it on either side (-1: no level outside), the centres'
+// coordinates and gamma, the active levels (0..7 occupied in ascending rank, 8..15 empty) and their eigenvector columns; behind
+// them the CIS stage's own stash of its two matrices.
+constexpr int kCisMaxWindow = GAUDI_PPP_CIS_MAX_WINDOW, kCisAct = 2 * kCisMaxWindow;
+constexpr int kCisXyz = 4, kCisGam = kCisXyz + 3 * kHuckelMaxPi, kCisEps = kCisGam + kHuckelMaxPi, kCisCoef = kCisEps + kCisAct;
+constexpr int kCisMatS = kCisCoef + kCisAct * kHuckelMaxPi, kCisMatT = kCisMatS + GAUDI_PPP_CIS_MAX_STATES * GAUDI_PPP_CIS_MAX_STATES;
+constexpr int kCisRow = kCisMatT + GAUDI_PPP_CIS_MAX_STATES * GAUDI_PPP_CIS_MAX_STATES;
 static_assert(GAUDI_PPP_OPEN_SHELL > GAUDI_HUCKEL_BAD_TABLE && GAUDI_PPP_BAD_GEOMETRY > GAUDI_HUCKEL_BAD_TABLE &&
                   GAUDI_PPP_DEGENERATE == GAUDI_HUCKEL_DEGENERATE,
               "the shared statuses and flags keep gaudi_huckel's values");
@@ -65,6 +75,8 @@ struct PppParams {
   const float* xyz;  // [B][A][3]
   const PppTab* tab;
   float* scratch;    // [workgroups of the launch][P * P]: the density matrix
+  float* cis;        // [B][kCisRow]: the hand-over to the CIS stage; null: none
+  int window;        // ... and its active window
   int repulsion;
   float damping;
   float* levels;              // [B][kHuckelMaxPi]
@@ -76,9 +88,9 @@ struct PppParams {
   float *homo, *lumo, *gap, *e_electronic, *e_core, *delta_p;                   // [B]
 };
 
-// gamma_rs, r != s: symmetric in its bits
-template <int P>
-__host__ __device__ __forceinline__ float ppp_gamma(const PppSmem<P>& s, int r, int c, int repulsion) {
+// gamma_rs, r != s: symmetric in its bits.  S is any work space with xyz and gam (ppp_cis.inc has one).
+template <class S>
+__host__ __device__ __forceinline__ float ppp_gamma(const S& s, int r, int c, int repulsion) {
 #pragma clang fp contract(off)
   const float dx = s.xyz[r][0] - s.xyz[c][0], dy = s.xyz[r][1] - s.xyz[c][1], dz = s.xyz[r][2] - s.xyz[c][2];
   const float d2 = (dx * dx + dy * dy) + dz * dz;
@@ -107,6 +119,34 @@ __host__ __device__ inline void ppp_fock(PppSmem<P>& s, const float* pm, int n, 
       s.a[r][c] = ppp_beta(s, r, c) - 0.5f * pm[r * P + c] * g;
     }
     s.a[c][c] = (0.5f * s.pd[c] * s.gam[c] - s.ion[c]) + coul;
+  }
+}
+
+// What the CIS stage needs of a solved molecule, written to its hand-over row (the layout above); s.ord and s.lev are the final ranks.
+template <int P>
+__host__ __device__ inline void ppp_cis_handover(const PppParams& Q, const PppSmem<P>& s, int b, int n, int n_occ, int lane) {
+#pragma clang fp contract(off)
+  float* row = Q.cis + (size_t)b * kCisRow;
+  const int W = Q.window, n_virt = n - n_occ;
+  const int n_o = n_occ < W ? n_occ : W, n_v = n_virt < W ? n_virt : W, first = n_occ - n_o, last = n_occ + n_v;
+  if (lane == 0) {
+    row[0] = __builtin_bit_cast(float, n);
+    row[1] = __builtin_bit_cast(float, n_occ);
+    row[2] = n_o > 0 && first > 0 ? s.lev[first] - s.lev[first - 1] : -1.0f;
+    row[3] = n_v > 0 && last < n ? s.lev[last] - s.lev[last - 1] : -1.0f;
+  }
+  for (int r = lane; r < n; r += kRwLanes) {
+    for (int k = 0; k < 3; ++k) row[kCisXyz + 3 * r + k] = s.xyz[r][k];
+    row[kCisGam + r] = s.gam[r];
+  }
+  for (int q = lane; q < kCisAct; q += kRwLanes) {
+    const int rank = q < kCisMaxWindow ? (q < n_o ? first + q : -1) : (q - kCisMaxWindow < n_v ? n_occ + q - kCisMaxWindow : -1);
+    row[kCisEps + q] = rank < 0 ? 0.0f : s.lev[rank];
+  }
+  for (int q = 0; q < kCisAct; ++q) {
+    const int rank = q < kCisMaxWindow ? (q < n_o ? first + q : -1) : (q - kCisMaxWindow < n_v ? n_occ + q - kCisMaxWindow : -1);
+    const int col = rank < 0 ? 0 : s.ord[rank];
+    for (int r = lane; r < n; r += kRwLanes) row[kCisCoef + q * kHuckelMaxPi + r] = rank < 0 ? 0.0f : s.v[r][col];
   }
 }
 
@@ -326,6 +366,7 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
     Q.occupation[(size_t)b * kHuckelMaxPi + rk] = (unsigned char)oc;
   }
   rw_fence();
+  if (Q.cis && converged && jacobi_ok) ppp_cis_handover(Q, s, b, n, n_occ, lane);
   // the density of these ranks: the energy by columns, the charges from its diagonal
   for (int c = lane; c < n; c += kRwLanes) {
     float e = 0.0f;
@@ -506,7 +547,29 @@ static void ppp_host_tier(const PppParams& Q, const int* mol, int count) {
   for (int i = 0; i < count; ++i) ppp_molecule<P>(Q, W[0], pm.data(), mol[i], 0);
 }
 
-}  // namespace gaudi
+// the ten outputs the CIS stage adds (ppp_cis.inc)
+struct CisOut {
+  float *singlet, *triplet, *osc, *dipole;
+  uint8_t* lead;
+  float* lead_weight;
+  int32_t *n_states, *n_active_occ, *n_active_virt, *cis_sweeps;
+};
+constexpr int kCisOuts = 10;
+
+static void cis_out_list(const CisOut& o, int B, void* (&p)[kCisOuts], size_t (&sz)[kCisOuts]) {
+  const size_t nB = (size_t)B, row = GAUDI_PPP_CIS_MAX_STATES;
+  void* ptrs[kCisOuts] = {o.singlet, o.triplet, o.osc, o.dipole, o.lead, o.lead_weight, o.n_states, o.n_active_occ, o.n_active_virt,
+                          o.cis_sweeps};
+  const size_t sizes[kCisOuts] = {4 * nB * row, 4 * nB * row, 4 * nB * row, 12 * nB * row, 2 * nB * row, 4 * nB * row, 4 * nB, 4 * nB,
+                                  4 * nB, 4 * nB};
+  for (int i = 0; i < kCisOuts; ++i) {
+    p[i] = ptrs[i];
+    sz[i] = sizes[i];
+  }
+}
+
+static int cis_device(gaudi_handle* h, const PppParams& Q, int B, void* (&douts)[kCisOuts]);  // ppp_cis.inc
+static void cis_host(const PppParams& Q, int B, void* (&outs)[kCisOuts]);
 
 #define GAUDI_PPP_ARGS                                                                                                           \
   const gaudi_ppp_tables *tables, int B, int A, int M, const int32_t *elem, const int32_t *n_atoms, const int32_t *bonds,        \
@@ -515,6 +578,13 @@ static void ppp_host_tier(const PppParams& Q, const int* mol, int count) {
       int32_t *n_electrons_out, int32_t *n_excluded_out, int32_t *iterations_out, int32_t *sweeps_out, int32_t *flags_out,       \
       int32_t *status_out, float *homo_out, float *lumo_out, float *gap_out, float *e_electronic_out, float *e_core_out,         \
       float *delta_p_out
+#define GAUDI_PPP_PASS                                                                                                           \
+  tables, B, A, M, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, levels_out, occupation_out, pi_charge_out,    \
+      pi_bond_order_out, site_class_out, n_pi_out, n_electrons_out, n_excluded_out, iterations_out, sweeps_out, flags_out,       \
+      status_out, homo_out, lumo_out, gap_out, e_electronic_out, e_core_out, delta_p_out
+#define GAUDI_PPP_CIS_ARGS                                                                                                       \
+  float *singlet_out, float *triplet_out, float *osc_out, float *dipole_out, uint8_t *lead_out, float *lead_weight_out,          \
+      int32_t *n_states_out, int32_t *n_active_occ_out, int32_t *n_active_virt_out, int32_t *cis_sweeps_out
 #define GAUDI_PPP_OUT                                                                                                            \
   gaudi::PppOut {                                                                                                                \
     levels_out, occupation_out, pi_charge_out, pi_bond_order_out, site_class_out, n_pi_out, n_electrons_out, n_excluded_out,     \
@@ -522,24 +592,34 @@ static void ppp_host_tier(const PppParams& Q, const int* mol, int count) {
         delta_p_out                                                                                                              \
   }
 
-extern "C" int gaudi_ppp(gaudi_handle* h, GAUDI_PPP_ARGS) {
+// gaudi_ppp (cis null) and gaudi_ppp_cis: the SCF launches, then the CIS launch on the same stream
+static int ppp_device(gaudi_handle* h, GAUDI_PPP_ARGS, const CisOut* cis, int window) {
   if (!h) return GAUDI_E_INVALID;
-  void* outs[gaudi::kPppOuts];
-  size_t osz[gaudi::kPppOuts];
-  gaudi::ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
+  void* outs[kPppOuts];
+  size_t osz[kPppOuts];
+  ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
   for (void* p : outs)
     if (!p) return fail(h, GAUDI_E_INVALID, "every output array is required");
+  void* couts[kCisOuts] = {};
+  size_t csz[kCisOuts] = {};
+  if (cis) {
+    cis_out_list(*cis, B > 0 ? B : 0, couts, csz);
+    for (void* p : couts)
+      if (!p) return fail(h, GAUDI_E_INVALID, "every output array is required");
+  }
   if (!tables || !xyz) return fail(h, GAUDI_E_INVALID, "invalid argument");
   const char* why = "";
   std::vector<int> mol;
   int tier_n[3];
-  if (int rc = gaudi::huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
-                                   tier_n, &why))
+  if (int rc = huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
+                            tier_n, &why))
     return fail(h, rc, why);
   if (B == 0) return GAUDI_OK;
-  std::vector<gaudi::PppTab> tab(1);
-  if (!gaudi::ppp_table(tables, repulsion, damping, tab[0])) {  // nothing runs on a table that cannot be read: every row zero
-    for (int i = 0; i < gaudi::kPppOuts; ++i) memset(outs[i], 0, osz[i]);
+  std::vector<PppTab> tab(1);
+  // nothing runs on a table that cannot be read, or with a window outside 1..8: every row zero
+  if (!ppp_table(tables, repulsion, damping, tab[0]) || (cis && (window < 1 || window > kCisMaxWindow))) {
+    for (int i = 0; i < kPppOuts; ++i) memset(outs[i], 0, osz[i]);
+    for (int i = 0; cis && i < kCisOuts; ++i) memset(couts[i], 0, csz[i]);
     for (int b = 0; b < B; ++b) status_out[b] = GAUDI_HUCKEL_BAD_TABLE;
     return GAUDI_OK;
   }
@@ -549,14 +629,14 @@ extern "C" int gaudi_ppp(gaudi_handle* h, GAUDI_PPP_ARGS) {
   if (!charge) zero.assign(nB, 0);
   constexpr int kIn = 8;
   const size_t isz[kIn] = {sizeof(int) * nB * A, sizeof(int) * nB, sizeof(int) * nB * M * 2, sizeof(int) * nB, sizeof(int) * nB,
-                           sizeof(int) * nB,     sizeof(gaudi::PppTab), sizeof(float) * nB * A * 3};
+                           sizeof(int) * nB,     sizeof(PppTab), sizeof(float) * nB * A * 3};
   const void* ins[kIn] = {elem, n_atoms, bonds, n_bonds, charge ? charge : zero.data(), mol.data(), tab.data(), xyz};
   for (int i = 0; i < kIn; ++i) {
     HIPCHECK(h, h->d_ppp[i].reserve(isz[i]));
     HIPCHECK(h, hipMemcpyAsync(h->d_ppp[i].p, ins[i], isz[i], hipMemcpyHostToDevice, h->stream));
   }
-  void* douts[gaudi::kPppOuts];
-  for (int i = 0; i < gaudi::kPppOuts; ++i) {  // a refused molecule writes its status only: zero everywhere else
+  void* douts[kPppOuts];
+  for (int i = 0; i < kPppOuts; ++i) {  // a refused molecule writes its status only: zero everywhere else
     HIPCHECK(h, h->d_ppp[kIn + i].reserve(osz[i]));
     HIPCHECK(h, hipMemsetAsync(h->d_ppp[kIn + i].p, 0, osz[i], h->stream));
     douts[i] = h->d_ppp[kIn + i].p;
@@ -565,52 +645,76 @@ extern "C" int gaudi_ppp(gaudi_handle* h, GAUDI_PPP_ARGS) {
   size_t rows = 0;
   const int cap[3] = {32, 64, 128};
   for (int k = 0; k < 3; ++k) rows = std::max(rows, (size_t)tier_n[k] * cap[k] * cap[k]);
-  DevBuf& scratch = h->d_ppp[kIn + gaudi::kPppOuts];
+  DevBuf& scratch = h->d_ppp[kIn + kPppOuts];
   HIPCHECK(h, scratch.reserve(sizeof(float) * rows));
-  gaudi::PppParams Q{};
-  gaudi::ppp_params(Q, tables, B, A, M, repulsion, damping, douts);
+  PppParams Q{};
+  ppp_params(Q, tables, B, A, M, repulsion, damping, douts);
   Q.in.elem = h->d_ppp[0].as<int>();
   Q.in.n_atoms = h->d_ppp[1].as<int>();
   Q.in.bonds = h->d_ppp[2].as<int>();
   Q.in.n_bonds = h->d_ppp[3].as<int>();
   Q.charge = h->d_ppp[4].as<int>();
-  Q.tab = h->d_ppp[6].as<gaudi::PppTab>();
+  Q.tab = h->d_ppp[6].as<PppTab>();
   Q.xyz = h->d_ppp[7].as<float>();
   Q.scratch = scratch.as<float>();
+  constexpr int kCisBuf = kIn + kPppOuts + 1;  // the hand-over rows, then the ten CIS outputs
+  void* dcis[kCisOuts] = {};
+  if (cis) {
+    HIPCHECK(h, h->d_ppp[kCisBuf].reserve(sizeof(float) * nB * kCisRow));
+    Q.cis = h->d_ppp[kCisBuf].as<float>();
+    Q.window = window;
+    for (int i = 0; i < kCisOuts; ++i) {
+      HIPCHECK(h, h->d_ppp[kCisBuf + 1 + i].reserve(csz[i]));
+      HIPCHECK(h, hipMemsetAsync(h->d_ppp[kCisBuf + 1 + i].p, 0, csz[i], h->stream));
+      dcis[i] = h->d_ppp[kCisBuf + 1 + i].p;
+    }
+  }
   const int* dmol = h->d_ppp[5].as<int>();
-  if (int rc = gaudi::ppp_launch<32>(h, Q, dmol, tier_n[0])) return rc;
-  if (int rc = gaudi::ppp_launch<64>(h, Q, dmol + tier_n[0], tier_n[1])) return rc;
-  if (int rc = gaudi::ppp_launch<128>(h, Q, dmol + tier_n[0] + tier_n[1], tier_n[2])) return rc;
-  for (int i = 0; i < gaudi::kPppOuts; ++i)
+  if (int rc = ppp_launch<32>(h, Q, dmol, tier_n[0])) return rc;
+  if (int rc = ppp_launch<64>(h, Q, dmol + tier_n[0], tier_n[1])) return rc;
+  if (int rc = ppp_launch<128>(h, Q, dmol + tier_n[0] + tier_n[1], tier_n[2])) return rc;
+  if (cis)
+    if (int rc = cis_device(h, Q, B, dcis)) return rc;
+  for (int i = 0; i < kPppOuts; ++i)
     HIPCHECK(h, hipMemcpyAsync(outs[i], douts[i], osz[i], hipMemcpyDeviceToHost, h->stream));
+  for (int i = 0; cis && i < kCisOuts; ++i)
+    HIPCHECK(h, hipMemcpyAsync(couts[i], dcis[i], csz[i], hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(h, hipStreamSynchronize(h->stream));
   return GAUDI_OK;
 }
 
-extern "C" int gaudi_host_ppp(GAUDI_PPP_ARGS) {
-  void* outs[gaudi::kPppOuts];
-  size_t osz[gaudi::kPppOuts];
-  gaudi::ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
+static int ppp_host(GAUDI_PPP_ARGS, const CisOut* cis, int window) {
+  void* outs[kPppOuts];
+  size_t osz[kPppOuts];
+  ppp_out_list(GAUDI_PPP_OUT, B > 0 ? B : 0, A, M, outs, osz);
   for (void* p : outs)
     if (!p) return GAUDI_E_INVALID;
+  void* couts[kCisOuts] = {};
+  size_t csz[kCisOuts] = {};
+  if (cis) {
+    cis_out_list(*cis, B > 0 ? B : 0, couts, csz);
+    for (void* p : couts)
+      if (!p) return GAUDI_E_INVALID;
+  }
   if (!tables || !xyz) return GAUDI_E_INVALID;
   const char* why = "";
   std::vector<int> mol;
   int tier_n[3];
-  if (int rc = gaudi::huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
-                                   tier_n, &why))
+  if (int rc = huckel_route(tables->n_elems, tables->h_elem, tables->c_elem, B, A, M, elem, n_atoms, bonds, n_bonds, mol,
+                            tier_n, &why))
     return rc;
   if (B == 0) return GAUDI_OK;
-  for (int i = 0; i < gaudi::kPppOuts; ++i) memset(outs[i], 0, osz[i]);
-  std::vector<gaudi::PppTab> tab(1);
-  if (!gaudi::ppp_table(tables, repulsion, damping, tab[0])) {
+  for (int i = 0; i < kPppOuts; ++i) memset(outs[i], 0, osz[i]);
+  for (int i = 0; cis && i < kCisOuts; ++i) memset(couts[i], 0, csz[i]);
+  std::vector<PppTab> tab(1);
+  if (!ppp_table(tables, repulsion, damping, tab[0]) || (cis && (window < 1 || window > kCisMaxWindow))) {
     for (int b = 0; b < B; ++b) status_out[b] = GAUDI_HUCKEL_BAD_TABLE;
     return GAUDI_OK;
   }
   std::vector<int32_t> zero;
   if (!charge) zero.assign((size_t)B, 0);
-  gaudi::PppParams Q{};
-  gaudi::ppp_params(Q, tables, B, A, M, repulsion, damping, outs);
+  PppParams Q{};
+  ppp_params(Q, tables, B, A, M, repulsion, damping, outs);
   Q.in.elem = elem;
   Q.in.n_atoms = n_atoms;
   Q.in.bonds = bonds;
@@ -618,13 +722,25 @@ extern "C" int gaudi_host_ppp(GAUDI_PPP_ARGS) {
   Q.charge = charge ? charge : zero.data();
   Q.xyz = xyz;
   Q.tab = tab.data();
-  gaudi::ppp_host_tier<32>(Q, mol.data(), tier_n[0]);
-  gaudi::ppp_host_tier<64>(Q, mol.data() + tier_n[0], tier_n[1]);
-  gaudi::ppp_host_tier<128>(Q, mol.data() + tier_n[0] + tier_n[1], tier_n[2]);
+  std::vector<float> rows;
+  if (cis) {
+    rows.assign((size_t)B * kCisRow, 0.0f);
+    Q.cis = rows.data();
+    Q.window = window;
+  }
+  ppp_host_tier<32>(Q, mol.data(), tier_n[0]);
+  ppp_host_tier<64>(Q, mol.data() + tier_n[0], tier_n[1]);
+  ppp_host_tier<128>(Q, mol.data() + tier_n[0] + tier_n[1], tier_n[2]);
+  if (cis) cis_host(Q, B, couts);
   return GAUDI_OK;
 }
-#undef GAUDI_PPP_ARGS
-#undef GAUDI_PPP_OUT
+
+}  // namespace gaudi
+
+extern "C" int gaudi_ppp(gaudi_handle* h, GAUDI_PPP_ARGS) { return gaudi::ppp_device(h, GAUDI_PPP_PASS, nullptr, 0); }
+
+extern "C" int gaudi_host_ppp(GAUDI_PPP_ARGS) { return gaudi::ppp_host(GAUDI_PPP_PASS, nullptr, 0); }
+// (the argument macros are ppp_cis.inc's too: it undefines them)
 
 extern "C" int gaudi_ppp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms) {
   if (!h || !n_launches || !total_ms) return GAUDI_E_INVALID;

@@ -884,6 +884,25 @@ class Engine:
         self._check(rc, "gaudi_ppp")
         return out
 
+    def ppp_cis_profile_get(self):
+        """(launches, summed milliseconds) of the CIS kernel of gaudi_ppp_cis since profile_reset(True): one launch per call (the
+        SCF launches of those calls are ppp_profile_get's)."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_ppp_cis_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_ppp_cis_profile_get")
+        return int(n.value), float(ms.value)
+
+    def ppp_cis(self, tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=0, damping=0.25, window=8):
+        """gaudi_ppp_cis on packed arrays: ``ppp``'s arguments and the active window (1..8) -> dict of ``ppp``'s eighteen arrays
+        (flags with the CIS bits) and _lib.PPP_CIS_ARRAYS: singlet / triplet / osc / lead_weight [B,64] float32, dipole [B,64,3]
+        float32, lead [B,64,2] uint8, n_states / n_active_occ / n_active_virt / cis_sweeps [B] int32.
+        gaudi_amd.ppp.excited_states is the interface on top."""
+        out = _lib.ppp_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        out.update(_lib.ppp_cis_outputs(elem.shape[0]))
+        rc = self.lib.gaudi_ppp_cis(self.h, *(_lib.ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out)
+                                              + _lib.ppp_cis_args(window, out)))
+        self._check(rc, "gaudi_ppp_cis")
+        return out
+
     def fp_library_set(self, fp=None):
         """gaudi_fp_library_set: keep fp [M,n_bins] uint8 on the device as THE resident library of this engine (None: free it)."""
         if fp is None:

@@ -142,7 +142,7 @@ def _is_packed(molecules) -> bool:
 
 
 def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
-                   canonical=False, huckel=False, ppp=False):
+                   canonical=False, huckel=False, ppp=False, ppp_cis=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -163,7 +163,11 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     huckel: a call of gaudi_huckel (gaudi_amd.huckel) adds huckel_gap, huckel_homo, huckel_lumo (|beta|),
     huckel_flags and huckel_status (gaudi_amd.huckel.STATUS_NAMES; 4 for a molecule that was not built) to every record.
     ppp: a call of gaudi_ppp (gaudi_amd.ppp) on the records' atoms3d adds ppp_gap, ppp_homo, ppp_lumo (eV),
-    ppp_flags and ppp_status (gaudi_amd.ppp.STATUS_NAMES; 4 for a molecule that was not built) to every record."""
+    ppp_flags and ppp_status (gaudi_amd.ppp.STATUS_NAMES; 4 for a molecule that was not built) to every record.
+    ppp_cis: a call of gaudi_ppp_cis (gaudi_amd.ppp.excited_states; window 8) adds ppp_s1, ppp_t1 (the lowest
+    singlet and triplet excitation energies, eV), ppp_s1_f (the oscillator strength of S1), ppp_bright (the lowest singlet with
+    f >= 0.01) -- NaN where nothing was solved -- and ppp_cis_flags (the GAUDI_PPP_CIS_* bits).  With ppp as well, the one call
+    serves both."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -204,9 +208,9 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
         from .huckel import record_fields
         for rec, extra in zip(out, record_fields(out, dataset, engine=eng)):
             rec.update(extra)
-    if ppp:
+    if ppp or ppp_cis:
         from .ppp import record_fields as ppp_fields
-        for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng)):
+        for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng, **({"ppp": bool(ppp), "ppp_cis": True} if ppp_cis else {}))):
             rec.update(extra)
     return out
 

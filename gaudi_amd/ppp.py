@@ -8,7 +8,11 @@ coordination) to a class or to "not a pi centre".  ``data/ppp_tables.json`` give
 beta_rs = beta0 * k_r * k_s for bonded centres (or the ``beta_pair`` value), gamma_rs from the distance by the Mataga-Nishimoto or
 the Ohno formula, and a closed-shell SCF with damping (include/gaudi_hip.h spells the model out).  The table is data and its
 values are recalled, not verified: ``parameters=`` replaces any of it, and no accuracy in eV is claimed --
-``gaudi_amd.huckel.calibrate`` fits the line to a user's own reference values."""
+``gaudi_amd.huckel.calibrate`` fits the line to a user's own reference values.
+
+``excited_states`` / ``optical`` / ``spectrum`` go one step further (csrc/ppp_cis.inc): configuration
+interaction over single excitations on that ground state, in an active window of at most 8 occupied and 8 empty levels -- the
+lowest singlet and triplet excitation energies, the singlet-triplet gap, oscillator strengths and the lowest bright singlet."""
 from __future__ import annotations
 
 import copy
@@ -17,7 +21,8 @@ import os
 
 import numpy as np
 
-from ._lib import HUCKEL_MAX_CLASSES, PPP_DEGENERATE, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, GaudiError, PPPTables
+from ._lib import (HUCKEL_MAX_CLASSES, PPP_CIS_FLAGS, PPP_CIS_JACOBI_CAP, PPP_CIS_TRIPLET_UNSTABLE, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE,
+                   PPP_DEGENERATE, PPP_JACOBI_CAP, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, PPP_SCF_CAP, GaudiError, PPPTables)
 from .analyze import _engine
 from .huckel import _charges
 
@@ -135,11 +140,25 @@ def _pack(molecules):
     return elem, na, bonds, nb, xyz
 
 
-def _raw(molecules, dataset, charge, parameters, repulsion, damping, engine):
+def _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, window=None):
+    """One gaudi_ppp call, or with a window one gaudi_ppp_cis call, for the list."""
     elem, na, bonds, nb, xyz = _pack(molecules)
-    raw = _engine(engine).ppp(c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)),
-                              _repulsion(repulsion), float(damping))
+    args = (c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)), _repulsion(repulsion), float(damping))
+    raw = _engine(engine).ppp(*args) if window is None else _engine(engine).ppp_cis(*args, int(window))
     return raw, na, nb
+
+
+def _orbital_record(raw, i, na, nb) -> dict:
+    n = int(raw["n_pi"][i])
+    flags = int(raw["flags"][i])
+    rec = {k: int(raw[k][i]) for k in ("status", "n_pi", "n_electrons", "n_excluded", "iterations", "sweeps", "flags")}
+    rec.update({k: float(raw[k][i]) for k in ("homo", "lumo", "gap", "e_electronic", "e_core", "delta_p")})
+    rec.update(ip=-rec["homo"], ea=-rec["lumo"], e_total=rec["e_electronic"] + rec["e_core"],
+               levels=raw["levels"][i, :n].copy(), occupation=raw["occupation"][i, :n].copy(),
+               open_shell=rec["status"] == PPP_OPEN_SHELL, degenerate=bool(flags & PPP_DEGENERATE),
+               pi_charge=raw["pi_charge"][i, :na[i]].copy(), pi_bond_order=raw["pi_bond_order"][i, :nb[i]].copy(),
+               site_class=raw["site_class"][i, :na[i]].copy())
+    return rec
 
 
 def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> list:
@@ -161,19 +180,7 @@ def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="ma
     if not molecules:
         return []
     raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
-    out = []
-    for i in range(len(na)):
-        n = int(raw["n_pi"][i])
-        flags = int(raw["flags"][i])
-        rec = {k: int(raw[k][i]) for k in ("status", "n_pi", "n_electrons", "n_excluded", "iterations", "sweeps", "flags")}
-        rec.update({k: float(raw[k][i]) for k in ("homo", "lumo", "gap", "e_electronic", "e_core", "delta_p")})
-        rec.update(ip=-rec["homo"], ea=-rec["lumo"], e_total=rec["e_electronic"] + rec["e_core"],
-                   levels=raw["levels"][i, :n].copy(), occupation=raw["occupation"][i, :n].copy(),
-                   open_shell=rec["status"] == PPP_OPEN_SHELL, degenerate=bool(flags & PPP_DEGENERATE),
-                   pi_charge=raw["pi_charge"][i, :na[i]].copy(), pi_bond_order=raw["pi_bond_order"][i, :nb[i]].copy(),
-                   site_class=raw["site_class"][i, :na[i]].copy())
-        out.append(rec)
-    return out
+    return [_orbital_record(raw, i, na, nb) for i in range(len(na))]
 
 
 def gap(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> np.ndarray:
@@ -192,11 +199,125 @@ def frontier(molecules, dataset="cata", charge=0, parameters=None, repulsion="ma
                 ea=np.where(ok, -raw["lumo"].astype(np.float64), np.nan))
 
 
-def record_fields(molecules, dataset="cata", engine=None) -> list:
-    """What rings_to_atoms(..., ppp=True) adds to every record."""
+def _frontier(raw) -> dict:
+    ok = _scf_status(raw) == 0
+    return dict(gap=np.where(ok, raw["gap"].astype(np.float64), np.nan), ip=np.where(ok, -raw["homo"].astype(np.float64), np.nan),
+                ea=np.where(ok, -raw["lumo"].astype(np.float64), np.nan))
+
+
+def _scf_status(raw) -> np.ndarray:
+    """The status gaudi_ppp alone gives: NOT_CONVERGED that only a CIS solve caused is OK."""
+    cis_only = (raw["status"] == 1) & ((raw["flags"] & (PPP_SCF_CAP | PPP_JACOBI_CAP)) == 0)
+    return np.where(cis_only, 0, raw["status"])
+
+
+def _optical(raw, f_min) -> dict:
+    """s1, t1, s1_f, bright, bright_f, st_gap as float64 [B] from the raw arrays of a gaudi_ppp_cis call."""
+    B = len(raw["status"])
+    have = (raw["status"] == 0) & (raw["n_states"] > 0)
+    pick = lambda a: np.where(have, a.astype(np.float64), np.nan)
+    live = np.arange(raw["osc"].shape[1])[None, :] < raw["n_states"][:, None]
+    lit = live & (raw["osc"] >= np.float32(f_min)) & have[:, None]
+    first = np.where(lit.any(1), lit.argmax(1), 0)
+    rows = np.arange(B)
+    s1, t1 = pick(raw["singlet"][:, 0]), pick(raw["triplet"][:, 0])
+    return dict(s1=s1, t1=t1, s1_f=pick(raw["osc"][:, 0]), bright=np.where(lit.any(1), raw["singlet"][rows, first].astype(np.float64), np.nan),
+                bright_f=np.where(lit.any(1), raw["osc"][rows, first].astype(np.float64), np.nan), st_gap=s1 - t1)
+
+
+def excited_states(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, window=8,
+                   engine=None) -> list:
+    """``orbitals`` and the CIS stage in one gaudi_ppp_cis call (the SCF launches, then one launch for every molecule).  ``window``:
+    the number of highest occupied and of lowest empty levels that take part, 1..8 (anything else: status 6 for every molecule).
+    Returns one dict per molecule with every key of ``orbitals`` (``flags`` carries the CIS bits too) and
+      n_states       n_active_occ * n_active_virt <= 64; 0 for a molecule without an electron or without an empty level
+      singlet, triplet   [n_states] float32, excitation energies in eV, ascending
+      osc, dipole    [n_states] oscillator strength and [n_states, 3] transition dipole (e Angstrom) of every singlet
+      lead, lead_weight   [n_states, 2] (occupied rank, empty rank) of a singlet's largest configuration and its weight X^2
+      s1, t1, s1_f, st_gap = s1 - t1   float, NaN without a state
+      cis_sweeps, n_active_occ, n_active_virt
+      cis_not_converged  a CIS diagonalisation used all its sweeps (status 1)
+      truncated      the window is smaller than the single-excitation space
+      window_edge    a level just outside the window within 1e-3 eV of the window's edge: the results depend on how a degenerate
+                     pair was oriented
+      triplet_unstable   t1 <= 0: the closed-shell ground state is not the lowest state (information, not an error)
+    A molecule whose status is not 0 has no states."""
     molecules = list(molecules)
     if not molecules:
         return []
-    raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine)
-    return [dict(ppp_gap=float(raw["gap"][i]), ppp_homo=float(raw["homo"][i]), ppp_lumo=float(raw["lumo"][i]),
-                 ppp_flags=int(raw["flags"][i]), ppp_status=int(raw["status"][i])) for i in range(len(molecules))]
+    raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, window)
+    opt = _optical(raw, 0.0)
+    out = []
+    for i in range(len(na)):
+        rec = _orbital_record(raw, i, na, nb)
+        k, flags = int(raw["n_states"][i]), rec["flags"]
+        rec.update({name: raw[name][i, :k].copy() for name in ("singlet", "triplet", "osc", "dipole", "lead", "lead_weight")})
+        rec.update({name: int(raw[name][i]) for name in ("n_states", "n_active_occ", "n_active_virt", "cis_sweeps")})
+        rec.update({name: float(opt[name][i]) for name in ("s1", "t1", "s1_f", "st_gap")})
+        rec.update(cis_not_converged=bool(flags & PPP_CIS_JACOBI_CAP), truncated=bool(flags & PPP_CIS_TRUNCATED),
+                   window_edge=bool(flags & PPP_CIS_WINDOW_EDGE), triplet_unstable=bool(flags & PPP_CIS_TRIPLET_UNSTABLE))
+        out.append(rec)
+    return out
+
+
+def optical(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, window=8, engine=None,
+            f_min=0.01) -> dict:
+    """One gaudi_ppp_cis call -> {"s1", "t1", "s1_f", "bright", "bright_f", "st_gap"}: float64 [B], energies in eV.  ``bright`` is
+    the lowest singlet with an oscillator strength of at least ``f_min`` (the optical gap) and ``bright_f`` its strength; NaN where
+    the status is not 0, there is no state, or no singlet is that bright."""
+    molecules = list(molecules)
+    if not molecules:
+        return {k: np.zeros(0) for k in ("s1", "t1", "s1_f", "bright", "bright_f", "st_gap")}
+    raw, _, _ = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, window)
+    return _optical(raw, f_min)
+
+
+def spectrum(states, grid_ev, width=0.3) -> np.ndarray:
+    """The absorption line shape of one ``excited_states`` record (or a list of them: their sum) on ``grid_ev``: every singlet a
+    normalised Gaussian of standard deviation ``width`` eV weighted by its oscillator strength.  Plain numpy on the host."""
+    grid = np.asarray(grid_ev, np.float64)
+    out = np.zeros(grid.shape, np.float64)
+    for rec in [states] if isinstance(states, dict) else list(states):
+        e, f = np.asarray(rec["singlet"], np.float64), np.asarray(rec["osc"], np.float64)
+        if len(e):
+            out += (f * np.exp(-0.5 * ((grid[..., None] - e) / width) ** 2)).sum(-1) / (width * np.sqrt(2.0 * np.pi))
+    return out
+
+
+def summary_fields(molecules, dataset="cata", engine=None, ppp=False, ppp_cis=True) -> dict:
+    """What design(..., ppp_cis=True) adds: {"ppp_s1", "ppp_t1", "ppp_bright"} float64 [B]; with ``ppp`` also ``frontier``'s
+    ppp_gap / ppp_ip / ppp_ea from the same call."""
+    molecules = list(molecules)
+    raw = None
+    if molecules:
+        raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, 8 if ppp_cis else None)
+    out = {}
+    if ppp:
+        front = _frontier(raw) if molecules else dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
+        out.update({"ppp_" + k: v for k, v in front.items()})
+    if ppp_cis:
+        opt = _optical(raw, 0.01) if molecules else {k: np.zeros(0) for k in ("s1", "t1", "bright")}
+        out.update({"ppp_" + k: opt[k] for k in ("s1", "t1", "bright")})
+    return out
+
+
+def record_fields(molecules, dataset="cata", engine=None, ppp=True, ppp_cis=False) -> list:
+    """What rings_to_atoms(..., ppp=True) adds to every record -- ppp_gap, ppp_homo, ppp_lumo, ppp_flags, ppp_status -- and / or
+    what ppp_cis=True adds -- ppp_s1, ppp_t1, ppp_s1_f, ppp_bright (eV; NaN without a solved state) and ppp_cis_flags; asked for
+    together, one gaudi_ppp_cis call serves both."""
+    molecules = list(molecules)
+    if not molecules:
+        return []
+    raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, 8 if ppp_cis else None)
+    out = [{} for _ in molecules]
+    if ppp:
+        status = _scf_status(raw)
+        for i, rec in enumerate(out):
+            rec.update(ppp_gap=float(raw["gap"][i]), ppp_homo=float(raw["homo"][i]), ppp_lumo=float(raw["lumo"][i]),
+                       ppp_flags=int(raw["flags"][i]) & ~PPP_CIS_FLAGS, ppp_status=int(status[i]))
+    if ppp_cis:
+        opt = _optical(raw, 0.01)
+        for i, rec in enumerate(out):
+            rec.update(ppp_s1=float(opt["s1"][i]), ppp_t1=float(opt["t1"][i]), ppp_s1_f=float(opt["s1_f"][i]),
+                       ppp_bright=float(opt["bright"][i]), ppp_cis_flags=int(raw["flags"][i]) & PPP_CIS_FLAGS)
+    return out

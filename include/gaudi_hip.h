@@ -802,6 +802,61 @@ int gaudi_host_ppp(const gaudi_ppp_tables* tables, int B, int A, int M, const in
  * (HIP events; uploads and downloads are outside). */
 int gaudi_ppp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- PPP-CIS excited states: S1, T1 and oscillator strengths (csrc/ppp_cis.inc). ----
+ * gaudi_ppp, then configuration interaction over single excitations on its ground state.  After a solve with status OK: the levels
+ * eps by rank, the normalised eigenvector columns C, n_occ = n_electrons / 2, n = n_pi, the centres' coordinates and gamma.
+ * Active window: window = W in 1..8 (any other value: BAD_TABLE for every molecule).  n_o = min(n_occ, W) highest occupied ranks,
+ * n_v = min(n - n_occ, W) lowest empty ranks, D = n_o * n_v <= 64 configurations (i -> a) ordered by (i ascending, a ascending).
+ * D = 0 (no electron, or no empty level): status OK, n_states = 0.
+ *   (ia|jb) = sum_r C_ri C_ra (sum_s gamma_rs C_sj C_sb);  (ij|ab) = sum_r C_ri C_rj (sum_s gamma_rs C_sa C_sb)
+ *   (gamma_rs as gaudi_ppp forms it, gamma_rr = gamma_r; r and s ascending; computed for ia <= jb and mirrored)
+ *   triplet matrix T[ia,jb] = delta_ij delta_ab (eps_a - eps_i) - (ij|ab);  singlet matrix S = T + 2 (ia|jb)
+ * Each is diagonalised by the Jacobi routine of gaudi_huckel on a 64-wide work space (threshold: 2^-24 of its largest |diagonal|
+ * rounded up to a power of two); the excitation energies are the dense Rayleigh quotients X^T M X of the normalised columns,
+ * ranked by counting (ties: the smaller index first):
+ *   singlet_out, triplet_out [B][64] fp32, eV, ascending, zero beyond n_states.
+ *   dipole_out [B][64][3], e Angstrom, of singlet k: sqrt2 sum_ia X_ia,k sum_r C_ri C_ra (x_r - x_0), x_0 the first pi centre.
+ *   osc_out [B][64] = (2 / 3) (E_k / 27.211386) |mu_k|^2 / 0.52917721^2.
+ *   lead_out [B][64][2] uint8: the (occupied rank, empty rank) of the largest X^2 of singlet k (ties: the smaller configuration),
+ *     lead_weight_out [B][64] that X^2.
+ *   n_states_out = D, n_active_occ_out = n_o, n_active_virt_out = n_v, cis_sweeps_out (both solves) [B] int32.
+ * The eighteen outputs of gaudi_ppp are written as gaudi_ppp writes them, bit for bit, except that flags_out gains
+ *   GAUDI_PPP_CIS_JACOBI_CAP -- a CIS solve used GAUDI_HUCKEL_MAX_SWEEPS sweeps; status_out becomes NOT_CONVERGED;
+ *   GAUDI_PPP_CIS_TRUNCATED -- D < n_occ * (n - n_occ): the window is smaller than the single-excitation space;
+ *   GAUDI_PPP_CIS_WINDOW_EDGE -- a level just outside the window within 1e-3 eV of the window's edge level: the results depend on
+ *     how the solver oriented a degenerate pair;
+ *   GAUDI_PPP_CIS_TRIPLET_UNSTABLE -- triplet[0] <= 0: the closed-shell ground state is not the lowest state (information).
+ * A molecule whose gaudi_ppp status is not OK keeps that status and has zero CIS rows.  One more launch after gaudi_ppp's, one
+ * 64-lane wave per molecule for all tiers; individually rounded fp32 in a fixed order: bit for bit what gaudi_host_ppp_cis returns. */
+#define GAUDI_PPP_CIS_MAX_WINDOW 8
+#define GAUDI_PPP_CIS_MAX_STATES 64
+#define GAUDI_PPP_CIS_JACOBI_CAP 16
+#define GAUDI_PPP_CIS_TRUNCATED 32
+#define GAUDI_PPP_CIS_WINDOW_EDGE 64
+#define GAUDI_PPP_CIS_TRIPLET_UNSTABLE 128
+int gaudi_ppp_cis(gaudi_handle* h, const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                  const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge, int repulsion,
+                  float damping, float* levels_out, uint8_t* occupation_out, float* pi_charge_out, float* pi_bond_order_out,
+                  int8_t* site_class_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                  int32_t* iterations_out, int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out,
+                  float* lumo_out, float* gap_out, float* e_electronic_out, float* e_core_out, float* delta_p_out, int window,
+                  float* singlet_out, float* triplet_out, float* osc_out, float* dipole_out, uint8_t* lead_out,
+                  float* lead_weight_out, int32_t* n_states_out, int32_t* n_active_occ_out, int32_t* n_active_virt_out,
+                  int32_t* cis_sweeps_out);
+/* gaudi_ppp_cis without a handle: the same source text compiled for the host and run serially.  Test surface, not a fallback. */
+int gaudi_host_ppp_cis(const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                       const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge, int repulsion,
+                       float damping, float* levels_out, uint8_t* occupation_out, float* pi_charge_out, float* pi_bond_order_out,
+                       int8_t* site_class_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                       int32_t* iterations_out, int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out,
+                       float* lumo_out, float* gap_out, float* e_electronic_out, float* e_core_out, float* delta_p_out, int window,
+                       float* singlet_out, float* triplet_out, float* osc_out, float* dipole_out, uint8_t* lead_out,
+                       float* lead_weight_out, int32_t* n_states_out, int32_t* n_active_occ_out, int32_t* n_active_virt_out,
+                       int32_t* cis_sweeps_out);
+/* Number of CIS launches (one per gaudi_ppp_cis call that reaches the device) since gaudi_profile_reset(h, 1) and their summed
+ * duration; the SCF launches of those calls are counted by gaudi_ppp_profile_get. */
+int gaudi_ppp_cis_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
