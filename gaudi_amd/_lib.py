@@ -75,6 +75,10 @@ ATOMS_MAX_BONDS = 384
 ATOMS_PLACE_H, ATOMS_FINGERPRINT = 1, 2
 
 BONDS_MAX_ATOMS, BONDS_MAX_HEAVY, BONDS_MAX_BONDS, BONDS_MAX_CHARGED = 384, 192, 384, 4  # include/gaudi_hip.h: GAUDI_BONDS_*
+# include/gaudi_hip.h: GAUDI_KEKULE_*
+KEKULE_BUDGET, KEKULE_MAX_SEL, KEKULE_MAX_EDGES = 1 << 20, 128, 192
+(KEKULE_OK, KEKULE_NO_KEKULE, KEKULE_NOT_NEUTRAL, KEKULE_NOT_CONNECTED, KEKULE_BAD_VALENCE, KEKULE_BAD_INPUT, KEKULE_OVERFLOW,
+ KEKULE_EMPTY, KEKULE_UNDECIDED) = range(9)
 (BONDS_OK, BONDS_NO_STRUCTURE, BONDS_CAPPED, BONDS_NOT_CONNECTED, BONDS_BAD_VALENCE, BONDS_BAD_INPUT, BONDS_OVERFLOW,
  BONDS_EMPTY, BONDS_GAVE_UP) = range(9)
 
@@ -113,6 +117,8 @@ FP = C.POINTER(C.c_float)
 IP = C.POINTER(C.c_int32)
 DP = C.POINTER(C.c_double)
 U8P = C.POINTER(C.c_uint8)
+U32P = C.POINTER(C.c_uint32)
+I64P = C.POINTER(C.c_int64)
 
 
 class TargetSpec(C.Structure):
@@ -193,6 +199,9 @@ EXPORTS = {
     "gaudi_ppp_cis": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_host_ppp_cis": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_ppp_cis_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_kekule": (C.c_int, [C.c_void_p, C.POINTER(ValenceTables)] + [C.c_int] * 3 + [IP] * 4 + [I64P, U32P, IP, IP, U32P, IP, IP, I64P, IP]),
+    "gaudi_host_kekule": (C.c_int, [C.POINTER(ValenceTables)] + [C.c_int] * 3 + [IP] * 4 + [I64P, U32P, IP, IP, U32P, IP, IP, I64P, IP]),
+    "gaudi_kekule_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -273,6 +282,7 @@ _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_n
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
 _PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
+_KEKULE_EXPORTS = ("gaudi_kekule", "gaudi_kekule_profile_get")  # ... and the Kekule structure counts
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -301,7 +311,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEKULE_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -383,6 +393,41 @@ def host_bond_orders(tables, elem, n_atoms, bonds, n_bonds) -> dict:
     rc = lib.gaudi_host_bond_orders(C.byref(tables), *bonds_args(elem, n_atoms, bonds, n_bonds, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_bond_orders failed ({rc})")
+    return out
+
+
+KEKULE_ARRAYS = ("k", "double_count", "n_hex", "hex_atoms", "sextet_count", "fries", "clar", "n_nodes", "status")
+
+
+def kekule_outputs(B: int, M: int) -> dict:
+    """The nine output arrays of gaudi_kekule / gaudi_host_kekule, in argument order."""
+    i32 = lambda: np.zeros(B, np.int32)  # noqa: E731
+    return dict(k=np.zeros(B, np.int64), double_count=np.zeros((B, M), np.uint32), n_hex=i32(),
+                hex_atoms=np.zeros((B, RINGS_MAX_RINGS, 6), np.int32), sextet_count=np.zeros((B, RINGS_MAX_RINGS), np.uint32),
+                fries=i32(), clar=i32(), n_nodes=np.zeros(B, np.int64), status=i32())
+
+
+def kekule_args(elem, n_atoms, bonds, n_bonds, out):
+    """The arguments both entry points share after the tables."""
+    for a in (elem, n_atoms, bonds, n_bonds):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert out["double_count"].shape == (B, M) and out["hex_atoms"].shape == (B, RINGS_MAX_RINGS, 6)
+    ip = lambda a: a.ctypes.data_as(IP)  # noqa: E731
+    u32 = lambda a: a.ctypes.data_as(U32P)  # noqa: E731
+    i64 = lambda a: a.ctypes.data_as(I64P)  # noqa: E731
+    return (B, A, M, ip(elem), ip(n_atoms), ip(bonds), ip(n_bonds), i64(out["k"]), u32(out["double_count"]), ip(out["n_hex"]),
+            ip(out["hex_atoms"]), u32(out["sextet_count"]), ip(out["fries"]), ip(out["clar"]), i64(out["n_nodes"]), ip(out["status"]))
+
+
+def host_kekule(tables, elem, n_atoms, bonds, n_bonds) -> dict:
+    """gaudi_host_kekule (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = kekule_outputs(elem.shape[0], bonds.shape[1])
+    rc = lib.gaudi_host_kekule(C.byref(tables), *kekule_args(elem, n_atoms, bonds, n_bonds, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_kekule failed ({rc})")
     return out
 
 

@@ -168,7 +168,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
-                                pattern_options=None, huckel=False, ppp=False, ppp_cis=False):
+                                pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -219,7 +219,13 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     The dict gains ``ppp_s1``, ``ppp_t1`` and ``ppp_bright``, arrays over the BUILT molecules in list order with the lowest singlet,
     the lowest triplet and the lowest singlet with f >= 0.01 in eV (NaN where nothing was solved), and
     ``ppp_triplet_unstable_fraction`` = built molecules whose lowest triplet lies at or below the closed-shell ground state / built
-    molecules (0.0 when none was built).  With ``ppp_cis=False`` nothing changes and no launch is made."""
+    molecules (0.0 when none was built).  With ``ppp_cis=False`` nothing changes and no launch is made.
+
+    aromaticity: one more launch (gaudi_amd.aromaticity) enumerates the Kekule structures of every built
+    molecule.  The dict gains ``mol_kekule_count`` and ``mol_clar``, int64 arrays over the BUILT molecules in list order (0 where
+    the status is not OK), and ``mean_log_kekule_per_center`` = the mean of ln(K) / (number of atoms that are not hydrogen) over
+    the built molecules with status OK (0.0 when there are none).  With ``aromaticity=False`` nothing changes and no launch is
+    made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -233,6 +239,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["ppp"] = True
     if ppp_cis:
         extra["ppp_cis"] = True
+    if aromaticity:
+        extra["aromaticity"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -292,6 +300,14 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
             d[k] = np.array([r[k] for r in rows], np.float64)
         d["ppp_triplet_unstable_fraction"] = (sum(bool(r["ppp_cis_flags"] & PPP_CIS_TRIPLET_UNSTABLE) for r in rows) / float(n_built)
                                               if n_built else 0.0)
+    if aromaticity:
+        from .gor2goa import atoms_list
+        h = atoms_list(dataset).index("H")
+        rows = [r for r, ok in zip(recs, built) if ok]
+        d["mol_kekule_count"] = np.array([r["kekule_count"] for r in rows], np.int64)
+        d["mol_clar"] = np.array([r["clar"] for r in rows], np.int64)
+        logs = [np.log(float(r["kekule_count"])) / float((np.asarray(r["atom_types"]) != h).sum()) for r in rows if r["resonance_status"] == 0]
+        d["mean_log_kekule_per_center"] = float(np.mean(logs)) if logs else 0.0
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

@@ -798,6 +798,22 @@ class Engine:
         self._check(rc, "gaudi_bond_orders")
         return out
 
+    def kekule_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_kekule since profile_reset(True)."""
+        n = C.c_int32()
+        ms = C.c_double()
+        self._check(self.lib.gaudi_kekule_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_kekule_profile_get")
+        return n.value, ms.value
+
+    def kekule(self, tables, elem, n_atoms, bonds, n_bonds):
+        """gaudi_kekule on packed arrays (as bond_orders takes them) -> dict of the raw output arrays (_lib.KEKULE_ARRAYS: k [B]
+        int64, double_count [B,M] uint32, n_hex [B], hex_atoms [B,32,6] int32, sextet_count [B,32] uint32, fries / clar [B],
+        n_nodes [B] int64, status [B]); gaudi_amd.aromaticity.resonance is the interface on top."""
+        out = _lib.kekule_outputs(elem.shape[0], bonds.shape[1])
+        rc = self.lib.gaudi_kekule(self.h, C.byref(tables), *_lib.kekule_args(elem, n_atoms, bonds, n_bonds, out))
+        self._check(rc, "gaudi_kekule")
+        return out
+
     def canon_profile_get(self):
         """(launches, summed milliseconds) of gaudi_canonical_order since profile_reset(True)."""
         n = C.c_int32()

@@ -142,7 +142,7 @@ def _is_packed(molecules) -> bool:
 
 
 def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
-                   canonical=False, huckel=False, ppp=False, ppp_cis=False):
+                   canonical=False, huckel=False, ppp=False, ppp_cis=False, aromaticity=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -167,7 +167,10 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     ppp_cis: a call of gaudi_ppp_cis (gaudi_amd.ppp.excited_states; window 8) adds ppp_s1, ppp_t1 (the lowest
     singlet and triplet excitation energies, eV), ppp_s1_f (the oscillator strength of S1), ppp_bright (the lowest singlet with
     f >= 0.01) -- NaN where nothing was solved -- and ppp_cis_flags (the GAUDI_PPP_CIS_* bits).  With ppp as well, the one call
-    serves both."""
+    serves both.
+    aromaticity: a launch of gaudi_kekule (gaudi_amd.aromaticity) adds kekule_count (the number of Kekule
+    structures), clar, fries, max_pauling_order (the largest double_count / kekule_count of a bond; NaN where nothing was counted)
+    and resonance_status (gaudi_amd.aromaticity.STATUS_NAMES; 7 for a molecule that was not built) to every record."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -211,6 +214,10 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     if ppp or ppp_cis:
         from .ppp import record_fields as ppp_fields
         for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng, **({"ppp": bool(ppp), "ppp_cis": True} if ppp_cis else {}))):
+            rec.update(extra)
+    if aromaticity:
+        from .aromaticity import record_fields as resonance_fields
+        for rec, extra in zip(out, resonance_fields(out, dataset, engine=eng)):
             rec.update(extra)
     return out
 

@@ -857,6 +857,56 @@ int gaudi_host_ppp_cis(const gaudi_ppp_tables* tables, int B, int A, int M, cons
  * duration; the SCF launches of those calls are counted by gaudi_ppp_profile_get. */
 int gaudi_ppp_cis_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- All Kekule structures: their count, Pauling bond orders, sextets, Fries and Clar numbers (csrc/kekule.inc, DESIGN.md
+ * section 8o), for B molecules in one launch. ----
+ * gaudi_bond_orders returns one Kekule structure; this enumerates them all.  Atoms, bonds, the sigma degree (bonds, one more for a
+ * carbon with exactly two) and the valence table are those of gaudi_bond_orders.  Every atom takes its FIRST option, which must be
+ * neutral; `sel` is the set of atoms whose option adds a bond, G[sel] the graph of the bonds with both ends in sel; a Kekule
+ * structure is a perfect matching of G[sel] and K their number (0 when |sel| is odd; 1 when sel is empty).  The molecule must be
+ * connected.  Exact integer combinatorics: no parameter, no floating point.
+ * The search tree, which defines the budget: the root is the empty matching; at a node v is the lowest-index unmatched atom of sel;
+ * without one the node is a structure; otherwise it has one child per unmatched sel neighbour of v, in ascending order; a node
+ * without a child is a dead end.  n_nodes_out counts every node.
+ * Hexagons: the chordless 6-cycles of the heavy-atom graph whose six atoms are all in sel (pyridine-type rings included; a
+ * five-ring whose heteroatom gives a lone pair is not a sextet here), ordered by their sorted atom tuple and each reported in
+ * cycle order from its smallest atom towards the smaller of that atom's two ring neighbours.  A hexagon is a sextet of a structure
+ * in which three of its six bonds are double.  fries = the most sextets of one structure; clar = the most pairwise atom-disjoint
+ * sextets of one structure, which is the Clar number.
+ * Not here: counts beyond the budget (no factorisation over components, no determinant method), charged resonance forms,
+ * lone-pair sextets of five-rings, resonance energies in eV. */
+#define GAUDI_KEKULE_BUDGET (1 << 20)  /* nodes of the search tree per molecule */
+#define GAUDI_KEKULE_MAX_SEL 128       /* atoms in sel (the largest tier of gaudi_huckel) */
+#define GAUDI_KEKULE_MAX_EDGES 192     /* bonds of G[sel] */
+/* status_out codes; anything but OK leaves every other output of the molecule zero. */
+#define GAUDI_KEKULE_OK 0
+#define GAUDI_KEKULE_NO_KEKULE 1      /* K = 0: |sel| is odd, or G[sel] has no perfect matching                              */
+#define GAUDI_KEKULE_NOT_NEUTRAL 2    /* an atom has options but no neutral one (its only option is charged)                 */
+#define GAUDI_KEKULE_NOT_CONNECTED 3
+#define GAUDI_KEKULE_BAD_VALENCE 4    /* an atom without an option, as GAUDI_BONDS_BAD_VALENCE                                */
+#define GAUDI_KEKULE_BAD_INPUT 5      /* as GAUDI_BONDS_BAD_INPUT                                                            */
+#define GAUDI_KEKULE_OVERFLOW 6       /* beyond gaudi_bond_orders' capacities, or more than 128 atoms in sel, 192 bonds in G[sel],
+                                         GAUDI_RINGS_MAX_RINGS hexagons, or a sel atom with more than three sel neighbours     */
+#define GAUDI_KEKULE_EMPTY 7          /* n_atoms = 0                                                                         */
+#define GAUDI_KEKULE_UNDECIDED 8      /* the tree has more than GAUDI_KEKULE_BUDGET nodes.  Like GAUDI_BONDS_GAVE_UP, and unlike every
+                                         other status and every count, this can depend on the atom numbering                 */
+/* Inputs as gaudi_bond_orders takes them.  One 64-lane wave per molecule; the tree is expanded level by level until 64 nodes are
+ * open, then every lane walks subtrees depth-first; sums and maxima commute, so the outputs are bit for bit those of
+ * gaudi_host_kekule wherever the molecule stands in the batch.
+ * k_out [B]; double_count_out [B][M]: structures in which the listed bond is double, 0 for a bond outside G[sel] (the Pauling bond
+ * order is double_count / K); n_hex_out [B]; hex_atoms_out [B][GAUDI_RINGS_MAX_RINGS][6]: atom indices; sextet_count_out
+ * [B][GAUDI_RINGS_MAX_RINGS]: structures in which the hexagon is a sextet; fries_out, clar_out, n_nodes_out, status_out [B]. */
+int gaudi_kekule(gaudi_handle* h, const gaudi_valence_tables* tables, int B, int A, int M, const int32_t* elem,
+                 const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, int64_t* k_out, uint32_t* double_count_out,
+                 int32_t* n_hex_out, int32_t* hex_atoms_out, uint32_t* sextet_count_out, int32_t* fries_out, int32_t* clar_out,
+                 int64_t* n_nodes_out, int32_t* status_out);
+/* gaudi_kekule without a handle: the same source text compiled for the host and run serially.  Test surface, not a fallback. */
+int gaudi_host_kekule(const gaudi_valence_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                      const int32_t* bonds, const int32_t* n_bonds, int64_t* k_out, uint32_t* double_count_out, int32_t* n_hex_out,
+                      int32_t* hex_atoms_out, uint32_t* sextet_count_out, int32_t* fries_out, int32_t* clar_out,
+                      int64_t* n_nodes_out, int32_t* status_out);
+/* Number of gaudi_kekule launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
+int gaudi_kekule_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
