@@ -105,6 +105,8 @@ PPP_MATAGA_NISHIMOTO, PPP_OHNO = 0, 1
 PPP_CIS_MAX_WINDOW, PPP_CIS_MAX_STATES = 8, 64
 PPP_CIS_JACOBI_CAP, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE, PPP_CIS_TRIPLET_UNSTABLE = 16, 32, 64, 128
 PPP_CIS_FLAGS = PPP_CIS_JACOBI_CAP | PPP_CIS_TRUNCATED | PPP_CIS_WINDOW_EDGE | PPP_CIS_TRIPLET_UNSTABLE
+# include/gaudi_hip.h: GAUDI_RING_CURRENT_*
+RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE, RING_CURRENT_SMALL_GAP, RING_CURRENT_RINGS_UNDEFINED = 32, 6, 9, 1
 
 
 class PPPTables(C.Structure):
@@ -202,6 +204,9 @@ EXPORTS = {
     "gaudi_kekule": (C.c_int, [C.c_void_p, C.POINTER(ValenceTables)] + [C.c_int] * 3 + [IP] * 4 + [I64P, U32P, IP, IP, U32P, IP, IP, I64P, IP]),
     "gaudi_host_kekule": (C.c_int, [C.POINTER(ValenceTables)] + [C.c_int] * 3 + [IP] * 4 + [I64P, U32P, IP, IP, U32P, IP, IP, I64P, IP]),
     "gaudi_kekule_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_ring_currents": (C.c_int, [C.c_void_p, C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP] + [FP, IP, IP, IP] + [FP] * 6 + [IP] * 5),
+    "gaudi_host_ring_currents": (C.c_int, [C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP] + [FP, IP, IP, IP] + [FP] * 6 + [IP] * 5),
+    "gaudi_ring_currents_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -283,6 +288,7 @@ _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
 _PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
 _KEKULE_EXPORTS = ("gaudi_kekule", "gaudi_kekule_profile_get")  # ... and the Kekule structure counts
+_RING_CURRENT_EXPORTS = ("gaudi_ring_currents", "gaudi_ring_currents_profile_get")  # ... and the ring currents
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -311,7 +317,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEKULE_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEKULE_EXPORTS + _RING_CURRENT_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -587,6 +593,44 @@ def host_huckel(tables, elem, n_atoms, bonds, n_bonds, charge=None) -> dict:
     rc = lib.gaudi_host_huckel(*huckel_args(tables, elem, n_atoms, bonds, n_bonds, charge, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_huckel failed ({rc})")
+    return out
+
+
+RING_CURRENT_ARRAYS = ("bond_current", "n_rings", "ring_atoms", "ring_size", "ring_current", "ring_area", "normal", "rms_out_of_plane",
+                       "gap", "residual", "n_pi", "n_electrons", "sweeps", "flags", "status")
+_RING_CURRENT_INT = ("n_rings", "ring_atoms", "ring_size", "n_pi", "n_electrons", "sweeps", "flags", "status")
+
+
+def ring_current_outputs(B: int, M: int) -> dict:
+    """The fifteen output arrays of gaudi_ring_currents / gaudi_host_ring_currents, in argument order."""
+    R, S = RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE
+    shape = dict(bond_current=(B, M), ring_atoms=(B, R, S), ring_size=(B, R), ring_current=(B, R), ring_area=(B, R), normal=(B, 3))
+    return {k: np.zeros(shape.get(k, (B,)), np.int32 if k in _RING_CURRENT_INT else np.float32) for k in RING_CURRENT_ARRAYS}
+
+
+def ring_current_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, out):
+    """The arguments both entry points share: the Hueckel table, the molecules as bond_orders takes them, xyz [B,A,3] float32,
+    charge [B] int32 or None, the outputs."""
+    for a in (elem, n_atoms, bonds, n_bonds) + (() if charge is None else (charge,)):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.shape == (B, A, 3)
+    assert charge is None or charge.shape == (B,)
+    assert out["bond_current"].shape == (B, M) and out["ring_atoms"].shape == (B, RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE)
+    ptr = lambda k: out[k].ctypes.data_as(IP if k in _RING_CURRENT_INT else FP)
+    return ((C.byref(tables), B, A, M, elem.ctypes.data_as(IP), n_atoms.ctypes.data_as(IP), bonds.ctypes.data_as(IP),
+             n_bonds.ctypes.data_as(IP), xyz.ctypes.data_as(FP), None if charge is None else charge.ctypes.data_as(IP))
+            + tuple(ptr(k) for k in RING_CURRENT_ARRAYS))
+
+
+def host_ring_currents(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None) -> dict:
+    """gaudi_host_ring_currents (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = ring_current_outputs(elem.shape[0], bonds.shape[1])
+    rc = lib.gaudi_host_ring_currents(*ring_current_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_ring_currents failed ({rc})")
     return out
 
 

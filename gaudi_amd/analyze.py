@@ -168,7 +168,8 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
-                                pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False):
+                                pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False,
+                                ring_currents=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -225,7 +226,13 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     molecule.  The dict gains ``mol_kekule_count`` and ``mol_clar``, int64 arrays over the BUILT molecules in list order (0 where
     the status is not OK), and ``mean_log_kekule_per_center`` = the mean of ln(K) / (number of atoms that are not hydrogen) over
     the built molecules with status OK (0.0 when there are none).  With ``aromaticity=False`` nothing changes and no launch is
-    made."""
+    made.
+
+    ring_currents: one more call (gaudi_amd.aromaticity.ring_currents) gives every built molecule its
+    Hueckel-London ring currents on its built geometry.  The dict gains ``mol_ring_current_max``, a float64 array over the BUILT
+    molecules in list order with the largest ring current in units of benzene's (NaN where nothing was solved), and
+    ``paratropic_fraction`` = solved molecules with a ring current below 0 / solved molecules (0.0 when none was solved).  With
+    ``ring_currents=False`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -241,6 +248,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["ppp_cis"] = True
     if aromaticity:
         extra["aromaticity"] = True
+    if ring_currents:
+        extra["ring_currents"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -308,6 +317,11 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         d["mol_clar"] = np.array([r["clar"] for r in rows], np.int64)
         logs = [np.log(float(r["kekule_count"])) / float((np.asarray(r["atom_types"]) != h).sum()) for r in rows if r["resonance_status"] == 0]
         d["mean_log_kekule_per_center"] = float(np.mean(logs)) if logs else 0.0
+    if ring_currents:
+        rows = [r for r, ok in zip(recs, built) if ok]
+        d["mol_ring_current_max"] = np.array([r["ring_current_max"] for r in rows], np.float64)
+        solved = [r["ring_current_min"] for r in rows if r["ring_current_status"] == 0 and not np.isnan(r["ring_current_min"])]
+        d["paratropic_fraction"] = sum(v < 0.0 for v in solved) / float(len(solved)) if solved else 0.0
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

@@ -4,12 +4,18 @@ DESIGN.md section 8o): the classical descriptors of a polycyclic aromatic system
 The graph, the sigma degree and the valence table are those of ``gor2goa.bond_orders``.  Every atom takes its first, neutral
 option; ``sel`` is the set of atoms that add a bond; a Kekule structure is a perfect matching of the bonds between sel atoms.
 Exact integer combinatorics with no parameter.  Not here: counts beyond the budget of 2^20 search nodes (no factorisation over
-components, no determinant method), charged resonance forms, lone-pair sextets of five-rings, resonance energies in eV."""
+components, no determinant method), charged resonance forms, lone-pair sextets of five-rings, resonance energies in eV.
+
+``ring_currents`` is the magnetic criterion next to that structural one (csrc/ring_current.inc): the
+Hueckel-London pi current a perpendicular field induces in every bond and every ring of 4 to 6 pi centres, in units of benzene's --
+positive (diatropic) in aromatic rings, negative (paratropic) in antiaromatic ones, four-rings and five-rings with a lone-pair
+heteroatom included.  The pi centres and the table are ``gaudi_amd.huckel``'s, the geometry is the record's ``atoms3d``.  Not
+here: coupled (PPP) currents, open shells, current-density maps, NICS, non-planar corrections."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KEKULE_EMPTY, KEKULE_OK
+from ._lib import KEKULE_EMPTY, KEKULE_OK, RING_CURRENT_RINGS_UNDEFINED
 from .analyze import _engine
 
 STATUS_NAMES = {0: "counted", 1: "no Kekule structure: an odd number of atoms that add a bond, or no perfect matching among them",
@@ -123,5 +129,92 @@ def record_fields(molecules, dataset="cata", engine=None) -> list:
     return out
 
 
-__all__ = ["STATUS_NAMES", "KEKULE_EMPTY", "KEKULE_OK", "resonance", "kekule_count", "clar_number", "record_fields", "summary_fields", "records",
+RING_CURRENT_STATUS_NAMES = {0: "solved", 1: "not converged: 30 Jacobi sweeps left an off-diagonal element above 2^-24",
+                             2: "a bond index outside the atom list, a repeated bond, an element outside the table, or a charge the pi "
+                                "system cannot carry",
+                             3: "more than 128 pi centres, 384 atoms, 192 heavy atoms or 384 bonds, or an atom with more than 8 bonds",
+                             4: "no atoms (not built)", 5: "no atom is a pi centre", 6: "the parameter table cannot be used",
+                             7: "open shell: an odd number of pi electrons",
+                             8: "bad geometry: a non-finite coordinate on a pi centre, or two pi centres closer than 0.5 Angstrom",
+                             9: "small gap: HOMO and LUMO closer than 1e-3 |beta| (or no occupied / no empty level): the paramagnetic "
+                                "term diverges"}
+
+
+def _ring_raw(molecules, dataset, charge, parameters, engine):
+    """One gaudi_ring_currents call for the list."""
+    from .huckel import _charges, c_huckel_tables
+    from .ppp import _pack
+    elem, na, bonds, nb, xyz = _pack(molecules)
+    raw = _engine(engine).ring_currents(c_huckel_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)))
+    return raw, na, nb
+
+
+def _ring_extremes(raw):
+    """(max, min) ring current per molecule, float64 [B]: NaN where nothing was solved or the rings are undefined, 0 for a solved
+    molecule without a ring."""
+    r = raw["n_rings"]
+    cur = raw["ring_current"].astype(np.float64)
+    live = np.arange(cur.shape[1])[None, :] < r[:, None]
+    solved = (raw["status"] == 0) & ((raw["flags"] & RING_CURRENT_RINGS_UNDEFINED) == 0)
+    hi = np.where(live, cur, -np.inf).max(1, initial=-np.inf)
+    lo = np.where(live, cur, np.inf).min(1, initial=np.inf)
+    return np.where(solved, np.where(r > 0, hi, 0.0), np.nan), np.where(solved, np.where(r > 0, lo, 0.0), np.nan)
+
+
+def ring_currents(molecules, dataset="cata", charge=0, parameters=None, engine=None) -> list:
+    """One launch per capacity tier (32 / 64 / 128 pi centres) for the whole list.  ``molecules``: records of rings_to_atoms (their
+    ``atoms3d`` is the geometry) or ``(atom_types [n], bonds [m,2], xyz [n,3])`` triples in Angstrom, as ``ppp.orbitals`` takes them;
+    ``charge`` and ``parameters`` as ``huckel.orbitals`` takes them (the electron count must be even).  Returns one dict per molecule:
+      status             0 = solved (RING_CURRENT_STATUS_NAMES; ``status_name`` is its text); otherwise the values below are zero / empty / NaN
+      bond_current       [m] float32: the current of listed bond (i, j) in the direction i -> j, in units of benzene's; zero on bonds
+                         not between pi centres
+      rings              [r, up to 6] atom indices (a list of int64 arrays): the chordless cycles of 4 to 6 pi centres, ordered by sorted
+                         atom tuple, each from its smallest atom counter-clockwise seen from the tip of ``normal``
+      ring_current       [r] float32: positive = diatropic (aromatic), negative = paratropic;  ring_area: [r] Angstrom^2
+      ring_current_max, ring_current_min: their extremes (0.0 without a ring, NaN where the rings are undefined)
+      rings_undefined    the flag: the chordless cycles are no basis of the cycle space (or more than 32, or one without an area);
+                         the bond currents stay valid
+      normal             [3] the unit normal of the best plane through the pi centres;  rms_out_of_plane: their rms distance from it
+      gap                x_HOMO - x_LUMO in |beta|;  residual: max |C I - b|, how well ring currents reproduce the bond currents
+      n_pi, n_electrons, sweeps, flags"""
+    molecules = list(molecules)
+    if not molecules:
+        return []
+    raw, na, nb = _ring_raw(molecules, dataset, charge, parameters, engine)
+    hi, lo = _ring_extremes(raw)
+    out = []
+    for i in range(len(na)):
+        r = int(raw["n_rings"][i])
+        rec = {k: int(raw[k][i]) for k in ("status", "n_pi", "n_electrons", "sweeps", "flags")}
+        rec.update({k: float(raw[k][i]) for k in ("rms_out_of_plane", "gap", "residual")})
+        rec.update(status_name=RING_CURRENT_STATUS_NAMES.get(rec["status"], str(rec["status"])),
+                   bond_current=raw["bond_current"][i, :nb[i]].copy(),
+                   rings=[raw["ring_atoms"][i, k, :raw["ring_size"][i, k]].astype(np.int64) for k in range(r)],
+                   ring_current=raw["ring_current"][i, :r].copy(), ring_area=raw["ring_area"][i, :r].copy(),
+                   ring_current_max=float(hi[i]), ring_current_min=float(lo[i]),
+                   rings_undefined=bool(rec["flags"] & RING_CURRENT_RINGS_UNDEFINED), normal=raw["normal"][i].copy())
+        out.append(rec)
+    return out
+
+
+def ring_current_extremes(molecules, dataset="cata", charge=0, parameters=None, engine=None) -> dict:
+    """The array form, one call -> {"ring_current_max", "ring_current_min": float64 [B] (NaN where nothing was solved or the rings
+    are undefined, 0.0 for a solved molecule without a ring), "status": int64 [B]}.  What design / design_sweep / refine(...,
+    ring_currents=True) add."""
+    molecules = list(molecules)
+    if not molecules:
+        return dict(ring_current_max=np.zeros(0), ring_current_min=np.zeros(0), status=np.zeros(0, np.int64))
+    raw = _ring_raw(molecules, dataset, charge, parameters, engine)[0]
+    hi, lo = _ring_extremes(raw)
+    return dict(ring_current_max=hi, ring_current_min=lo, status=raw["status"].astype(np.int64))
+
+
+def ring_current_fields(molecules, dataset="cata", engine=None) -> list:
+    """What rings_to_atoms(..., ring_currents=True) adds to every record."""
+    ext = ring_current_extremes(molecules, dataset, engine=engine)
+    return [dict(ring_current_max=float(hi), ring_current_min=float(lo), ring_current_status=int(st))
+            for hi, lo, st in zip(ext["ring_current_max"], ext["ring_current_min"], ext["status"])]
+
+
+__all__ = ["RING_CURRENT_STATUS_NAMES", "ring_currents", "ring_current_extremes", "ring_current_fields", "STATUS_NAMES", "KEKULE_EMPTY", "KEKULE_OK", "resonance", "kekule_count", "clar_number", "record_fields", "summary_fields", "records",
            "sel_bonds"]

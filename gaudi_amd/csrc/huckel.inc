@@ -172,19 +172,11 @@ __host__ __device__ inline bool jacobi_sweeps(S& s, int n, int lane, float thres
   return converged;
 }
 
-// One molecule.  Every branch around a fence or a reduction is lane-uniform.
-template <int P>
-__host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSmem<P>& s, int b, int lane) {
-#pragma clang fp contract(off)
-  const int A = Q.in.A, M = Q.in.M;
-  int H = 0, E = 0;
-  const int gstatus = canon_graph(Q.in, s.g, b, lane, H, E);
-  if (gstatus != GAUDI_CANON_OK) {
-    if (lane == 0) Q.status[b] = gstatus;
-    return;
-  }
-  const HuckelTab& T = *Q.tab;
-  // ---- 1. site classes; the pi centres numbered in ascending atom index (vertices are)
+// Step 1 for molecule b whose graph is in s.g (H vertices): site classes, the pi centres numbered in ascending atom index
+// (vertices are) into s.vcls, s.pidx, s.vert, s.cls.  -> n centres, n_el electrons and GAUDI_HUCKEL_OK, or the status that refuses
+// the molecule.  S is any work space with these arrays (ring_current.inc has one); every exit is lane-uniform.
+template <int P, class S>
+__host__ __device__ inline int huckel_sites(const HuckelTab& T, S& s, int H, int charge, int lane, int& n, int& n_el) {
   const int per = (H + kRwLanes - 1) / kRwLanes, lo = lane * per, hi = lo + per < H ? lo + per : H;
   int cnt = 0, el = 0;
   for (int v = lo; v < hi; ++v) {
@@ -196,10 +188,9 @@ __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSme
     cnt += c >= 0;
     el += c >= 0 ? T.n_e[c] : 0;
   }
-  int n, n_el;
   int pos = rw_scan(cnt, lane, n);
   (void)rw_scan(el, lane, n_el);
-  n_el -= Q.charge[b];
+  n_el -= charge;
   for (int v = lo; v < hi; ++v) {
     const int c = s.vcls[v];
     s.pidx[v] = (unsigned char)(c >= 0 && pos < P ? pos : kCanonNone);
@@ -211,16 +202,16 @@ __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSme
       ++pos;
     }
   }
-  int refused = GAUDI_HUCKEL_OK;
-  if (n == 0) refused = GAUDI_HUCKEL_NO_PI;
-  else if (n > P) refused = GAUDI_HUCKEL_OVERFLOW;  // (the host sends a molecule to a tier that holds its heavy atoms: P is 128 here)
-  else if (n_el < 0 || n_el > 2 * n) refused = GAUDI_HUCKEL_BAD_INPUT;  // a charge the pi system cannot carry
-  if (refused != GAUDI_HUCKEL_OK) {
-    if (lane == 0) Q.status[b] = refused;
-    return;
-  }
+  if (n == 0) return GAUDI_HUCKEL_NO_PI;
+  if (n > P) return GAUDI_HUCKEL_OVERFLOW;  // (the host sends a molecule to a tier that holds its heavy atoms: P is 128 here)
+  if (n_el < 0 || n_el > 2 * n) return GAUDI_HUCKEL_BAD_INPUT;  // a charge the pi system cannot carry
   rw_fence();
-  // ---- A = M, V = I; the sparse matrix kept for step 3
+  return GAUDI_HUCKEL_OK;
+}
+
+// A = M, V = I; the sparse matrix (s.hd, s.nb, s.kn) kept for the Rayleigh pass
+template <class S>
+__host__ __device__ inline void huckel_matrix(const HuckelTab& T, S& s, int n, int lane) {
   for (int r = 0; r < n; ++r)
     for (int c = lane; c < n; c += kRwLanes) {
       s.a[r][c] = 0.0f;
@@ -252,10 +243,13 @@ __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSme
     }
   }
   rw_fence();
-  // ---- 2. Jacobi sweeps
-  int sweeps = 0;
-  const bool converged = jacobi_sweeps<P>(s, n, lane, kHuckelOff, sweeps);
-  // ---- 3. Rayleigh quotients with the matrix the molecule started from; columns normalised
+}
+
+// Step 3: s.x[i] = the Rayleigh quotient of column i of V with the sparse matrix, rows ascending, a row's bonds in adjacency
+// order; the column normalised.
+template <class S>
+__host__ __device__ inline void huckel_rayleigh(S& s, int n, int lane) {
+#pragma clang fp contract(off)
   for (int i = lane; i < n; i += kRwLanes) {
     float num = 0.0f, den = 0.0f;
     for (int r = 0; r < n; ++r) {
@@ -273,6 +267,34 @@ __host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSme
     for (int r = 0; r < n; ++r) s.v[r][i] = s.v[r][i] / norm;
   }
   rw_fence();
+}
+
+// One molecule.  Every branch around a fence or a reduction is lane-uniform.
+template <int P>
+__host__ __device__ inline void huckel_molecule(const HuckelParams& Q, HuckelSmem<P>& s, int b, int lane) {
+#pragma clang fp contract(off)
+  const int A = Q.in.A, M = Q.in.M;
+  int H = 0, E = 0;
+  const int gstatus = canon_graph(Q.in, s.g, b, lane, H, E);
+  if (gstatus != GAUDI_CANON_OK) {
+    if (lane == 0) Q.status[b] = gstatus;
+    return;
+  }
+  const HuckelTab& T = *Q.tab;
+  // ---- 1. site classes; the pi centres numbered in ascending atom index (vertices are)
+  int n, n_el;
+  const int refused = huckel_sites<P>(T, s, H, Q.charge[b], lane, n, n_el);
+  if (refused != GAUDI_HUCKEL_OK) {
+    if (lane == 0) Q.status[b] = refused;
+    return;
+  }
+  // ---- A = M, V = I; the sparse matrix kept for step 3
+  huckel_matrix(T, s, n, lane);
+  // ---- 2. Jacobi sweeps
+  int sweeps = 0;
+  const bool converged = jacobi_sweeps<P>(s, n, lane, kHuckelOff, sweeps);
+  // ---- 3. Rayleigh quotients with the matrix the molecule started from; columns normalised
+  huckel_rayleigh(s, n, lane);
   // ---- 4. ranks, occupations, the frontier
   const int n_occ = (n_el + 1) >> 1;  // levels holding an electron
   for (int i = lane; i < n; i += kRwLanes) {

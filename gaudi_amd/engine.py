@@ -900,6 +900,23 @@ class Engine:
         self._check(rc, "gaudi_ppp")
         return out
 
+    def ring_currents_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_ring_currents since profile_reset(True): one launch per capacity tier present."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_ring_currents_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_ring_currents_profile_get")
+        return int(n.value), float(ms.value)
+
+    def ring_currents(self, tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None):
+        """gaudi_ring_currents on packed arrays: a HuckelTables (gaudi_amd.huckel.c_huckel_tables), the molecules as bond_orders
+        takes them, xyz [B,A,3] float32 in Angstrom, charge [B] int32 or None -> dict of the raw output arrays
+        (_lib.RING_CURRENT_ARRAYS: bond_current [B,M] float32, n_rings [B], ring_atoms [B,32,6], ring_size [B,32] int32, ring_current /
+        ring_area [B,32], normal [B,3], rms_out_of_plane / gap / residual [B] float32, n_pi / n_electrons / sweeps / flags / status [B]
+        int32).  gaudi_amd.aromaticity.ring_currents is the interface on top."""
+        out = _lib.ring_current_outputs(elem.shape[0], bonds.shape[1])
+        rc = self.lib.gaudi_ring_currents(self.h, *_lib.ring_current_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, out))
+        self._check(rc, "gaudi_ring_currents")
+        return out
+
     def ppp_cis_profile_get(self):
         """(launches, summed milliseconds) of the CIS kernel of gaudi_ppp_cis since profile_reset(True): one launch per call (the
         SCF launches of those calls are ppp_profile_get's)."""

@@ -907,6 +907,61 @@ int gaudi_host_kekule(const gaudi_valence_tables* tables, int B, int A, int M, c
 /* Number of gaudi_kekule launches since gaudi_profile_reset(h, 1) and their summed duration (HIP events). */
 int gaudi_kekule_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Hueckel-London ring currents: the pi current a perpendicular magnetic field induces in every bond and every ring
+ * (csrc/ring_current.inc), for B molecules. ----
+ * The graph, the pi centres, the classes, the matrix M, the electron count, `charge` and the level filling are gaudi_huckel's; the
+ * energy matrix is E = -M (units |beta|), the orbital energies eps = -x.  xyz [B][A][3] fp32 in Angstrom as gaudi_ppp takes it; only
+ * pi centres are looked at.
+ *   plane     c = the centroid of the pi centres, n = the unit eigenvector of the smallest eigenvalue of sum (r-c)(r-c)^T, its
+ *             component of largest magnitude positive (the lower index wins a tie); rms_out_of_plane = the root mean square of n.(r-c).
+ *   areas     s_rs = n.((r_r-c) x (r_s-c)) / 2.
+ *   response  A_rs = E_rs s_rs on bonds, a_lk = v_l^T A v_k, W_lk = 2 a_lk / (eps_k - eps_l) for k occupied and l empty,
+ *             Q = sum W_lk (v_l v_k^T - v_k v_l^T), P = 2 sum_occ v v^T, J_rs = 2 E_rs (s_rs P_rs + Q_sr).
+ *   units     c0 = 2 A0 / 9, A0 = (3 sqrt(3) / 2) (1.40)^2: bond_current of listed bond (i, j) = -J_ij / c0 in the direction i -> j; it is
+ *             +1 in benzene (a regular hexagon of 1.40 Angstrom, k = 1), counter-clockwise seen from the tip of n: positive is
+ *             diatropic.  Zero on bonds that are not between pi centres, and exactly zero on a bond that lies on none of the
+ *             rings when the ring currents are defined (it lies on no cycle: Kirchhoff's law).
+ *   rings     the chordless cycles of 4, 5 or 6 pi centres of the graph of pi centres, ordered by sorted atom tuple, each reported
+ *             from its smallest atom in the direction whose area projected along n (ring_area) is positive.
+ *   currents  the ring currents I solve C I = b (b the bond currents, C[e][r] = +-1 where ring r runs along or against listed bond
+ *             e) through the normal equations (C^T C) I = C^T b; residual = max |C I - b|.  They are defined when n_rings equals
+ *             bonds - centres + components of the pi graph, n_rings <= 32, every ring_area > 1e-3 and the elimination meets no pivot
+ *             <= 0; otherwise flags has GAUDI_RING_CURRENT_RINGS_UNDEFINED, n_rings and the ring rows are zero and the bond currents
+ *             stay valid.
+ * status, in this order: the GAUDI_HUCKEL_* refusals with their meaning there; GAUDI_PPP_OPEN_SHELL -- an odd electron count;
+ * NOT_CONVERGED; GAUDI_RING_CURRENT_SMALL_GAP -- x_HOMO - x_LUMO < 1e-3 (the paramagnetic term diverges), also no occupied or no
+ * empty level; a pi graph without a cycle is then OK with every current, the normal and rms_out_of_plane zero, whatever its
+ * coordinates; GAUDI_PPP_BAD_GEOMETRY -- the rule of gaudi_ppp.  Every status but OK leaves every other output of the molecule zero.
+ * Outputs: bond_current_out [B][M]; n_rings_out [B]; ring_atoms_out [B][32][6] atom indices in cycle order, -1 padded (a solved
+ * molecule's rows beyond n_rings are -1 too); ring_size_out, ring_current_out, ring_area_out [B][32]; normal_out [B][3];
+ * rms_out_of_plane_out, gap_out (x_HOMO - x_LUMO), residual_out [B] fp32; n_pi_out, n_electrons_out, sweeps_out, flags_out,
+ * status_out [B].
+ * One 64-lane wave per molecule, tiers and launches as gaudi_huckel, whose Jacobi routine and Rayleigh pass it runs.  Individually
+ * rounded fp32 in a fixed order, no atomics: the outputs are a function of the molecule's own arrays and bit for bit what
+ * gaudi_host_ring_currents returns.  B * max(A, M, 192) <= 2^31.
+ * Not here: coupled (PPP) currents, open shells, current-density maps, NICS, non-planar corrections. */
+#define GAUDI_RING_CURRENT_MAX_RINGS 32
+#define GAUDI_RING_CURRENT_MAX_SIZE 6
+#define GAUDI_RING_CURRENT_SMALL_GAP 9       /* a status, after GAUDI_PPP_BAD_GEOMETRY */
+#define GAUDI_RING_CURRENT_RINGS_UNDEFINED 1 /* a flag */
+int gaudi_ring_currents(gaudi_handle* h, const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem,
+                        const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge,
+                        float* bond_current_out, int32_t* n_rings_out, int32_t* ring_atoms_out, int32_t* ring_size_out,
+                        float* ring_current_out, float* ring_area_out, float* normal_out, float* rms_out_of_plane_out, float* gap_out,
+                        float* residual_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* sweeps_out, int32_t* flags_out,
+                        int32_t* status_out);
+/* gaudi_ring_currents without a handle: the same source text (csrc/ring_current.inc: ring_current_molecule) compiled for the host
+ * and run serially.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_ring_currents(const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                             const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge,
+                             float* bond_current_out, int32_t* n_rings_out, int32_t* ring_atoms_out, int32_t* ring_size_out,
+                             float* ring_current_out, float* ring_area_out, float* normal_out, float* rms_out_of_plane_out,
+                             float* gap_out, float* residual_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* sweeps_out,
+                             int32_t* flags_out, int32_t* status_out);
+/* Number of gaudi_ring_currents launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their
+ * summed duration (HIP events). */
+int gaudi_ring_currents_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
