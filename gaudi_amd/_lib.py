@@ -188,6 +188,13 @@ EXPORTS = {
     "gaudi_fp_common": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, U8P, IP]),
     "gaudi_host_fp_nearest": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, U8P, C.c_int, IP, IP, IP]),
     "gaudi_fp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_fp_neighbours": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, C.c_int, IP, C.c_int64, I64P, IP]),
+    "gaudi_host_fp_neighbours": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, C.c_int, IP, C.c_int64, I64P, IP]),
+    "gaudi_fp_cluster": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, C.c_int] + [IP] * 5),
+    "gaudi_host_fp_cluster": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, C.c_int] + [IP] * 5),
+    "gaudi_fp_pick_diverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, U8P, C.c_int, U8P] + [C.c_int] * 4 + [IP] * 7),
+    "gaudi_host_fp_pick_diverse": (C.c_int, [C.c_int, C.c_int, U8P, C.c_int, U8P] + [C.c_int] * 4 + [IP] * 7),
+    "gaudi_fp_select_stages_get": (C.c_int, [C.c_void_p, DP]),
     "gaudi_substructure_search": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [IP] * 4 + [C.c_int] * 3 + [IP] * 5 + [IP, IP, U8P, IP, IP]),
     "gaudi_host_substructure_search": (C.c_int, [C.c_int] * 6 + [IP] * 4 + [C.c_int] * 3 + [IP] * 5 + [IP, IP, U8P, IP, IP]),
     "gaudi_host_substructure_root_steps": (C.c_int, [C.c_int]),
@@ -283,7 +290,8 @@ _RINGS_EXPORTS = ("gaudi_atoms_to_rings", "gaudi_rings_profile_get")  # ... and 
 _BONDS_EXPORTS = ("gaudi_bond_orders", "gaudi_bonds_profile_get")  # ... and bond orders / formal charges
 _CANON_EXPORTS = ("gaudi_canonical_order", "gaudi_canon_profile_get")  # ... and the canonical numbering
 _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_nearest", "gaudi_fp_common",
-               "gaudi_fp_profile_get")  # ... and the circular fingerprints with their similarity
+               "gaudi_fp_profile_get", "gaudi_fp_neighbours", "gaudi_fp_cluster",
+               "gaudi_fp_pick_diverse", "gaudi_fp_select_stages_get")  # ... and the circular fingerprints with their similarity, clusters and diverse picks
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
 _PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
@@ -516,6 +524,100 @@ def host_fp_nearest(q, lib_rows, k=1) -> dict:
     if rc != 0:
         raise GaudiError(f"gaudi_host_fp_nearest failed ({rc})")
     return out
+
+
+FP_MAX_THRESHOLD_DEN = 65536  # include/gaudi_hip.h: gaudi_fp_neighbours
+E_CAPACITY = -5               # include/gaudi_hip.h: GAUDI_E_CAPACITY
+
+
+def fp_threshold(threshold) -> tuple:
+    """A similarity threshold as the exact rational (num, den) the entry points compare with: a float becomes
+    Fraction(threshold).limit_denominator(65536), a Fraction or a (num, den) pair is taken as given."""
+    from fractions import Fraction
+    if isinstance(threshold, (tuple, list)):
+        num, den = (int(v) for v in threshold)
+    else:
+        f = threshold if isinstance(threshold, Fraction) else Fraction(float(threshold)).limit_denominator(FP_MAX_THRESHOLD_DEN)
+        num, den = f.numerator, f.denominator
+    if not (1 <= den <= FP_MAX_THRESHOLD_DEN and 0 <= num <= den):
+        raise GaudiError(f"a threshold is num / den with 0 <= num <= den <= {FP_MAX_THRESHOLD_DEN}, got {num} / {den}")
+    return num, den
+
+
+def _fp_fail(fn, rc, check):
+    if check is not None:
+        check(rc, fn.__name__)
+    raise GaudiError(f"{fn.__name__} failed ({rc})")
+
+
+def fp_neighbours_call(fn, head, rows, num, den, check=None) -> dict:
+    """gaudi_fp_neighbours / gaudi_host_fp_neighbours (head = the handle, or nothing) by the capacity protocol: counts and offsets
+    first, then the lists into a buffer of exactly offsets[N] entries -> dict(count int32 [N], offsets int64 [N+1], list int32)."""
+    rows = fp_rows(rows)
+    N = rows.shape[0]
+    count, offsets = np.zeros(N, np.int32), np.zeros(N + 1, np.int64)
+    args = (*head, rows.shape[1], N, rows.ctypes.data_as(U8P), int(num), int(den), count.ctypes.data_as(IP))
+    rc = fn(*args, 0, offsets.ctypes.data_as(I64P), None)
+    if rc != 0:
+        _fp_fail(fn, rc, check)
+    lst = np.zeros(int(offsets[N]), np.int32)
+    if len(lst):
+        rc = fn(*args, len(lst), offsets.ctypes.data_as(I64P), lst.ctypes.data_as(IP))
+        if rc != 0:
+            _fp_fail(fn, rc, check)
+    return dict(count=count, offsets=offsets, list=lst)
+
+
+def fp_cluster_call(fn, head, rows, num, den, check=None) -> dict:
+    """gaudi_fp_cluster / gaudi_host_fp_cluster -> dict(cluster, centroid, size, count: int32 [N]; n_clusters int)."""
+    rows = fp_rows(rows)
+    N = rows.shape[0]
+    out = dict(cluster=np.full(N, -1, np.int32), centroid=np.full(N, -1, np.int32), size=np.zeros(N, np.int32),
+               count=np.zeros(N, np.int32))
+    n = np.zeros(1, np.int32)
+    rc = fn(*head, rows.shape[1], N, rows.ctypes.data_as(U8P), int(num), int(den),
+            *(out[k].ctypes.data_as(IP) for k in ("cluster", "centroid", "size", "count")), n.ctypes.data_as(IP))
+    if rc != 0:
+        _fp_fail(fn, rc, check)
+    out["n_clusters"] = int(n[0])
+    return out
+
+
+def fp_pick_call(fn, head, rows, S, seeds, first, k, num, den, check=None) -> dict:
+    """gaudi_fp_pick_diverse / gaudi_host_fp_pick_diverse.  seeds: rows [S,n_bins] or None (S > 0 then names the resident
+    library); first: -1 or a row; den = 0: no threshold -> dict(picked, pick_common, pick_union: int32 [k]; n_picked int; owner,
+    owner_common, owner_union: int32 [N])."""
+    rows = fp_rows(rows)
+    N, k = rows.shape[0], int(k)
+    seeds = None if seeds is None else fp_rows(seeds)
+    if seeds is not None and (seeds.shape[0] != S or (S and seeds.shape[1] != rows.shape[1])):
+        raise GaudiError(f"seeds must be [{S}, {rows.shape[1]}], got {seeds.shape}")
+    out = dict(picked=np.full(max(k, 0), -1, np.int32), pick_common=np.zeros(max(k, 0), np.int32), pick_union=np.zeros(max(k, 0), np.int32),
+               owner=np.full(N, -1, np.int32), owner_common=np.zeros(N, np.int32), owner_union=np.zeros(N, np.int32))
+    n = np.zeros(1, np.int32)
+    ip = lambda a: a.ctypes.data_as(IP)  # noqa: E731
+    rc = fn(*head, rows.shape[1], N, rows.ctypes.data_as(U8P), int(S), None if seeds is None or S == 0 else seeds.ctypes.data_as(U8P),
+            int(first), k, int(num), int(den), ip(out["picked"]), ip(out["pick_common"]), ip(out["pick_union"]), ip(n),
+            ip(out["owner"]), ip(out["owner_common"]), ip(out["owner_union"]))
+    if rc != 0:
+        _fp_fail(fn, rc, check)
+    out["n_picked"] = int(n[0])
+    return out
+
+
+def host_fp_neighbours(rows, num, den) -> dict:
+    """gaudi_host_fp_neighbours (needs no device): plain loops over every pair.  Test surface only."""
+    return fp_neighbours_call(load_library().gaudi_host_fp_neighbours, (), rows, num, den)
+
+
+def host_fp_cluster(rows, num, den) -> dict:
+    """gaudi_host_fp_cluster (needs no device): the literal sort and walk on the host's neighbour lists.  Test surface only."""
+    return fp_cluster_call(load_library().gaudi_host_fp_cluster, (), rows, num, den)
+
+
+def host_fp_pick_diverse(rows, k, num=0, den=0, seeds=None, first=-1) -> dict:
+    """gaudi_host_fp_pick_diverse (needs no device): the literal MaxMin loop.  Test surface only."""
+    return fp_pick_call(load_library().gaudi_host_fp_pick_diverse, (), rows, 0 if seeds is None else len(seeds), seeds, first, k, num, den)
 
 
 def sub_outputs(B: int, P: int, A: int, QA: int) -> dict:

@@ -169,7 +169,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
                                 pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False,
-                                ring_currents=False):
+                                ring_currents=False, cluster_threshold=None):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -199,7 +199,11 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     two).  With ``train_library`` (a gaudi_amd.similarity.Library of fingerprints of radius 2, resident on the engine used here)
     also ``nearest_train_similarity`` and ``nearest_train_index``, one per molecule: how close the nearest training molecule is
     and which it is, 0.0 and -1 where the molecule was not built.  Membership (``train_keys``) says novel or not; this says how
-    novel.
+    novel.  With ``cluster_threshold`` (a float, a Fraction or a (num, den) pair, as gaudi_amd.similarity.cluster takes it;
+    DESIGN.md section 8q) the built molecules are clustered by Butina's method at that similarity and the dict gains
+    ``n_clusters`` and ``largest_cluster_fraction`` = the size of the largest cluster / built molecules (0.0 when none was
+    built): one mean cannot tell a batch spread evenly from three skeletons plus noise, a cluster count can.  With
+    ``cluster_threshold=None`` nothing changes and no launch is made.
 
     patterns: a list of patterns for gaudi_amd.substructure.search (one more launch per 64 patterns, and
     one for their symmetry), with ``pattern_options`` = its keywords ``hydrogens`` / ``closed``.  The dict gains ``pattern_hits``
@@ -236,6 +240,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
+    if cluster_threshold is not None and not similarity:
+        raise ValueError("cluster_threshold needs similarity=True")
     # (the keyword only when asked for: a rings_to_atoms stand-in with the earlier signature, as tests/test_gor2goa_cpu.py passes, keeps working)
     extra = {"bond_orders": True} if valence_check else {}
     if exact:
@@ -285,7 +291,7 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         if train is not None:
             d["mol_novel_valid"] = sum(k not in train for k in valid_keys) / float(n_valid) if n_valid else 0.0
     if similarity:
-        d.update(_similarity(recs, built, dataset, _engine(engine), train_library))
+        d.update(_similarity(recs, built, dataset, _engine(engine), train_library, cluster_threshold))
     if patterns is not None:
         from .substructure import search
         hits = search(recs, patterns, dataset, engine=_engine(engine), **(pattern_options or {}))["hit"]
@@ -325,9 +331,10 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 
-def _similarity(recs, built, dataset, engine, train_library=None) -> dict:
-    """``diversity`` of the built records and, with a library, their nearest training molecules (analyze_atoms_for_molecules)."""
-    from .similarity import fingerprints, internal_diversity
+def _similarity(recs, built, dataset, engine, train_library=None, cluster_threshold=None, diverse=None) -> dict:
+    """``diversity`` of the built records and, with a library, their nearest training molecules (analyze_atoms_for_molecules);
+    with a threshold their Butina clusters, with ``diverse`` = k up to k MaxMin picks among them."""
+    from .similarity import cluster, fingerprints, internal_diversity, pick_diverse
     n_bins = 1024 if train_library is None else train_library.n_bins
     fp = fingerprints(recs, dataset, n_bins=n_bins, engine=engine)
     out = {"diversity": internal_diversity(fp["fp"], fp["total"], engine=engine)}
@@ -338,4 +345,13 @@ def _similarity(recs, built, dataset, engine, train_library=None) -> dict:
         ok = np.array(built, dtype=bool)
         out["nearest_train_similarity"] = np.where(ok, sim[:, 0], 0.0)
         out["nearest_train_index"] = np.where(ok, idx[:, 0], -1)
+    if cluster_threshold is not None or diverse is not None:
+        rows = np.where(np.asarray(built, bool)[:, None], fp["fp"], 0).astype(np.uint8)  # (not built: a zero row, never clustered or picked)
+        if cluster_threshold is not None:
+            cl = cluster(rows, cluster_threshold, engine=engine)
+            n_live = int((cl["cluster"] >= 0).sum())
+            out["n_clusters"] = cl["n_clusters"]
+            out["largest_cluster_fraction"] = float(cl["sizes"].max()) / n_live if cl["n_clusters"] else 0.0
+        if diverse is not None:
+            out["diverse_indices"] = pick_diverse(rows, int(diverse), engine=engine)["picked"]
     return out

@@ -383,16 +383,19 @@ enum FpBuf : int {
 };
 static_assert(kFpBufs == 16, "gaudi_handle::d_fp");
 
-// rows [n][n_bins] from the host into slot `rows`, their totals into slot `tot` (on the handle's stream)
-static int fp_upload(gaudi_handle* h, int rows, int tot, const uint8_t* src, int n, int n_bins) {
+// rows [n][n_bins] from the host into the buffer `rows`, their totals into `tot` (on the handle's stream)
+static int fp_upload(gaudi_handle* h, DevBuf& rows, DevBuf& tot, const uint8_t* src, int n, int n_bins) {
   const size_t bytes = (size_t)n * n_bins;
-  HIPCHECK(h, h->d_fp[rows].reserve(bytes));
-  HIPCHECK(h, h->d_fp[tot].reserve(sizeof(int) * (size_t)n));
-  HIPCHECK(h, hipMemcpyAsync(h->d_fp[rows].p, src, bytes, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(fp_totals_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_fp[rows].as<unsigned char>(), n, n_bins,
-                     h->d_fp[tot].as<int>());
+  HIPCHECK(h, rows.reserve(bytes));
+  HIPCHECK(h, tot.reserve(sizeof(int) * (size_t)n));
+  HIPCHECK(h, hipMemcpyAsync(rows.p, src, bytes, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(fp_totals_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, rows.as<unsigned char>(), n, n_bins, tot.as<int>());
   HIPCHECK(h, hipGetLastError());
   return GAUDI_OK;
+}
+// ... into the d_fp slots `rows` and `tot` (fp_select.inc passes slots of its own)
+static int fp_upload(gaudi_handle* h, int rows, int tot, const uint8_t* src, int n, int n_bins) {
+  return fp_upload(h, h->d_fp[rows], h->d_fp[tot], src, n, n_bins);
 }
 
 // the library a call compares against: the one passed in (uploaded to the temporary slots) or the resident one

@@ -136,6 +136,8 @@ struct gaudi_handle {
   DevBuf d_canon[11];  // gaudi_canonical_order (canon.inc): its four inputs and its seven outputs
   DevBuf d_fp[16];     // fingerprints and their similarity (fp.inc: FpBuf names the slots)
   int fp_lib_rows = 0, fp_lib_bins = 0;  // the resident fingerprint library (gaudi_fp_library_set); 0 rows: none
+  DevBuf d_fps[16];    // neighbour lists, clusters and diverse picks of fingerprint batches (fp_select.inc: FsBuf names the slots)
+  double fs_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ... and the stage times of their most recent profiled call (FsStage)
   DevBuf d_sub[10];    // gaudi_substructure_search (sub.inc): its four inputs, the pattern plans and its five outputs
   DevBuf d_huckel[22];  // gaudi_huckel (huckel.inc): its five inputs, the tier lists, the table and its fifteen outputs
   DevBuf d_ppp[38];     // gaudi_ppp (ppp.inc): its six inputs, the tier lists, the table, its eighteen outputs and the density scratch;
@@ -1640,6 +1642,7 @@ void gaudi_destroy(gaudi_handle* h) {
   for (DevBuf& b : h->d_bonds) b.release();
   for (DevBuf& b : h->d_canon) b.release();
   for (DevBuf& b : h->d_fp) b.release();
+  for (DevBuf& b : h->d_fps) b.release();
   for (DevBuf& b : h->d_sub) b.release();
   for (DevBuf& b : h->d_huckel) b.release();
   for (DevBuf& b : h->d_ppp) b.release();
@@ -2179,6 +2182,7 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 #include "bonds.inc"
 #include "canon.inc"
 #include "fp.inc"
+#include "fp_select.inc"
 #include "sub.inc"
 #include "huckel.inc"
 #include "ppp.inc"

@@ -967,6 +967,31 @@ class Engine:
         self._check(rc, "gaudi_fp_common")
         return out
 
+    def fp_neighbours(self, rows, num, den):
+        """gaudi_fp_neighbours: for every row of rows [N,n_bins] the live rows at least num / den similar to it, itself included ->
+        dict(count int32 [N], offsets int64 [N+1], list int32 [offsets[N]]: ascending, CSR)."""
+        return _lib.fp_neighbours_call(self.lib.gaudi_fp_neighbours, (self.h,), rows, num, den, self._check)
+
+    def fp_cluster(self, rows, num, den):
+        """gaudi_fp_cluster: Butina clusters at num / den -> dict(cluster, centroid, size, count: int32 [N]; n_clusters)."""
+        return _lib.fp_cluster_call(self.lib.gaudi_fp_cluster, (self.h,), rows, num, den, self._check)
+
+    def fp_pick_diverse(self, rows, k, num=0, den=0, seeds=None, first=-1, S=None):
+        """gaudi_fp_pick_diverse: up to k MaxMin picks from rows [N,n_bins].  seeds [S,n_bins], or None with S > 0 for the resident
+        library of S rows; den = 0: no threshold -> dict(picked, pick_common, pick_union: int32 [k]; n_picked; owner, owner_common,
+        owner_union: int32 [N])."""
+        S = (0 if seeds is None else len(seeds)) if S is None else int(S)
+        return _lib.fp_pick_call(self.lib.gaudi_fp_pick_diverse, (self.h,), rows, S, seeds, first, k, num, den, self._check)
+
+    FP_SELECT_STAGES = ("count", "offsets", "fill", "sort", "walk", "pick_setup", "pick_rounds", "totals")
+
+    def fp_select_stages_get(self) -> dict:
+        """gaudi_fp_select_stages_get: the kernel milliseconds, by stage, of the most recent fp_neighbours / fp_cluster /
+        fp_pick_diverse call made after profile_reset(True); a stage the call did not run is 0.0."""
+        ms = np.zeros(len(self.FP_SELECT_STAGES), np.float64)
+        self._check(self.lib.gaudi_fp_select_stages_get(self.h, ms.ctypes.data_as(_lib.DP)), "gaudi_fp_select_stages_get")
+        return dict(zip(self.FP_SELECT_STAGES, ms.tolist()))
+
     def set_fix_noise(self, enable: bool, key_sample: int = 0):
         """fix_noise=True of the reference (en_diffusion.py:562-566): every molecule of a call receives the raw draws of
         ONE sample (Philox stream of global sample ``key_sample``, or injected noise of shape [T+2,1,N,3+F])."""

@@ -54,7 +54,7 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
            valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None, huckel=False,
-           ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+           ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, cluster_threshold=None, diverse=None):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -84,7 +84,13 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     counted).  With ``aromaticity=False`` nothing is launched.  ring_currents (with with_atoms): one more call
     (gaudi_amd.aromaticity.ring_current_extremes) and the dict gains ``ring_current_max`` and
     ``ring_current_min`` float64 [B]: the extreme Hueckel-London ring currents of every molecule in units of benzene's, on its built
-    geometry (NaN where the molecule was not built or not solved).  With ``ring_currents=False`` nothing is launched."""
+    geometry (NaN where the molecule was not built or not solved).  With ``ring_currents=False`` nothing is launched.
+    cluster_threshold (with with_atoms and similarity): Butina clusters of the built molecules at that similarity
+    (gaudi_amd.similarity.cluster), and the dict gains ``n_clusters`` and ``largest_cluster_fraction`` =
+    the largest cluster / built molecules -- whether the batch collapsed onto a few skeletons, which the one mean ``diversity``
+    does not show.  diverse (with with_atoms and similarity): the dict gains ``diverse_indices``, up to ``diverse`` MaxMin picks
+    (gaudi_amd.similarity.pick_diverse) among the built molecules, as indices into the batch in pick order: the ones to take on.
+    With ``cluster_threshold=None`` / ``diverse=None`` nothing is launched."""
     model.eval()
     cond_predictor.eval()
     nodesxsample = np.array([n_nodes] * args.batch_size, dtype=np.int64)
@@ -94,12 +100,14 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     seconds = time() - start_time
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
-                     with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents)
+                     with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
+                     cluster_threshold=cluster_threshold, diverse=diverse)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
                  n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None, patterns=None,
-                 pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+                 pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
+                 cluster_threshold=None, diverse=None):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -113,7 +121,8 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     ppp: as design takes it; every setting gets its own ``ppp_gap``, ``ppp_ip`` and ``ppp_ea``.  ppp_cis: as design takes it; every
     setting gets its own ``ppp_s1``, ``ppp_t1`` and ``ppp_bright``.  aromaticity: as design takes it; every setting gets its own
     ``kekule_count`` and ``clar``.  ring_currents: as design takes it; every setting gets its own ``ring_current_max`` and
-    ``ring_current_min``."""
+    ``ring_current_min``.  cluster_threshold / diverse: as design takes them; every setting gets its own ``n_clusters``,
+    ``largest_cluster_fraction`` and ``diverse_indices`` (indices into the setting's own molecules)."""
     from .models_edm import ValueTarget
     model.eval()
     cond_predictor.eval()
@@ -164,7 +173,8 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
         lo, hi = j * bs, (j + 1) * bs
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
                       em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library, patterns,
-                      pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents)
+                      pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold=cluster_threshold,
+                      diverse=diverse)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
@@ -172,14 +182,14 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
            prop_dist=None, with_atoms=False, valence_check=False, similarity=False, patterns=None, pattern_options=None,
-           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, diverse=None):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought.  similarity (with with_atoms): the seeds go
     through rings_to_atoms as well, and the dict gains ``diversity`` and ``similarity_to_seed`` [B], the similarity of every
     refined molecule with its own seed (0.0 where either was not built): how far the refinement moved.  patterns /
     pattern_options: as design takes them, on the refined molecules.  huckel, ppp, ppp_cis, aromaticity, ring_currents: as design takes them, on
-    the refined molecules."""
+    the refined molecules.  diverse: as design takes it, on the refined molecules."""
     model.eval()
     cond_predictor.eval()
     bs, n_nodes = _to_numpy(x).shape[0], _to_numpy(x).shape[1]
@@ -192,7 +202,8 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     seconds = time() - start_time
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
-                    seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents)
+                    seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
+                    diverse=diverse)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     if similarity:
         from .similarity import fingerprints, rowwise_similarity
@@ -204,7 +215,8 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
 
 
 def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None,
-           patterns=None, pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+           patterns=None, pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
+           cluster_threshold=None, diverse=None):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -229,7 +241,7 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
         out["mol_valid"] = float(out["valid"].mean())
     if similarity:
         from .analyze import _similarity
-        out.update(_similarity(recs, [r["status"] == 0 for r in recs], dataset, engine, train_library))
+        out.update(_similarity(recs, [r["status"] == 0 for r in recs], dataset, engine, train_library, cluster_threshold, diverse))
     if patterns is not None:
         from .substructure import search
         out["contains"] = search(recs, patterns, dataset, engine=engine, **(pattern_options or {}))["hit"]
@@ -254,7 +266,8 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
               with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None, patterns=None,
-              pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+              pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
+              cluster_threshold=None, diverse=None):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     if patterns is not None and not with_atoms:
         raise ValueError("patterns need with_atoms=True")
@@ -272,6 +285,8 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
         raise ValueError("similarity / train_library need with_atoms=True")
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
+    if (cluster_threshold is not None or diverse is not None) and not (with_atoms and similarity):
+        raise ValueError("cluster_threshold / diverse need with_atoms=True and similarity=True")
     _check(x, node_mask)
     stability_dict, _, _, _, _ = eval_stability(x, one_hot, node_mask, edge_mask, dataset=args.dataset,
                                                 engine=model.engine)
@@ -290,7 +305,7 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
                pred=_like_ref(pred), best=order, seconds=seconds, molecules_per_second=x.shape[0] / seconds)
     if with_atoms:
         out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library,
-                          patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents))
+                          patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold, diverse))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import FP_BINS, GaudiError
+from ._lib import FP_BINS, GaudiError, fp_threshold
 from .analyze import _engine
 
 
@@ -94,6 +94,62 @@ def internal_diversity(fp, total, engine=None) -> float:
         return 0.0
     sim = similarity_matrix(fp, engine=engine)
     return float(1.0 - (sim.sum() - np.trace(sim)) / (n * (n - 1)))
+
+
+def _threshold(threshold):
+    from fractions import Fraction
+    num, den = fp_threshold(threshold)
+    return num, den, Fraction(num, den)
+
+
+def neighbours(fp, threshold, engine=None) -> dict:
+    """For every row the live rows (total > 0) at least ``threshold`` similar to it, itself included, ascending, as CSR:
+    dict(count int64 [N], offsets int64 [N+1], list int64 [offsets[N]], threshold).  A row that is not live has no neighbours and is
+    nobody's.  ``threshold``: a float (it becomes Fraction(threshold).limit_denominator(65536)), a Fraction or a (num, den) pair;
+    the returned ``threshold`` is the exact Fraction compared with (csrc/fp_select.inc: no float is compared anywhere)."""
+    num, den, thr = _threshold(threshold)
+    raw = _engine(engine).fp_neighbours(fp, num, den)
+    return dict(count=raw["count"].astype(np.int64), offsets=raw["offsets"].astype(np.int64), list=raw["list"].astype(np.int64),
+                threshold=thr)
+
+
+def cluster(fp, threshold, engine=None) -> dict:
+    """Butina clusters at ``threshold`` (as for ``neighbours``): the rows by neighbour count descending, then index; a live row
+    not yet assigned becomes the next centroid and claims the unassigned rows of its neighbour list ->
+    dict(cluster int64 [N] (-1: not live), centroids int64 [n_clusters], sizes int64 [n_clusters], count int64 [N], n_clusters,
+    threshold)."""
+    num, den, thr = _threshold(threshold)
+    raw = _engine(engine).fp_cluster(fp, num, den)
+    n = raw["n_clusters"]
+    return dict(cluster=raw["cluster"].astype(np.int64), centroids=raw["centroid"][:n].astype(np.int64),
+                sizes=raw["size"][:n].astype(np.int64), count=raw["count"].astype(np.int64), n_clusters=n, threshold=thr)
+
+
+def pick_diverse(fp, k, threshold=None, seeds=None, first=None, engine=None) -> dict:
+    """Up to k MaxMin picks: each the live row least similar to everything chosen before it (ties to the smaller index).
+    ``seeds``: rows chosen earlier -- an array [S,n_bins], or a ``Library`` for the engine's resident one; without seeds the
+    first pick is row ``first`` (None: the first live row).  With a ``threshold`` picking also stops once every live row is at
+    least that similar to something chosen: the picks then cover the batch at that radius ->
+    dict(picked int64 [n_picked] in pick order, pick_similarity float64 [n_picked]: to the nearest chosen element when picked,
+    owner int64 [N]: the pick (a row index) or seed s (-2 - s) nearest to each row, -1 for a row that is not live,
+    owner_similarity float64 [N], n_picked, threshold: the exact Fraction or None)."""
+    num, den, thr = (0, 0, None) if threshold is None else _threshold(threshold)
+    eng = _engine(engine)
+    if isinstance(seeds, Library):
+        if first is not None:
+            raise ValueError("first is read only without seeds")
+        if seeds.engine is not eng:
+            raise GaudiError("a Library as seeds is the resident library of ITS engine: pass that engine")
+        seeds._live()
+        raw = eng.fp_pick_diverse(fp, k, num, den, None, -1, S=seeds.M)
+    else:
+        if seeds is not None and first is not None:
+            raise ValueError("first is read only without seeds")
+        raw = eng.fp_pick_diverse(fp, k, num, den, seeds, -1 if first is None else int(first))
+    n = raw["n_picked"]
+    return dict(picked=raw["picked"][:n].astype(np.int64), pick_similarity=_quotient(raw["pick_common"][:n], raw["pick_union"][:n]),
+                owner=raw["owner"].astype(np.int64), owner_similarity=_quotient(raw["owner_common"], raw["owner_union"]),
+                n_picked=n, threshold=thr)
 
 
 def rowwise_similarity(a, b) -> np.ndarray:

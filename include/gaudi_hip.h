@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get, gaudi_fp_neighbours, gaudi_fp_cluster, gaudi_fp_pick_diverse, gaudi_host_fp_neighbours, gaudi_host_fp_cluster, gaudi_host_fp_pick_diverse, gaudi_fp_select_stages_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -610,6 +610,54 @@ int gaudi_fp_common(gaudi_handle* h, int n_bins, int B, const uint8_t* q, int M,
  * events; uploads and downloads are outside). */
 int gaudi_fp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Diverse subsets and Butina clusters of fingerprint batches (csrc/fp_select.inc). ----
+ * Which of a batch to take on: what RDKit users get from MaxMinPicker and Butina clustering.  rows [N][n_bins] of uint8, n_bins
+ * 256, 512 or 1024; total_i = the sum of row i's bytes and a row is LIVE when total_i > 0.  Rows that are not live (the refused or
+ * unbuilt molecules) are never picked, never clustered, have no neighbours and are nobody's neighbour.  common and union are the
+ * ones above and every comparison of two similarities is the cross product above, in 64-bit integers.  A threshold is the
+ * rational thr_num / thr_den with 0 <= thr_num <= thr_den <= 65536: the pair i, j is AT LEAST THR when union_ij > 0 and
+ * common_ij * thr_den >= thr_num * union_ij.  No float is compared anywhere, and every output is exactly what the gaudi_host_
+ * twin of the entry point returns.  N <= 2^20 and at most 2^28 neighbour entries (GAUDI_E_CAPACITY with a message beyond); N = 0
+ * is GAUDI_OK with nothing written.  The launches are counted (one by one) and timed in gaudi_fp_profile_get's log.
+ *
+ * gaudi_fp_neighbours: count_out [N] = for a live row i the number of live j at least thr to it, i itself included, and 0 for a
+ * row that is not live; offsets_out [N + 1] = the exclusive prefix of the counts; list_out = those j, ascending, row after row
+ * (CSR).  list_out may be NULL with capacity 0: counts and offsets only.  A capacity below offsets_out[N] returns
+ * GAUDI_E_CAPACITY after count_out and offsets_out are written, so the caller sizes the buffer and calls again.  The batch is
+ * compared with itself in splits of whole tiles as gaudi_fp_nearest does it (GAUDI_FP_SPLITS forces their number); no output
+ * depends on the number of splits. */
+int gaudi_fp_neighbours(gaudi_handle* h, int n_bins, int N, const uint8_t* rows, int thr_num, int thr_den, int32_t* count_out,
+                        int64_t capacity, int64_t* offsets_out, int32_t* list_out);
+/* Butina clustering on those lists, which stay on the device.  The rows are ordered by count descending, then index ascending; along
+ * that order a live row not yet assigned becomes the centroid of the next cluster (0, 1, ...) and claims every not yet assigned
+ * row of its list, itself included.  cluster_out [N]: the cluster of row i, -1 for a row that is not live.  centroid_out [N],
+ * size_out [N]: by cluster number, -1 and 0 from *n_clusters_out on.  count_out [N] as above. */
+int gaudi_fp_cluster(gaudi_handle* h, int n_bins, int N, const uint8_t* rows, int thr_num, int thr_den, int32_t* cluster_out,
+                     int32_t* centroid_out, int32_t* size_out, int32_t* count_out, int32_t* n_clusters_out);
+/* MaxMin picking of up to k rows.  seeds [S][n_bins]: rows chosen before (NULL with S > 0: the resident library of
+ * gaudi_fp_library_set, which must have S rows of n_bins; a seed row of zeros has similarity 0 to every row).  Every live row i
+ * carries near(i) = (common, union, owner): the most similar chosen element so far, among equally similar ones the earliest
+ * chosen -- seeds in index order, then picks in pick order.  Pick t: with S = 0 and t = 0 the row `first` (-1: the live row with
+ * the smallest index; out of range or not live: GAUDI_E_INVALID; `first` is read only when S = 0); otherwise the live unpicked
+ * row whose near is LEAST similar, equal similarity to the smaller row index.  pick_common_out[t], pick_union_out[t] = that
+ * row's near when it is picked (0, 0 for a first pick without seeds).  Picking stops after k picks, when no live unpicked row is
+ * left, or -- thr_den > 0 -- when the candidate's near is at least thr already: it is not picked, and the picks cover the batch
+ * at that radius.  thr_den = 0: no threshold.  After a pick every live row strictly more similar to it than to its near takes it
+ * as owner, and the picked row owns itself with common = union = total.  picked_out, pick_common_out, pick_union_out: each [k],
+ * -1, 0, 0 from *n_picked_out on.  owner_out [N]: the row index of the owning pick, -2 - s for seed s, -1 for a row that is not
+ * live or when nothing was chosen; owner_common_out, owner_union_out [N]: its near (0, 0 with owner -1).  One launch per pick, with
+ * no host synchronisation inside a chunk of 256 picks; GAUDI_FP_SPLITS forces the number of workgroups a round cuts the rows
+ * into, and no output depends on it. */
+int gaudi_fp_pick_diverse(gaudi_handle* h, int n_bins, int N, const uint8_t* rows, int S, const uint8_t* seeds, int first, int k,
+                          int thr_num, int thr_den, int32_t* picked_out, int32_t* pick_common_out, int32_t* pick_union_out,
+                          int32_t* n_picked_out, int32_t* owner_out, int32_t* owner_common_out, int32_t* owner_union_out);
+/* The kernel times of the most recent of the three calls above that ran with profiling on (gaudi_profile_reset(h, 1)), by stage,
+ * in milliseconds (HIP events): ms_out [8] = the COUNT pass, the offsets, the FILL pass, the sort, the walk, the set-up of a pick
+ * call (the seed search, the cleared state, the round that makes no pick), all its rounds together, and fp_totals_kernel over
+ * the same rows (a pick call with profiling on launches it once more as the yardstick of a round: it reads every byte once).
+ * Stages the call did not run are 0.  With profiling on these calls synchronise the stream where a stage ends. */
+int gaudi_fp_select_stages_get(gaudi_handle* h, double* ms_out);
+
 /* ---- Substructure search over graphs of atoms (csrc/sub.inc). ----
  * Does a molecule contain a motif, where, and how often: what a SMARTS match without bond primitives answers.
  * Graphs, on both sides, are the one of gaudi_canonical_order: vertices = the non-hydrogen atoms; a vertex carries its element and
@@ -1009,6 +1057,16 @@ int gaudi_host_substructure_root_steps(int reset);
  * surface for the CPU suite, not a CPU fallback. */
 int gaudi_host_fp_nearest(int n_bins, int B, const uint8_t* q, int M, const uint8_t* lib, int k, int32_t* idx_out,
                           int32_t* common_out, int32_t* union_out);
+/* gaudi_fp_neighbours, gaudi_fp_cluster and gaudi_fp_pick_diverse without a handle (and so without a resident library: seeds must
+ * be given when S > 0): plain loops over every pair with the same comparison functions (csrc/fp_select.inc).  Test surface, not a
+ * CPU fallback. */
+int gaudi_host_fp_neighbours(int n_bins, int N, const uint8_t* rows, int thr_num, int thr_den, int32_t* count_out, int64_t capacity,
+                             int64_t* offsets_out, int32_t* list_out);
+int gaudi_host_fp_cluster(int n_bins, int N, const uint8_t* rows, int thr_num, int thr_den, int32_t* cluster_out,
+                          int32_t* centroid_out, int32_t* size_out, int32_t* count_out, int32_t* n_clusters_out);
+int gaudi_host_fp_pick_diverse(int n_bins, int N, const uint8_t* rows, int S, const uint8_t* seeds, int first, int k, int thr_num,
+                               int thr_den, int32_t* picked_out, int32_t* pick_common_out, int32_t* pick_union_out,
+                               int32_t* n_picked_out, int32_t* owner_out, int32_t* owner_common_out, int32_t* owner_union_out);
 /* The layout gaudi_predictor_loss_grad reads the predictor in (pred_train_host.inc: pt_layout): off_out[4 + 13 L] = float
  * offset of each role inside the names-order flat buffer (-1: absent; head: embedding w/b, embedding_out w/b; per layer:
  * edge_mlp.0 w/b, edge_mlp.2 w/b, att_mlp.0 w/b, coord_mlp.0 w/b, coord_mlp.2 w, node_mlp.0 w/b, node_mlp.2 w/b),
