@@ -315,6 +315,27 @@ struct NodeCtxH {
   float* scales_b = nullptr;  // the second source's, when they do not follow the first's (a kept copy of h: node_ctx_keep)
 };
 
+// no hook behind the last weight load (node_gemm_h: hook)
+struct NoHookH {
+  static constexpr bool kOn = false;
+  __device__ __forceinline__ void operator()() const {}
+};
+template <class F>
+struct HookH {
+  static constexpr bool kOn = true;
+  F f;
+  __device__ __forceinline__ void operator()() const { f(); }
+};
+template <class F>
+__device__ __forceinline__ HookH<F> hook_h(F f) { return HookH<F>{f}; }
+// the chunk of a call's LAST source behind whose matrix instructions the call's last weight load goes out (node_gemm_h: source);
+// -1: that source loads nothing (every chunk travelled ahead or was loaded at the top, nothing is loaded ahead)
+__host__ __device__ constexpr int nh_last_load(int nc, int D, int kOut) {
+  int r = -1;
+  for (int i = 0; i < nc; ++i)
+    if (i + D < nc || i % D < kOut) r = i;
+  return r;
+}
 // what y starts from
 struct YInitBias {};
 struct YInitRows {
@@ -330,15 +351,21 @@ struct YInitRows {
 // NU: the tile slots this body loads, multiplies and stores (tile-slot classes above), 0 = the geometry's.
 // sXa: the first source's rows, a pointer or a row source too.  yinit (YInitRows): y starts from the rows of an LDS array [N][HP + 4]
 // instead of the bias -- a first source's whole contribution computed elsewhere (side_job_h below), bias and tail step included.
+// hook (round 14): runs ONCE, directly behind the call's LAST weight load (nh_last_load) -- global loads of the caller's that it
+// uses behind the call (activation-stash rows: w8_pred.h, pred_backward).  Behind them lie the remaining chunks' matrix
+// instructions, the tail step, the fold and the epilogue, and nothing of that waits on the vector-memory counter for anything
+// newer: no weight load waits for a hooked load, and the call's rest covers part of its round trip.  The caller closes such a call
+// with lds_barrier(), which leaves the loads in flight.
 template <int HP, int EPI, bool TWO, int MAXNT, int PIN = kAheadOne, int POUT = kAheadOne, int FL = kNodePlain, int TAIL = kTailRuntime,
-          int NU = 0, class XB = const float*, class XA = const float*, class YI = YInitBias>
+          int NU = 0, class XB = const float*, class XA = const float*, class YI = YInitBias, class HOOK = NoHookH>
 __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sXa, bool do_split_a, int Wb, const XB& sXb,
                                             const float* sBias, float* sY, const float* sRes, const float* sMask, int N, int wave,
                                             int lane, const NodeCtxH& cx, NodePFH<HP>& pf, int nextW = -1, float* gPre = nullptr,
                                             uint32_t* sMaxOut = nullptr /* LDS [N], zeroed: max |y| bits of every node's row */,
-                                            NodeStampH* ns = nullptr, const YI& yinit = YI{}) {
+                                            NodeStampH* ns = nullptr, const YI& yinit = YI{}, const HOOK& hook = HOOK{}) {
   (void)ns;
   (void)yinit;
+  (void)hook;
   using G = NodeGeoH<HP>;
   constexpr int T = G::T, LD = HP + 4, NTW = NU > 0 ? NU : G::NTW, nc = G::nc, D = G::D;
   constexpr int kIn = PIN < D ? PIN : D, kOut = POUT < D ? POUT : D;
@@ -460,6 +487,10 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
     constexpr bool last_src = !TWO || src == 1;
     const int Wcur = src == 0 ? Wa : Wb;
     BH bcur = bld(s_, 0, 0);
+    if constexpr (HOOK::kOn && last_src && nh_last_load(nc, D, kOut) < 0) {
+      hook();
+      __builtin_amdgcn_sched_barrier(0);
+    }
     static_for<nc>([&](auto i_tag) {
       constexpr int i = decltype(i_tag)::value;
       constexpr int d = i % D;
@@ -482,6 +513,10 @@ __device__ __forceinline__ void node_gemm_h(const WBuf& wh, int Wa, const XA& sX
         else if constexpr (d < kOut) nh_load<HP, NTW>(pf.s[d], wh, 2 * Wn + d * nh_chunk_floats(HP), tl_next);
       }
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (HOOK::kOn && last_src && i == nh_last_load(nc, D, kOut)) {
+        hook();
+        __builtin_amdgcn_sched_barrier(0);
+      }
       bcur = bnext;
     });
   };
@@ -701,20 +736,22 @@ __device__ __forceinline__ void node_prefetch_x(PF& pf, const WBuf& wb, const WB
 // kernel that the host picks for more than 16 node slots) and off in the one C2 / C3 run on.
 // FL = kNodeOneTile: the instantiation the host picks for at most 16 node slots (one column tile, one tail k-step: see above).
 // XBS: the second source is Xb + Xb1 (1), (Xb + Xb1) / xb_div (2) -- fp16-pair GEMMs whose rows are not staged only (RowsSum).
-template <int HP, int EPI, bool TWO, int GN, bool NH, int PIN, int POUT, int FL = kNodePlain, int XBS = 0, class PF>
+// hook: node_gemm_h's (the fp16-pair form of an unsummed second source only).
+template <int HP, int EPI, bool TWO, int GN, bool NH, int PIN, int POUT, int FL = kNodePlain, int XBS = 0, class PF, class HOOK = NoHookH>
 __device__ __forceinline__ void node_gemm_x(const WBuf& wb, const WBuf& wbe, int Wa, const float* Xa, const float* XaS, bool split_a, int Wb,
                                             const float* Xb, const float* XbS, const float* sBias, float* sY, const float* sRes,
                                             const float* sMask, int N, int wave, int lane, bool tw, const NodeCtxH& cx, PF& pf,
                                             int nextW = -1, float* gPre = nullptr, uint32_t* sMaxOut = nullptr,
-                                            const float* Xb1 = nullptr, float xb_div = 1.f) {
+                                            const float* Xb1 = nullptr, float xb_div = 1.f, const HOOK& hook = HOOK{}) {
   static_assert(XBS == 0 || (NH && GN == 0 && TWO), "summed second sources: the fp16-pair form of the resident kernels");
+  static_assert(!HOOK::kOn || (NH && XBS == 0), "a hook rides behind the fp16-pair form's last weight load");
   if constexpr (NH) {
     constexpr int MAXNT = GN ? 3 : node_one_tile(FL) ? 1 : 2;
     constexpr int TAIL = node_one_tile(FL) && nh_odd(HP) ? kTailOne : kTailRuntime;
     constexpr int NU = node_slots<HP>(FL);
     if constexpr (XBS == 0)
-      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL, NU>(wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW,
-                                                                gPre, sMaxOut);
+      node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL, NU, const float*, const float*, YInitBias, HOOK>(
+          wbe, Wa, Xa, split_a, Wb, Xb, sBias, sY, sRes, sMask, N, wave, lane, cx, pf, nextW, gPre, sMaxOut, nullptr, YInitBias{}, hook);
     else
       node_gemm_h<HP, EPI, TWO, MAXNT, PIN, POUT, FL, TAIL, NU>(wbe, Wa, Xa, split_a, Wb, RowsSum<XBS == 2>{Xb, Xb1, xb_div}, sBias, sY, sRes, sMask,
                                                                 N, wave, lane, cx, pf, nextW, gPre, sMaxOut);

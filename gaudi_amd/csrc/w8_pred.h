@@ -6,6 +6,22 @@
 #pragma once
 #include "pred_device.h"
 #include "w8_edm.h"
+#ifndef GAUDI_STASH_RIDE
+#define GAUDI_STASH_RIDE 3  // pred_backward, the sites whose first stash reads ride under the GEMM ahead of them -- bit 0: v under the
+                            // de GEMM (A); bit 1: silu'(cpre), phi and the last layer's v under (d) (B); 0: none (A/B builds)
+#endif
+// Tiles (float4 per lane) of a site's 13 that ride; the others are read where they are used.  pred_bwd8_call stands at 248 VGPRs
+// and 16 B / lane of scratch: with 7 or more riding at either site the phase takes more registers and the kernel around it spills
+// more (112 -> 126 ... 132 VGPRs), with all 13 the phase itself spills inside the layer loop (profiles/r14_resource_usage.txt).
+#ifndef GAUDI_RIDE_TILES
+#define GAUDI_RIDE_TILES 6  // site A
+#endif
+#ifndef GAUDI_HOOK_TILES
+#define GAUDI_HOOK_TILES 6  // site B
+#endif
+#ifndef GAUDI_STASH_RIDE_PLAIN
+#define GAUDI_STASH_RIDE_PLAIN 0  // 1: the plain resident split kernel rides too (the stamped diagnostic build runs that one)
+#endif
 
 namespace gaudi {
 namespace w8 {
@@ -376,6 +392,16 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
   const float* pstash = astash + (size_t)W.L * S;
   const float* dpred = sm.pred + 16;
   const int nslots = mg.ntiles * 16;
+  // The edge pass's stash reads ride under the GEMM ahead of their use in the resident single-round N1 kernels (round 14; DESIGN
+  // section 8): v in the last full chunk's trip of the de GEMM, with the barrier of the trip after it -- the K tail's, which these
+  // kernels' matrices always carry -- letting it fly (w8_split.h: RideAt); silu'(cpre) and phi behind the last weight load of
+  // (d) (w8_nodes_f16.h: hook).  Every other kernel reads where it uses.
+  constexpr bool kRide = SP == 1 && !MR && GN == 0 && SplitGeo<HP, SP == 1 ? 1 : 2>::kTailOK &&
+                         (node_one_tile(FL) || (GAUDI_STASH_RIDE_PLAIN && FL != kNodeFresh));
+  constexpr bool kRideA = kRide && (GAUDI_STASH_RIDE & 1), kRideB = kRide && (GAUDI_STASH_RIDE & 2);
+  constexpr int kHookTiles = GAUDI_HOOK_TILES < T ? GAUDI_HOOK_TILES : T;
+  constexpr int kRideTiles = GAUDI_RIDE_TILES < T ? GAUDI_RIDE_TILES : T;
+  constexpr int kRideTrip = SplitGeo<HP, SP == 1 ? 1 : 2>::kTripsTail - 2;
   f4* dus = (f4*)const_cast<float*>(pstash + (size_t)W.L * S);  // [S / 16 tiles][T][64] float4: du of every tile (more than one round only)
 
   if (sZin != nullptr) {
@@ -488,14 +514,41 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
                                                  mg.NC, wave, lane, tw, hctx(), pf, Lw.Wn1ht);
     __syncthreads();
     // (d) dh += Wn1h^T dnpre ; dagg = Wn1a^T dnpre -> B0 (h is dead)
+    f4 er[kHookTiles];  // (kRideB: the edge-stash rows and phi that ride under (d))
+    float rphi = 0.f;
+    // rows `which` (0: v, the pre-activation of m; 1: silu'(cpre)) of edge tile `tile` of this layer's stash, the lane's float4
+    auto edge_rows = [=](int tile, int which) {  // (by value: a reference to the loop counter changes the code of every kernel)
+#ifdef GAUDI_DIAG_HOT_STASH  // (timing experiment only: wrong results)
+      return (const f4*)(W.w + (size_t)((which ? 0 : 8) + tile) * (T * 256)) + lane;
+#else
+      return (const f4*)(estash + edge_stash_off8(l, tile, which, S, HP)) + lane;
+#endif
+    };
     {
       const NodeCtxH cx = hctx();
       node_gemm_x<HP, EPI_ACCUM, false, GN, NH, kAheadOne, kAheadAll, FL>(wb, wbe, Lw.Wn1ht, B4, xs1, true, -1, nullptr, nullptr, nullptr, dh, dh, nullptr, mg.NC,
                                                      wave, lane, tw, cx, pf, Lw.Wn1at);
-      node_gemm_x<HP, EPI_NONE, false, GN, NH, kAheadAll, 0, FL>(wb, wbe, Lw.Wn1at, B4, xs1, false, -1, nullptr, nullptr, nullptr, B0, nullptr, nullptr,
-                                                    mg.NC, wave, lane, tw, cx, pf);
+      if constexpr (kRideB) {
+        // the edge pass's first stash reads -- silu'(cpre) of the wave's tile and phi; in the last layer, which has no coordinate
+        // branch, v instead -- go out behind this call's last weight load (w8_nodes_f16.h: hook) and fly under what is left of
+        // it.  No branch around them (a load behind a branch makes every later wait of the K loop a conservative one): a wave
+        // without a tile reads tile 0's rows, as load_tile clamps it, and drops them.
+        node_gemm_x<HP, EPI_NONE, false, GN, NH, kAheadAll, 0, FL>(
+            wb, wbe, Lw.Wn1at, B4, xs1, false, -1, nullptr, nullptr, nullptr, B0, nullptr, nullptr, mg.NC, wave, lane, tw, cx, pf, -1,
+            nullptr, nullptr, nullptr, 1.f, hook_h([&] {
+              const int rtile = wave < mg.ntiles ? wave : 0;
+              const f4* sr = edge_rows(rtile, last ? 0 : 1);
+              rphi = gload(pstash + (size_t)l * S + rtile * 16 + c);  // (first: the counter retires in order, and phi is used first)
+#pragma unroll
+              for (int t = 0; t < kHookTiles; ++t) er[t] = stash_load(sr + t * 64);
+            }));
+      } else {
+        node_gemm_x<HP, EPI_NONE, false, GN, NH, kAheadAll, 0, FL>(wb, wbe, Lw.Wn1at, B4, xs1, false, -1, nullptr, nullptr, nullptr, B0, nullptr, nullptr,
+                                                      mg.NC, wave, lane, tw, cx, pf);
+      }
     }
-    __syncthreads();
+    if constexpr (kRideB) lds_barrier();  // (the hooked loads stay in flight)
+    else __syncthreads();
     STAMP(ST_BWD_NODE);
     if constexpr (RI) er_start<HP>(ring, wbe, last ? Lw.W2t : Lw.Wc1t, wave, lane);
     // (e) edge pass: MLP chain backward for the wave's tile, then du of all slots is published CH feature tiles at a time
@@ -517,7 +570,7 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
       f4 du[T];
       float a = 0.f, tau = 0.f, dtx = 0.f, dty = 0.f, dtz = 0.f;
       {
-        f4 de[T];
+        f4 de[T], ve[T];
         if (tc.active) {
           a = gload(astash + (size_t)l * S + tc.slot);
           dtx = sm.dx[4 * tc.i + 0];  // dtrans = dx'_i
@@ -527,14 +580,11 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
         if (!last) {
           f4 cp[T];
           if (tc.active) {
-#ifdef GAUDI_DIAG_HOT_STASH
-            const f4* sc = (const f4*)(W.w + (size_t)tile * (T * 256)) + lane;
-#else
-            const f4* sc = (const f4*)(estash + edge_stash_off8(l, tile, 1, S, HP)) + lane;
-#endif
+            const f4* sc = edge_rows(tile, 1);
 #pragma unroll
-            for (int t = 0; t < T; ++t) cp[t] = stash_load(sc + t * 64);  // silu'(cpre)
-            const float phi = gload(pstash + (size_t)l * S + tc.slot);
+            for (int t = 0; t < T; ++t) cp[t] = (kRideB && t < kHookTiles) ? er[t] : stash_load(sc + t * 64);  // silu'(cpre)
+            if constexpr (kRideB) __builtin_amdgcn_sched_barrier(0);  // (the rows that did not ride go out before anything waits for phi)
+            const float phi = kRideB ? rphi : gload(pstash + (size_t)l * S + tc.slot);
             const float th = tanhf(phi);
             tau = W.use_tanh ? th * W.coords_range_layer : phi;
             const float dtau = (dtx * gg[1] + dty * gg[2] + dtz * gg[3]) * tc.mk;
@@ -547,8 +597,19 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
             for (int t = 0; t < T; ++t) cp[t] = splat(0.f);
           }
           STAMP(ST_B_DCP);
-          er_gemm_regs<HP>(de, cp, ring, wbe, Lw.Wc1t, Lw.W2t, nullptr, B0 + tc.i * LD /* + dagg_i (agg_i = sum_j e_ij) */,
+          if constexpr (kRideA) {
+            // the first stash reads of v ride under this GEMM's last trips (w8_split.h: RideAt) instead of standing, at HBM latency,
+            // between it and their first use
+            er_gemm_regs<HP>(de, cp, ring, wbe, Lw.Wc1t, Lw.W2t, nullptr, B0 + tc.i * LD, tc.active, wave, lane,
+                             ride_at<kRideTiles, kRideTrip>([&] {
+                               const f4* sv = edge_rows(tile, 0);
+#pragma unroll
+                               for (int t = 0; t < kRideTiles; ++t) ve[t] = stash_load(sv + t * 64);
+                             }));
+          } else {
+            er_gemm_regs<HP>(de, cp, ring, wbe, Lw.Wc1t, Lw.W2t, nullptr, B0 + tc.i * LD /* + dagg_i (agg_i = sum_j e_ij) */,
                              tc.active, wave, lane);
+          }
           STAMP(ST_B_DE);
         } else {
 #pragma unroll
@@ -556,14 +617,20 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
         }
         if (tc.active) {
           // e = m * a * mask ; a = sigmoid(wa . m + ba)
-          f4 ve[T];
-#ifdef GAUDI_DIAG_HOT_STASH
-          const f4* sv = (const f4*)(W.w + (size_t)(8 + tile) * (T * 256)) + lane;
-#else
-          const f4* sv = (const f4*)(estash + edge_stash_off8(l, tile, 0, S, HP)) + lane;
-#endif
+          if constexpr (kRideA || kRideB) {  // (the last layer has no edge GEMM ahead of this point: its v rides under (d))
+            const f4* sv = edge_rows(tile, 0);
+            if (last) {
 #pragma unroll
-          for (int t = 0; t < T; ++t) ve[t] = stash_load(sv + t * 64);
+              for (int t = 0; t < T; ++t) ve[t] = (kRideB && t < kHookTiles) ? er[t] : stash_load(sv + t * 64);
+            } else {
+#pragma unroll
+              for (int t = kRideA ? kRideTiles : 0; t < T; ++t) ve[t] = stash_load(sv + t * 64);
+            }
+          } else {
+            const f4* sv = edge_rows(tile, 0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) ve[t] = stash_load(sv + t * 64);
+          }
           float dadot = 0.f;
 #pragma unroll
           for (int t = 0; t < T; ++t) dadot += dot4(de[t], silu4v(ve[t]));

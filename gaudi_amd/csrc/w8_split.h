@@ -419,12 +419,31 @@ __device__ __forceinline__ void edge_gemm_pq_s(f4 (&acc)[HP / 16], RingS<HP, MOD
   for (int t = 0; t < T; ++t) acc[t] = acc[t] * dsc + *(const f4*)(sB2 + 16 * t + 4 * g);
 }
 
+// A ride (round 14): K global loads of the CALLER's that a wave WITH a tile issues in the middle of trip R of a chained edge GEMM,
+// directly behind that trip's ring request (rings_stage) -- activation-stash rows the caller uses right after the GEMM.  vmcnt
+// retires in order: the barrier that opens trip R + 1 waits for the ring request alone, by leaving exactly the K loads behind it
+// in flight (side_barrier), and the matrix work of trips R and R + 1 covers their round trip; the barrier of trip R + 2 -- or
+// the caller's first use -- waits for everything, as every trip barrier does.  A wave WITHOUT a tile issues nothing and keeps
+// trip_barrier: with a count it would leave its own ring units in flight.  No weight load ever waits behind a ride.
+struct NoRide {
+  static constexpr int K = 0, R = -1;
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int K_, int R_, class F>
+struct RideAt {
+  static constexpr int K = K_, R = R_;
+  F f;  // issues exactly K vector-memory loads, no branch around any of them
+  __device__ __forceinline__ void operator()() const { f(); }
+};
+template <int K, int R, class F>
+__device__ __forceinline__ RideAt<K, R, F> ride_at(F f) { return RideAt<K, R, F>{f}; }
+
 // Chained edge GEMM, input in registers (accumulator layout of the previous GEMM): out = bias + rowinit + W . in.  The column scale
 // is the exact maximum of the lane's own inputs (all lane groups of the column).
-template <int HP, int MODE>
+template <int HP, int MODE, class RIDE = NoRide>
 __device__ __forceinline__ void edge_gemm_regs_s(f4 (&out)[HP / 16], const f4 (&in)[HP / 16], RingS<HP, MODE>& ring, const WBuf& wb,
                                                  int W, int nextW, const float* sBias, const float* rowinit, bool active,
-                                                 int wave, int lane) {
+                                                 int wave, int lane, const RIDE& ride = RIDE{}) {
   using G = SplitGeo<HP, MODE>;
   constexpr int T = G::T;
   const int g = lane >> 4;
@@ -441,15 +460,39 @@ __device__ __forceinline__ void edge_gemm_regs_s(f4 (&out)[HP / 16], const f4 (&
 #if GAUDI_EDGE_PRIO & 2
   if (wave >= kWaves / 2) __builtin_amdgcn_s_setprio(1);
 #endif
+  static_assert(RIDE::K == 0 || (RIDE::R >= 0 && RIDE::R + 1 <= (G::NC - 1) * G::NH), "a ride sits in a full chunk's trip, with a trip after it");
+  // the barrier that opens trip tr: behind a ride it leaves the wave's K loads in flight (a wave without a tile issued none)
+  auto open = [&](auto tr_tag) {
+    constexpr int tr = decltype(tr_tag)::value;
+    if constexpr (RIDE::K > 0 && tr == RIDE::R + 1) {
+      if (active) side_barrier<RIDE::K>();
+      else trip_barrier();
+    } else {
+      trip_open(ring, lane);
+    }
+  };
   auto chunk = [&](auto m_tag) {
     constexpr int m = decltype(m_tag)::value;
     const B3 bin = split8(in[2 * m], 2 * m + 1 < T ? in[2 * m + 1 < T ? 2 * m + 1 : 0] : splat(0.f), se);
     auto trip = [&](auto h_tag) {
       constexpr int h = decltype(h_tag)::value;
       constexpr int tr = m * G::NH + h;
-      trip_open(ring, lane);
-      rings_mfma<HP, MODE, G::tiles_of(h)>(out + h * G::CH, ring.slot(ring.par) + lane * 4, bin, active,
-                                           [&] { rings_stage(ring, wb, W, nextW, tr, wave, lane); });
+      open(std::integral_constant<int, tr>{});
+      if constexpr (RIDE::K > 0 && tr == RIDE::R) {  // (the ride goes out behind the ring's request and stays there)
+        if (active)
+          rings_mfma_act<HP, MODE, G::tiles_of(h), true>(out + h * G::CH, ring.slot(ring.par) + lane * 4, bin, [&] {
+            rings_stage(ring, wb, W, nextW, tr, wave, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            ride();
+            __builtin_amdgcn_sched_barrier(0);
+          });
+        else
+          rings_mfma_act<HP, MODE, G::tiles_of(h), false>(out + h * G::CH, ring.slot(ring.par) + lane * 4, bin,
+                                                          [&] { rings_stage(ring, wb, W, nextW, tr, wave, lane); });
+      } else {
+        rings_mfma<HP, MODE, G::tiles_of(h)>(out + h * G::CH, ring.slot(ring.par) + lane * 4, bin, active,
+                                             [&] { rings_stage(ring, wb, W, nextW, tr, wave, lane); });
+      }
       trip_close(ring, lane);
     };
     trip(std::integral_constant<int, 0>{});
@@ -471,7 +514,7 @@ __device__ __forceinline__ void edge_gemm_regs_s(f4 (&out)[HP / 16], const f4 (&
   static_for<G::NC - 1>([&](auto m_tag) { chunk(m_tag); });
   if constexpr (G::kTailOK) {
     if (ring.ktail) {
-      trip_open(ring, lane);
+      open(std::integral_constant<int, G::kTripsTail - 1>{});
       rings_mfma_tail<HP, MODE>(out, ring.slot(ring.par) + lane * 4, tail_to_b(in[T - 1], c, g)[0] * se, active,
                           [&] { rings_stage(ring, wb, W, nextW, G::kTripsTail - 1, wave, lane); });
       trip_close(ring, lane);
@@ -548,10 +591,11 @@ __device__ __forceinline__ void er_gemm_regs(f4 (&out)[HP / 16], const f4 (&in)[
                                              int nextW, const float* sBias, const float* rowinit, bool active, int wave, int lane) {
   edge_gemm_regs<HP>(out, in, ring, wb, W, nextW, sBias, rowinit, active, wave, lane);
 }
-template <int HP, int MODE>
+template <int HP, int MODE, class RIDE = NoRide>
 __device__ __forceinline__ void er_gemm_regs(f4 (&out)[HP / 16], const f4 (&in)[HP / 16], RingS<HP, MODE>& ring, const WBuf& wb, int W,
-                                             int nextW, const float* sBias, const float* rowinit, bool active, int wave, int lane) {
-  edge_gemm_regs_s(out, in, ring, wb, split_off(W), split_off(nextW), sBias, rowinit, active, wave, lane);
+                                             int nextW, const float* sBias, const float* rowinit, bool active, int wave, int lane,
+                                             const RIDE& ride = RIDE{}) {
+  edge_gemm_regs_s<HP, MODE, RIDE>(out, in, ring, wb, split_off(W), split_off(nextW), sBias, rowinit, active, wave, lane, ride);
 }
 
 }  // namespace w8
