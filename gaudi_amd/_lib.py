@@ -107,6 +107,7 @@ PPP_CIS_JACOBI_CAP, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE, PPP_CIS_TRIPLET_UNST
 PPP_CIS_FLAGS = PPP_CIS_JACOBI_CAP | PPP_CIS_TRUNCATED | PPP_CIS_WINDOW_EDGE | PPP_CIS_TRIPLET_UNSTABLE
 # include/gaudi_hip.h: GAUDI_RING_CURRENT_*
 RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE, RING_CURRENT_SMALL_GAP, RING_CURRENT_RINGS_UNDEFINED = 32, 6, 9, 1
+REACTIVITY_KINDS, REACTIVITY_MAX_SLICES, REACTIVITY_SWEEP_CAP, REACTIVITY_RINGS_TRUNCATED = 3, 16, 1, 2
 
 
 class PPPTables(C.Structure):
@@ -214,6 +215,9 @@ EXPORTS = {
     "gaudi_ring_currents": (C.c_int, [C.c_void_p, C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP] + [FP, IP, IP, IP] + [FP] * 6 + [IP] * 5),
     "gaudi_host_ring_currents": (C.c_int, [C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP] + [FP, IP, IP, IP] + [FP] * 6 + [IP] * 5),
     "gaudi_ring_currents_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_reactivity": (C.c_int, [C.c_void_p, C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [C.c_int] * 2 + [FP, FP, IP, IP, FP, FP, FP] + [IP] * 6),
+    "gaudi_host_reactivity": (C.c_int, [C.POINTER(HuckelTables)] + [C.c_int] * 3 + [IP] * 5 + [C.c_int] * 2 + [FP, FP, IP, IP, FP, FP, FP] + [IP] * 6),
+    "gaudi_reactivity_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_philox_normal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, FP]),
     "gaudi_host_schedule": (C.c_int, [C.c_int, C.c_float, C.c_float, FP, FP]),
     "gaudi_host_eigh3": (C.c_int, [C.c_int, DP, DP]),
@@ -297,6 +301,7 @@ _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hu
 _PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
 _KEKULE_EXPORTS = ("gaudi_kekule", "gaudi_kekule_profile_get")  # ... and the Kekule structure counts
 _RING_CURRENT_EXPORTS = ("gaudi_ring_currents", "gaudi_ring_currents_profile_get")  # ... and the ring currents
+_REACTIVITY_EXPORTS = ("gaudi_reactivity", "gaudi_reactivity_profile_get")  # ... and the localization energies
 _KEY_EXPORTS = ("gaudi_last_kernel_key", "gaudi_kernel_key_log", "gaudi_host_kernel_keys")  # ... and the names of the kernels launched / registered
 
 _lib = None
@@ -325,7 +330,7 @@ def load_library() -> C.CDLL:
         raise GaudiError(f"{LIB_PATH} exports ABI version {abi}, this package expects {ABI_VERSION}: rebuild it "
                          "(`python -m gaudi_amd.build --force`)")
     for name, (res, args) in EXPORTS.items():
-        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEKULE_EXPORTS + _RING_CURRENT_EXPORTS + _KEY_EXPORTS):
+        if lenient and not hasattr(lib, name) and (name.startswith("gaudi_host_") or name in _ROUND6_EXPORTS + _NLL_EXPORTS + _GRID_EXPORTS + _TARGET_EXPORTS + _ATOMS_EXPORTS + _RINGS_EXPORTS + _BONDS_EXPORTS + _CANON_EXPORTS + _FP_EXPORTS + _SUB_EXPORTS + _HUCKEL_EXPORTS + _PPP_EXPORTS + _KEKULE_EXPORTS + _RING_CURRENT_EXPORTS + _REACTIVITY_EXPORTS + _KEY_EXPORTS):
             continue
         if lenient and abi != ABI_VERSION and name.startswith("gaudi_host_"):
             continue  # left unbound on purpose: a call raises instead of corrupting memory
@@ -733,6 +738,44 @@ def host_ring_currents(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None) 
     rc = lib.gaudi_host_ring_currents(*ring_current_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_ring_currents failed ({rc})")
+    return out
+
+
+REACTIVITY_ARRAYS = ("atom_localization", "free_valence", "rings", "n_rings", "para_localization", "ortho_localization", "e_pi",
+                     "n_pi", "n_electrons", "n_jobs", "sweeps", "flags", "status")
+_REACTIVITY_INT = ("rings", "n_rings", "n_pi", "n_electrons", "n_jobs", "sweeps", "flags", "status")
+
+
+def reactivity_outputs(B: int, A: int, M: int) -> dict:
+    """The thirteen output arrays of gaudi_reactivity / gaudi_host_reactivity, in argument order."""
+    R, S = RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE
+    shape = dict(atom_localization=(B, REACTIVITY_KINDS, A), free_valence=(B, A), rings=(B, R, S), para_localization=(B, R, 3),
+                 ortho_localization=(B, M))
+    return {k: np.zeros(shape.get(k, (B,)), np.int32 if k in _REACTIVITY_INT else np.float32) for k in REACTIVITY_ARRAYS}
+
+
+def reactivity_args(tables, elem, n_atoms, bonds, n_bonds, charge, with_bonds, slices, out):
+    """The arguments both entry points share: the Hueckel table, the molecules as bond_orders takes them, charge [B] int32 or None,
+    with_bonds, slices (0: the entry point chooses), the outputs."""
+    for a in (elem, n_atoms, bonds, n_bonds) + (() if charge is None else (charge,)):
+        assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    B, A, M = elem.shape[0], elem.shape[1], bonds.shape[1]
+    assert elem.shape == (B, A) and bonds.shape == (B, M, 2) and n_atoms.shape == (B,) and n_bonds.shape == (B,)
+    assert charge is None or charge.shape == (B,)
+    assert out["atom_localization"].shape == (B, REACTIVITY_KINDS, A) and out["ortho_localization"].shape == (B, M)
+    ptr = lambda k: out[k].ctypes.data_as(IP if k in _REACTIVITY_INT else FP)
+    return ((C.byref(tables), B, A, M, elem.ctypes.data_as(IP), n_atoms.ctypes.data_as(IP), bonds.ctypes.data_as(IP),
+             n_bonds.ctypes.data_as(IP), None if charge is None else charge.ctypes.data_as(IP), int(bool(with_bonds)), int(slices))
+            + tuple(ptr(k) for k in REACTIVITY_ARRAYS))
+
+
+def host_reactivity(tables, elem, n_atoms, bonds, n_bonds, charge=None, with_bonds=True, slices=0) -> dict:
+    """gaudi_host_reactivity (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = reactivity_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_reactivity(*reactivity_args(tables, elem, n_atoms, bonds, n_bonds, charge, with_bonds, slices, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_reactivity failed ({rc})")
     return out
 
 

@@ -144,6 +144,7 @@ struct gaudi_handle {
                         // gaudi_ppp_cis (ppp_cis.inc): the hand-over rows and its ten outputs
   DevBuf d_kekule[14];  // gaudi_kekule (kekule.inc): its four inputs, the tables and its nine outputs
   DevBuf d_ring[23];    // gaudi_ring_currents (ring_current.inc): its six inputs, the tier lists, the table and its fifteen outputs
+  DevBuf d_react[21];   // gaudi_reactivity (reactivity.inc): its five inputs, the tier lists, the table, its thirteen outputs and the job words
   DevBuf d_vtpar, d_vttrace, d_vtdev;  // value targets: per-molecule parameter rows, the guidance trace, the VtDev that names them
   PinBuf p_pred, p_dpred;     // gaudi_sample_cb: pred [B,K] device -> host, dT/dpred [B,K] host -> device, once per step
   PinBuf p_z, p_dz;           // gaudi_sample_cbz: z_s [B,N,D] device -> host, scale * dT/dz host -> device
@@ -238,7 +239,7 @@ struct gaudi_handle {
       ms = 0.0;
       n = 0;
     }
-  } prof_log, stab_log, atoms_log, rings_log, bonds_log, canon_log, fp_log, sub_log, huckel_log, ppp_log, ppp_cis_log, kekule_log, ring_log;
+  } prof_log, stab_log, atoms_log, rings_log, bonds_log, canon_log, fp_log, sub_log, huckel_log, ppp_log, ppp_cis_log, kekule_log, ring_log, react_log;
   long long prof_steps = 0;
 #ifdef GAUDI_STAMPS
   DevBuf d_stamps;
@@ -1631,6 +1632,7 @@ void gaudi_destroy(gaudi_handle* h) {
   h->ppp_cis_log.reset(true);
   h->kekule_log.reset(true);
   h->ring_log.reset(true);
+  h->react_log.reset(true);
   DevBuf* bufs[] = {&h->edm_w, &h->pred_w, &h->coef_d, &h->edm_w4, &h->pred_w4, &h->edm_ws, &h->pred_ws, &h->d_mask, &h->d_order, &h->d_edges, &h->d_emask, &h->d_npairs,
                     &h->d_seg, &h->d_zin, &h->d_zout, &h->d_t, &h->d_x, &h->d_h, &h->d_noise, &h->d_nan, &h->d_dpred,
                     &h->d_pred, &h->d_tw, &h->d_stash, &h->d_chain, &h->d_sx, &h->d_stype, &h->d_sn,
@@ -1648,6 +1650,7 @@ void gaudi_destroy(gaudi_handle* h) {
   for (DevBuf& b : h->d_ppp) b.release();
   for (DevBuf& b : h->d_kekule) b.release();
   for (DevBuf& b : h->d_ring) b.release();
+  for (DevBuf& b : h->d_react) b.release();
   pt_release(h);
   et_release(h);
   h->p_pred.release();
@@ -2142,6 +2145,7 @@ int gaudi_profile_reset(gaudi_handle* h, int enable) {
   h->ppp_cis_log.reset(false);
   h->kekule_log.reset(false);
   h->ring_log.reset(false);
+  h->react_log.reset(false);
   h->prof_steps = 0;
   h->prof = enable != 0;
   return GAUDI_OK;
@@ -2189,5 +2193,6 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 #include "ppp_cis.inc"
 #include "kekule.inc"
 #include "ring_current.inc"
+#include "reactivity.inc"
 #include "nll_host.inc"
 #include "edm_train_host.inc"

@@ -917,6 +917,24 @@ class Engine:
         self._check(rc, "gaudi_ring_currents")
         return out
 
+    def reactivity_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_reactivity since profile_reset(True): one launch per capacity tier present."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_reactivity_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_reactivity_profile_get")
+        return int(n.value), float(ms.value)
+
+    def reactivity(self, tables, elem, n_atoms, bonds, n_bonds, charge=None, with_bonds=True, slices=0):
+        """gaudi_reactivity on packed arrays: a HuckelTables (gaudi_amd.huckel.c_huckel_tables), the molecules as bond_orders takes
+        them, charge [B] int32 or None, with_bonds (the ortho localization energies: one more solve per pi bond), slices (waves
+        per molecule, 1..16; 0: chosen from the compute units and the batch) -> dict of the raw output arrays
+        (_lib.REACTIVITY_ARRAYS: atom_localization [B,3,A], free_valence [B,A] float32, rings [B,32,6], n_rings [B] int32,
+        para_localization [B,32,3], ortho_localization [B,M], e_pi [B] float32, n_pi / n_electrons / n_jobs / sweeps / flags /
+        status [B] int32; NaN where an entry does not apply).  gaudi_amd.reactivity.localization is the interface on top."""
+        out = _lib.reactivity_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_reactivity(self.h, *_lib.reactivity_args(tables, elem, n_atoms, bonds, n_bonds, charge, with_bonds, slices, out))
+        self._check(rc, "gaudi_reactivity")
+        return out
+
     def ppp_cis_profile_get(self):
         """(launches, summed milliseconds) of the CIS kernel of gaudi_ppp_cis since profile_reset(True): one launch per call (the
         SCF launches of those calls are ppp_profile_get's)."""

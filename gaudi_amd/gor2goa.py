@@ -142,7 +142,7 @@ def _is_packed(molecules) -> bool:
 
 
 def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
-                   canonical=False, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False):
+                   canonical=False, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, reactivity=False):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -174,7 +174,12 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     ring_currents: a call of gaudi_ring_currents (gaudi_amd.aromaticity.ring_currents) on the records' atoms3d
     adds ring_current_max, ring_current_min (the extreme Hueckel-London ring currents in units of benzene's; NaN where nothing was
     solved, 0.0 without a ring) and ring_current_status (gaudi_amd.aromaticity.RING_CURRENT_STATUS_NAMES; 4 for a molecule that was
-    not built) to every record.  With ring_currents=False nothing changes and no launch is made."""
+    not built) to every record.  With ring_currents=False nothing changes and no launch is made.
+    reactivity: a call of gaudi_reactivity (gaudi_amd.reactivity; no ortho solves) adds
+    min_atom_localization (the smallest radical localization energy over the pi centres that carry a hydrogen), min_para_localization
+    (the smallest para-localization energy over the six-rings), both in |beta| and NaN where nothing was solved or nothing of the
+    kind exists, and reactivity_status (gaudi_amd.reactivity.STATUS_NAMES; 4 for a molecule that was not built) to every record.
+    With reactivity=False nothing changes and no launch is made."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -226,6 +231,10 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     if ring_currents:
         from .aromaticity import ring_current_fields
         for rec, extra in zip(out, ring_current_fields(out, dataset, engine=eng)):
+            rec.update(extra)
+    if reactivity:
+        from .reactivity import record_fields as reactivity_fields
+        for rec, extra in zip(out, reactivity_fields(out, dataset, engine=eng)):
             rec.update(extra)
     return out
 

@@ -1010,6 +1010,61 @@ int gaudi_host_ring_currents(const gaudi_huckel_tables* tables, int B, int A, in
  * summed duration (HIP events). */
 int gaudi_ring_currents_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- Hueckel localization energies: where a conjugated molecule reacts and how easily (csrc/reactivity.inc, DESIGN.md section
+ * 8r), for B molecules. ----
+ * The graph, the pi centres, the classes, the matrix M, the electron count n_el, `charge` and the level filling are gaudi_huckel's,
+ * and so is E_pi: the sum of occupation * x in |beta| (the larger x, the lower the level).  The parent has n centres.  Deleting
+ * centres removes their rows, columns and bonds from M; h, k and the pair values of what survives stay as the table gives them.  A
+ * residual system is filled as the parent is: two electrons per level from the lowest energy, the last level may hold one; an
+ * empty residual system has E_pi = 0.
+ *   atom localization (Wheland), per pi centre r and kind q = the pi electrons that stay localized on r (2 electrophilic, 1
+ *     radical, 0 nucleophilic attack):  L_q(r) = E_pi(parent) - [E_pi(parent without r, n_el - q electrons) + q h_r];
+ *     undefined where n_el - q < 0 or n_el - q > 2 (n - 1).
+ *   para localization (Brown), per chordless six-ring c[0..5] of pi centres and pair k = 0..2 of opposite positions (c[k], c[k+3]):
+ *     L = E_pi(parent) - [E_pi(parent without both, n_el - 2 electrons) + h_r + h_s]; undefined where n_el - 2 < 0 or > 2 (n - 2).
+ *   ortho (bond) localization, per listed bond between two pi centres: the same with the bonded pair (with_bonds != 0 only).
+ *   free valence, per pi centre: 1.7320508f less the pi bond orders (gaudi_huckel's) to its pi neighbours: the carbon scale.
+ *   rings: the chordless cycles of 4, 5 or 6 pi centres of the graph of pi centres, ordered by sorted atom tuple, each in cycle
+ *     order from its smallest atom towards the smaller of that atom's two ring neighbours.  At most 32: the rings are taken in the
+ *     order of their smallest centre, and those of a smallest centre are kept while the count through that centre stays within
+ *     32; when any is dropped, flags has GAUDI_REACTIVITY_RINGS_TRUNCATED and the para values are those of the kept rings.
+ * One molecule costs n + 3 (six-rings) + (pi bonds) diagonalisations beside the parent's: its jobs, in this fixed order.  A residual
+ * diagonalisation that uses GAUDI_HUCKEL_MAX_SWEEPS sweeps without converging leaves its entries undefined and sets
+ * GAUDI_REACTIVITY_SWEEP_CAP in flags.
+ * Outputs: atom_localization_out [B][3][A] (kinds q = 0, 1, 2); free_valence_out [B][A]; rings_out [B][32][6] atom indices, -1 padded;
+ * n_rings_out [B]; para_localization_out [B][32][3]; ortho_localization_out [B][M]; e_pi_out [B] (gaudi_huckel's e_pi, bit for
+ * bit); n_pi_out, n_electrons_out, n_jobs_out, sweeps_out (the parent's and every residual solve's), flags_out, status_out [B].
+ * In a molecule with status OK every fp32 entry that carries no value holds the quiet NaN 0x7fc00000: a hydrogen, an excluded
+ * atom, the padding beyond n_atoms / n_bonds / n_rings, a four- or five-ring, a bond to an atom that is no pi centre, an undefined
+ * kind, every ortho entry when with_bonds = 0.  status: the GAUDI_HUCKEL_* values with their meaning there; NOT_CONVERGED is the
+ * parent's diagonalisation.  Every status but OK leaves every other output of the molecule zero.
+ * One launch per capacity tier present (tiers as gaudi_huckel); the grid is (molecule, slice), one 64-lane wave per workgroup:
+ * every wave solves the parent, then the jobs j = slice (mod slices).  slices: 1..16, or 0 to have the entry point choose
+ * ceil(2 * compute units / molecules of the tier) clamped to 1..16 (gaudi_host_reactivity: 1).  Individually rounded fp32 in a
+ * fixed order, no atomics: the outputs do not depend on `slices`, the tier, the batch or the molecule's place in it, and are bit
+ * for bit what gaudi_host_reactivity returns.  B * max(3 A, 224 + M) <= 2^31.
+ * Not here: PPP-level (self-consistent) localization, transition states, steric effects, regioselectivity beyond these indices. */
+#define GAUDI_REACTIVITY_KINDS 3
+#define GAUDI_REACTIVITY_MAX_SLICES 16
+#define GAUDI_REACTIVITY_SWEEP_CAP 1       /* flags */
+#define GAUDI_REACTIVITY_RINGS_TRUNCATED 2
+int gaudi_reactivity(gaudi_handle* h, const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem,
+                     const int32_t* n_atoms, const int32_t* bonds, const int32_t* n_bonds, const int32_t* charge, int with_bonds,
+                     int slices, float* atom_localization_out, float* free_valence_out, int32_t* rings_out, int32_t* n_rings_out,
+                     float* para_localization_out, float* ortho_localization_out, float* e_pi_out, int32_t* n_pi_out,
+                     int32_t* n_electrons_out, int32_t* n_jobs_out, int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out);
+/* gaudi_reactivity without a handle: the same source text (csrc/reactivity.inc: reactivity_molecule) compiled for the host and run
+ * serially, slice after slice.  Test surface for the CPU suite, not a CPU fallback: gaudi_amd never calls it on its own. */
+int gaudi_host_reactivity(const gaudi_huckel_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                          const int32_t* bonds, const int32_t* n_bonds, const int32_t* charge, int with_bonds, int slices,
+                          float* atom_localization_out, float* free_valence_out, int32_t* rings_out, int32_t* n_rings_out,
+                          float* para_localization_out, float* ortho_localization_out, float* e_pi_out, int32_t* n_pi_out,
+                          int32_t* n_electrons_out, int32_t* n_jobs_out, int32_t* sweeps_out, int32_t* flags_out,
+                          int32_t* status_out);
+/* Number of gaudi_reactivity launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed
+ * duration (HIP events; uploads, downloads and the host-side fold are outside). */
+int gaudi_reactivity_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* Device Philox stream used when noise == NULL, exposed for tests: out[draw][b][e], e < n_elem. */
 int gaudi_philox_normal(gaudi_handle* h, uint64_t seed, int64_t sample_offset, int B, int n_elem, int draw0,
                         int n_draws, float* out);
