@@ -104,6 +104,7 @@ PPP_MAX_ITERATIONS, PPP_OPEN_SHELL, PPP_BAD_GEOMETRY, PPP_DEGENERATE, PPP_SCF_CA
 PPP_MATAGA_NISHIMOTO, PPP_OHNO = 0, 1
 PPP_CIS_MAX_WINDOW, PPP_CIS_MAX_STATES = 8, 64
 PPP_CIS_JACOBI_CAP, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE, PPP_CIS_TRIPLET_UNSTABLE = 16, 32, 64, 128
+PPP_OPEN_TIE = 256
 PPP_CIS_FLAGS = PPP_CIS_JACOBI_CAP | PPP_CIS_TRUNCATED | PPP_CIS_WINDOW_EDGE | PPP_CIS_TRIPLET_UNSTABLE
 # include/gaudi_hip.h: GAUDI_RING_CURRENT_*
 RING_CURRENT_MAX_RINGS, RING_CURRENT_MAX_SIZE, RING_CURRENT_SMALL_GAP, RING_CURRENT_RINGS_UNDEFINED = 32, 6, 9, 1
@@ -206,6 +207,9 @@ EXPORTS = {
     "gaudi_ppp": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
     "gaudi_host_ppp": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6),
     "gaudi_ppp_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_ppp_open": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP]),
+    "gaudi_host_ppp_open": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP]),
+    "gaudi_ppp_open_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_ppp_cis": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_host_ppp_cis": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_ppp_cis_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -298,7 +302,8 @@ _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_n
                "gaudi_fp_pick_diverse", "gaudi_fp_select_stages_get")  # ... and the circular fingerprints with their similarity, clusters and diverse picks
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
-_PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get")  # ... and the PPP levels and excited states
+_PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get", "gaudi_ppp_open",
+                "gaudi_ppp_open_profile_get")  # ... and the PPP levels and excited states
 _KEKULE_EXPORTS = ("gaudi_kekule", "gaudi_kekule_profile_get")  # ... and the Kekule structure counts
 _RING_CURRENT_EXPORTS = ("gaudi_ring_currents", "gaudi_ring_currents_profile_get")  # ... and the ring currents
 _REACTIVITY_EXPORTS = ("gaudi_reactivity", "gaudi_reactivity_profile_get")  # ... and the localization energies
@@ -817,6 +822,40 @@ def host_ppp(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, repulsion=
     rc = lib.gaudi_host_ppp(*ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_ppp failed ({rc})")
+    return out
+
+
+PPP_OPEN_ARRAYS = PPP_ARRAYS + ("spin_density", "e_state", "he_correction", "n_open", "somo")
+
+
+def ppp_open_outputs(B: int, A: int, M: int) -> dict:
+    """The twenty-three output arrays of gaudi_ppp_open / gaudi_host_ppp_open, in argument order."""
+    out = ppp_outputs(B, A, M)
+    out.update(spin_density=np.zeros((B, A), np.float32), e_state=np.zeros(B, np.float64), he_correction=np.zeros(B, np.float64),
+               n_open=np.zeros(B, np.int32), somo=np.zeros((B, 2), np.int32))
+    return out
+
+
+def ppp_open_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, damping, out):
+    """ppp_args with multiplicity [B] int32 or None behind the charge and the five further outputs at the end."""
+    base = ppp_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, repulsion, damping, out)
+    B, A = elem.shape
+    assert multiplicity is None or (multiplicity.dtype == np.int32 and multiplicity.flags["C_CONTIGUOUS"] and multiplicity.shape == (B,))
+    assert out["spin_density"].shape == (B, A) and out["somo"].shape == (B, 2)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    return (base[:10] + (None if multiplicity is None else multiplicity.ctypes.data_as(IP),) + base[10:]
+            + (out["spin_density"].ctypes.data_as(FP), dp(out["e_state"]), dp(out["he_correction"]), out["n_open"].ctypes.data_as(IP),
+               out["somo"].ctypes.data_as(IP)))
+
+
+def host_ppp_open(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, multiplicity=None, repulsion=PPP_MATAGA_NISHIMOTO,
+                  damping=0.25) -> dict:
+    """gaudi_host_ppp_open (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = ppp_open_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_ppp_open(*ppp_open_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, damping, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_ppp_open failed ({rc})")
     return out
 
 

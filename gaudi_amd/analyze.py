@@ -169,7 +169,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
                                 pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False,
-                                ring_currents=False, cluster_threshold=None, reactivity=False):
+                                ring_currents=False, cluster_threshold=None, reactivity=False, ppp_dscf=False):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -241,7 +241,12 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     reactivity: one more call (gaudi_amd.reactivity) gives every built molecule its Hueckel localization
     energies.  The dict gains ``mol_min_para_localization`` and ``mol_min_atom_localization``, float64 arrays over the BUILT
     molecules in list order, in |beta| (NaN where nothing was solved or the molecule has no six-ring / no centre with a hydrogen).
-    With ``reactivity=False`` nothing changes and no launch is made."""
+    With ``reactivity=False`` nothing changes and no launch is made.
+
+    ppp_dscf: one more call (gaudi_amd.ppp.ionization) solves every built molecule as neutral, cation and
+    anion by the half-electron method.  The dict gains ``mol_ppp_ip_dscf`` and ``mol_ppp_ea_dscf``, float64 arrays over the BUILT
+    molecules in list order with the delta-SCF ionisation potential and electron affinity in eV (NaN where a state was not solved).
+    With ``ppp_dscf=False`` nothing changes and no launch is made."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -263,6 +268,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["ring_currents"] = True
     if reactivity:
         extra["reactivity"] = True
+    if ppp_dscf:
+        extra["ppp_dscf"] = True
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing
@@ -339,6 +346,10 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         rows = [r for r, ok in zip(recs, built) if ok]
         d["mol_min_para_localization"] = np.array([r["min_para_localization"] for r in rows], np.float64)
         d["mol_min_atom_localization"] = np.array([r["min_atom_localization"] for r in rows], np.float64)
+    if ppp_dscf:
+        rows = [r for r, ok in zip(recs, built) if ok]
+        d["mol_ppp_ip_dscf"] = np.array([r["ppp_ip_dscf"] for r in rows], np.float64)
+        d["mol_ppp_ea_dscf"] = np.array([r["ppp_ea_dscf"] for r in rows], np.float64)
     return d, [m for m, ok in zip(molecule_list, keep) if ok]
 
 

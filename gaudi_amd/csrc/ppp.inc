@@ -21,6 +21,10 @@
 // Every fp32 operation is individually rounded (contraction off, correctly rounded / and sqrtf) and every sum runs in one fixed
 // order; delta_p and the diagonal maximum are reduced through their bits.  No atomics.  Every branch around a fence or a reduction
 // is lane-uniform.
+// OPEN SHELLS (ppp_open.inc, gaudi_ppp_open; DESIGN.md section 8s): ppp_molecule<P, true> is the same text with Dewar's half-electron
+// occupations 2 / 1 / 0 -- a row is (molecule, charge, multiplicity) -- and, after the eighteen outputs, the state energy in fp64,
+// the spin density and the singly occupied ranks.  Every addition stands behind `if constexpr (Open)`: ppp_molecule<P, false> is
+// operation for operation what it was.
 
 namespace gaudi {
 
@@ -29,6 +33,7 @@ constexpr float kPppCoulomb = 14.397f;         // e^2 / (4 pi eps0) in eV Angstr
 constexpr float kPppDeltaP = 1.52587890625e-5f;  // 2^-16
 constexpr float kPppTooClose2 = 0.25f;         // (0.5 Angstrom)^2
 constexpr float kPppDegenerate = 1e-3f;        // eV
+static_assert(GAUDI_PPP_OPEN_TIE == 2 * GAUDI_PPP_CIS_TRIPLET_UNSTABLE, "the next free bit of flags");
 // The hand-over to the CIS stage (ppp_cis.inc): a row of global scratch per molecule, in floats.  n and n_occ as their bits, the
 // separation of the window's edge level from the level just outside it on either side (-1: no level outside), the centres'
 // coordinates and gamma, the active levels (0..7 occupied in ascending rank, 8..15 empty) and their eigenvector columns; behind
@@ -65,6 +70,8 @@ struct PppSmem {
   signed char cls[P];
   unsigned char pidx[kCanonMaxHeavy];  // vertex -> pi centre, none for an excluded atom
   signed char vcls[kCanonMaxHeavy];    // vertex -> site class, -1 for an excluded atom
+  double xd[P];                        // per-column partial sums in fp64 (ppp_molecule<P, true> only; last, so that every other
+                                       // member keeps the offset it had)
 };
 static_assert(sizeof(PppSmem<128>) <= 160 * 1024, "the largest tier fits the LDS of a CU");
 
@@ -86,6 +93,11 @@ struct PppParams {
   signed char* site_class;    // [B][A]
   int *n_pi, *n_electrons, *n_excluded, *iterations, *sweeps, *flags, *status;  // [B]
   float *homo, *lumo, *gap, *e_electronic, *e_core, *delta_p;                   // [B]
+  // gaudi_ppp_open only (ppp_molecule<P, true>)
+  const int* multiplicity;  // [B]
+  float* spin_density;      // [B][A]
+  double *e_state, *he_correction;  // [B]
+  int *n_open, *somo;       // [B]; [B][2]
 };
 
 // gamma_rs, r != s: symmetric in its bits.  S is any work space with xyz and gam (ppp_cis.inc has one).
@@ -122,6 +134,42 @@ __host__ __device__ inline void ppp_fock(PppSmem<P>& s, const float* pm, int n, 
   }
 }
 
+// P_rc of the ranked columns: twice the n_occ doubly occupied ones, and once the n_open singly occupied ones behind them.
+template <int P, bool Open>
+__host__ __device__ __forceinline__ float ppp_density(const PppSmem<P>& s, int r, int c, int n_occ, int n_open) {
+#pragma clang fp contract(off)
+  float acc = 0.0f;
+  for (int k = 0; k < n_occ; ++k) {
+    const int i = s.ord[k];
+    acc = acc + s.v[r][i] * s.v[c][i];
+  }
+  float p = 2.0f * acc;
+  if constexpr (Open) {
+    if (n_open > 0) {
+      float half = 0.0f;
+      for (int k = n_occ; k < n_occ + n_open; ++k) {
+        const int i = s.ord[k];
+        half = half + s.v[r][i] * s.v[c][i];
+      }
+      p = p + half;
+    }
+  }
+  return p;
+}
+
+// Whether the levels on either boundary of the open set (ranks n_occ - 1 | n_occ, n_occ + n_open - 1 | n_occ + n_open) are closer
+// than kPppDegenerate; lev(rank) reads a ranked level.  Every lane computes the same answer from LDS.
+template <class L>
+__host__ __device__ __forceinline__ bool ppp_open_tie(const L& lev, int n, int n_occ, int n_open) {
+#pragma clang fp contract(off)
+  if (n_open == 0) return false;
+  const int top = n_occ + n_open;
+  bool tie = false;
+  if (n_occ >= 1) tie = lev(n_occ) - lev(n_occ - 1) < kPppDegenerate;
+  if (top < n) tie = tie || lev(top) - lev(top - 1) < kPppDegenerate;
+  return tie;
+}
+
 // What the CIS stage needs of a solved molecule, written to its hand-over row (the layout above); s.ord and s.lev are the final ranks.
 template <int P>
 __host__ __device__ inline void ppp_cis_handover(const PppParams& Q, const PppSmem<P>& s, int b, int n, int n_occ, int lane) {
@@ -151,7 +199,7 @@ __host__ __device__ inline void ppp_cis_handover(const PppParams& Q, const PppSm
 }
 
 // One molecule; `pm` is its scratch row.  Every branch around a fence or a reduction is lane-uniform.
-template <int P>
+template <int P, bool Open = false>
 __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, float* pm, int b, int lane) {
 #pragma clang fp contract(off)
   const int A = Q.in.A, M = Q.in.M;
@@ -193,7 +241,15 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
   if (n == 0) refused = GAUDI_HUCKEL_NO_PI;
   else if (n > P) refused = GAUDI_HUCKEL_OVERFLOW;  // (the host sends a molecule to a tier that holds its heavy atoms: P is 128 here)
   else if (n_el < 0 || n_el > 2 * n) refused = GAUDI_HUCKEL_BAD_INPUT;  // a charge the pi system cannot carry
-  else if (n_el & 1) refused = GAUDI_PPP_OPEN_SHELL;
+  else if (!Open && (n_el & 1)) refused = GAUDI_PPP_OPEN_SHELL;
+  int n_open = 0;
+  if constexpr (Open) {  // the multiplicity: 0 is the lowest the parity allows; n_open = multiplicity - 1 singly occupied levels
+    const int asked = Q.multiplicity[b];
+    if (asked >= 0 && asked <= 3) n_open = (asked == 0 ? 1 + (n_el & 1) : asked) - 1;  // (only then: no arithmetic on a wild value)
+    if (refused == GAUDI_HUCKEL_OK &&
+        (asked < 0 || asked > 3 || n_el < n_open || ((n_el - n_open) & 1) || ((n_el - n_open) >> 1) + n_open > n))
+      refused = GAUDI_HUCKEL_BAD_INPUT;
+  }
   if (refused != GAUDI_HUCKEL_OK) {
     if (lane == 0) Q.status[b] = refused;
     return;
@@ -249,23 +305,32 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
   const int repulsion = Q.repulsion;
   for (int c = lane; c < n; c += kRwLanes) {
     float att = 0.0f, rep = 0.0f;
+    [[maybe_unused]] double rep64 = 0.0;
     for (int r = 0; r < n; ++r) {
       pm[r * P + c] = r == c ? s.zc[c] : 0.0f;
       if (r == c) continue;
       const float g = ppp_gamma(s, r, c, repulsion);
       att = att + s.zc[r] * g;
       if (r < c) rep = rep + (s.zc[r] * s.zc[c]) * g;
+      if constexpr (Open)
+        if (r < c) rep64 = rep64 + (double)((s.zc[r] * s.zc[c]) * g);
     }
     s.hd[c] = -s.ion[c] - att;
     s.x[c] = rep;
+    if constexpr (Open) s.xd[c] = rep64;
   }
   rw_fence();
   float e_core = 0.0f;
-  if (lane == 0)
+  double e_core64 = 0.0;
+  if (lane == 0) {
     for (int c = 0; c < n; ++c) e_core = e_core + s.x[c];
+    if constexpr (Open)
+      for (int c = 0; c < n; ++c) e_core64 = e_core64 + s.xd[c];
+  }
   rw_fence();
   // ---- 2. the SCF loop
-  const int n_occ = n_el >> 1;
+  const int n_occ = (n_el - n_open) >> 1;  // the doubly occupied levels
+  bool tie = false;
   const float damping = Q.damping, fresh = 1.0f - damping;
   float threshold = 0.0f, delta = 0.0f;
   int iterations = 0, sweeps = 0;
@@ -309,15 +374,11 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
       s.ord[rk] = (unsigned char)i;
     }
     rw_fence();
+    if constexpr (Open) tie = tie || ppp_open_tie([&](int k) { return s.x[s.ord[k]]; }, n, n_occ, n_open);
     float worst = 0.0f;
     for (int c = lane; c < n; c += kRwLanes)
       for (int r = 0; r < n; ++r) {
-        float acc = 0.0f;
-        for (int k = 0; k < n_occ; ++k) {
-          const int i = s.ord[k];
-          acc = acc + s.v[r][i] * s.v[c][i];
-        }
-        const float fresh_p = 2.0f * acc, old = pm[r * P + c], d = fabsf(fresh_p - old);
+        const float fresh_p = ppp_density<P, Open>(s, r, c, n_occ, n_open), old = pm[r * P + c], d = fabsf(fresh_p - old);
         worst = d > worst ? d : worst;
         const float mixed = fresh * fresh_p + damping * old;
         pm[r * P + c] = mixed;
@@ -331,13 +392,9 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
   // ---- 3. P = P_new of the last eigenvectors; a = F(P); levels = v^T F v
   for (int c = lane; c < n; c += kRwLanes)
     for (int r = 0; r < n; ++r) {
-      float acc = 0.0f;
-      for (int k = 0; k < n_occ; ++k) {
-        const int i = s.ord[k];
-        acc = acc + s.v[r][i] * s.v[c][i];
-      }
-      pm[r * P + c] = 2.0f * acc;
-      if (r == c) s.pd[c] = 2.0f * acc;
+      const float p = ppp_density<P, Open>(s, r, c, n_occ, n_open);
+      pm[r * P + c] = p;
+      if (r == c) s.pd[c] = p;
     }
   rw_fence();
   ppp_fock(s, pm, n, lane, repulsion);
@@ -359,7 +416,7 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
       const float xj = s.x[j];
       rk += xj < xi || (xj == xi && j < i);
     }
-    const int oc = rk < n_occ ? 2 : 0;
+    const int oc = rk < n_occ ? 2 : rk < n_occ + n_open ? 1 : 0;
     s.ord[rk] = (unsigned char)i;
     s.lev[rk] = xi;
     Q.levels[(size_t)b * kHuckelMaxPi + rk] = xi;
@@ -370,25 +427,66 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
   // the density of these ranks: the energy by columns, the charges from its diagonal
   for (int c = lane; c < n; c += kRwLanes) {
     float e = 0.0f;
+    [[maybe_unused]] double e64 = 0.0;
     for (int r = 0; r < n; ++r) {
-      float acc = 0.0f;
-      for (int k = 0; k < n_occ; ++k) {
-        const int i = s.ord[k];
-        acc = acc + s.v[r][i] * s.v[c][i];
-      }
-      const float p = 2.0f * acc, f = s.a[r][c];
-      e = e + p * ((r == c ? s.hd[c] : ppp_beta(s, r, c)) + f);
+      const float p = ppp_density<P, Open>(s, r, c, n_occ, n_open), f = s.a[r][c];
+      const float hf = (r == c ? s.hd[c] : ppp_beta(s, r, c)) + f;
+      e = e + p * hf;
+      if constexpr (Open) e64 = e64 + (double)p * (double)hf;
       if (r == c) Q.pi_charge[(size_t)b * A + s.g.hv[s.vert[c]]] = s.zc[c] - p;
     }
     s.x[c] = e;
+    if constexpr (Open) {
+      s.xd[c] = e64;
+      float spin = 0.0f;
+      for (int k = n_occ; k < n_occ + n_open; ++k) {
+        const float vc = s.v[c][s.ord[k]];
+        spin = spin + vc * vc;
+      }
+      Q.spin_density[(size_t)b * A + s.g.hv[s.vert[c]]] = spin;
+    }
   }
   rw_fence();
+  if constexpr (Open) {
+    // the state energy in fp64 from the fp32 elements: E_he = 1/2 sum P (H + F); the half-electron correction
+    // -J_mm / 4 (doublet), -(J_mm + J_nn) / 4 - K_mn / 2 (triplet), by columns and then over the columns in ascending order
+    double e_he = 0.0, corr = 0.0;
+    if (lane == 0)
+      for (int c = 0; c < n; ++c) e_he = e_he + s.xd[c];
+    rw_fence();
+    if (n_open > 0) {
+      const int m = s.ord[n_occ], q = s.ord[n_occ + n_open - 1];  // the open columns (the same one for a doublet)
+      for (int c = lane; c < n; c += kRwLanes) {
+        const double cm = (double)s.v[c][m], cq = (double)s.v[c][q];
+        double jm = 0.0, jq = 0.0, kx = 0.0;
+        for (int r = 0; r < n; ++r) {
+          const double g = (double)(r == c ? s.gam[c] : ppp_gamma(s, r, c, repulsion));
+          const double rm = (double)s.v[r][m], rq = (double)s.v[r][q];
+          jm = jm + ((rm * rm) * (cm * cm)) * g;
+          jq = jq + ((rq * rq) * (cq * cq)) * g;
+          kx = kx + ((rm * rq) * (cm * cq)) * g;
+        }
+        s.xd[c] = n_open == 1 ? 0.25 * jm : 0.25 * (jm + jq) + 0.5 * kx;
+      }
+      rw_fence();
+      if (lane == 0)
+        for (int c = 0; c < n; ++c) corr = corr + s.xd[c];
+    }
+    if (lane == 0) {
+      Q.he_correction[b] = 0.0 - corr;
+      Q.e_state[b] = (0.5 * e_he - corr) + e_core64;
+      Q.n_open[b] = n_open;
+      for (int k = 0; k < 2; ++k) Q.somo[(size_t)b * 2 + k] = k < n_open ? n_occ + k : -1;
+    }
+    tie = tie || ppp_open_tie([&](int k) { return s.lev[k]; }, n, n_occ, n_open);
+  }
   if (lane == 0) {
-    int ih = n_occ - 1, il = n_occ;
+    int ih = n_occ + n_open - 1, il = n_occ + n_open;
     if (ih < 0) ih = il;   // no electron: both names go to the lowest level
     if (il >= n) il = ih;  // no empty level: both to the highest
     int flags = 0;
-    if (n_occ >= 1 && n_occ < n && s.lev[n_occ] - s.lev[n_occ - 1] < kPppDegenerate) flags |= GAUDI_PPP_DEGENERATE;
+    if (il > ih && s.lev[il] - s.lev[ih] < kPppDegenerate) flags |= GAUDI_PPP_DEGENERATE;
+    if (tie) flags |= GAUDI_PPP_OPEN_TIE;
     if (!converged) flags |= GAUDI_PPP_SCF_CAP;
     if (!jacobi_ok) flags |= GAUDI_PPP_JACOBI_CAP;
     float e = 0.0f;
@@ -417,12 +515,7 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
     if (hi_ == kCanonNone || hj == kCanonNone) continue;
     const int pr = s.pidx[hi_], ps = s.pidx[hj];
     if (pr == kCanonNone || ps == kCanonNone) continue;
-    float acc = 0.0f;
-    for (int q = 0; q < n_occ; ++q) {
-      const int i = s.ord[q];
-      acc = acc + s.v[pr][i] * s.v[ps][i];
-    }
-    Q.pi_bond_order[(size_t)b * M + k] = 2.0f * acc;
+    Q.pi_bond_order[(size_t)b * M + k] = ppp_density<P, Open>(s, pr, ps, n_occ, n_open);
   }
 }
 

@@ -900,6 +900,23 @@ class Engine:
         self._check(rc, "gaudi_ppp")
         return out
 
+    def ppp_open_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_ppp_open since profile_reset(True): one launch per capacity tier present."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_ppp_open_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_ppp_open_profile_get")
+        return int(n.value), float(ms.value)
+
+    def ppp_open(self, tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, multiplicity=None, repulsion=0, damping=0.25):
+        """gaudi_ppp_open on packed arrays: ``ppp``'s arguments with multiplicity [B] int32 or None (0: the lowest the parity
+        allows) behind the charge -> dict of ``ppp``'s eighteen arrays (occupation 2 / 1 / 0) and spin_density [B,A] float32,
+        e_state / he_correction [B] float64, n_open [B] and somo [B,2] int32 (_lib.PPP_OPEN_ARRAYS).  gaudi_amd.ppp.states is
+        the interface on top."""
+        out = _lib.ppp_open_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_ppp_open(self.h, *_lib.ppp_open_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity,
+                                                                 repulsion, damping, out))
+        self._check(rc, "gaudi_ppp_open")
+        return out
+
     def ring_currents_profile_get(self):
         """(launches, summed milliseconds) of gaudi_ring_currents since profile_reset(True): one launch per capacity tier present."""
         n, ms = C.c_int32(0), C.c_double(0.0)

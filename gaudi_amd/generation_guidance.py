@@ -54,7 +54,8 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
            valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None, huckel=False,
-           ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, cluster_threshold=None, diverse=None, reactivity=False):
+           ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, cluster_threshold=None, diverse=None, reactivity=False,
+           ppp_dscf=False):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -89,6 +90,10 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     and the dict gains ``min_para_localization`` and ``min_atom_localization`` float64 [B]: the smallest para-localization energy
     over the six-rings and the smallest radical localization energy over the centres that carry a hydrogen, in |beta| (NaN where
     the molecule was not built or not solved).  With ``reactivity=False`` nothing is launched.
+    ppp_dscf (with with_atoms): one more call (gaudi_amd.ppp.ionization) and the dict gains ``ppp_ip_dscf`` and
+    ``ppp_ea_dscf`` float64 [B]: the delta-SCF ionisation potential and electron affinity of every molecule in eV -- orbital
+    relaxation included, next to the Koopmans ``ppp_ip`` / ``ppp_ea`` (NaN where the molecule was not built or a state was not
+    solved).  With ``ppp_dscf=False`` nothing is launched.
     cluster_threshold (with with_atoms and similarity): Butina clusters of the built molecules at that similarity
     (gaudi_amd.similarity.cluster), and the dict gains ``n_clusters`` and ``largest_cluster_fraction`` =
     the largest cluster / built molecules -- whether the batch collapsed onto a few skeletons, which the one mean ``diversity``
@@ -105,13 +110,13 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
                      with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
-                     cluster_threshold=cluster_threshold, diverse=diverse, reactivity=reactivity)
+                     cluster_threshold=cluster_threshold, diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
                  n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None, patterns=None,
                  pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-                 cluster_threshold=None, diverse=None, reactivity=False):
+                 cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -126,7 +131,8 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
     setting gets its own ``ppp_s1``, ``ppp_t1`` and ``ppp_bright``.  aromaticity: as design takes it; every setting gets its own
     ``kekule_count`` and ``clar``.  ring_currents: as design takes it; every setting gets its own ``ring_current_max`` and
     ``ring_current_min``.  reactivity: as design takes it; every setting gets its own ``min_para_localization`` and
-    ``min_atom_localization``.  cluster_threshold / diverse: as design takes them; every setting gets its own ``n_clusters``,
+    ``min_atom_localization``.  ppp_dscf: as design takes it; every setting gets its own ``ppp_ip_dscf`` and ``ppp_ea_dscf``.
+    cluster_threshold / diverse: as design takes them; every setting gets its own ``n_clusters``,
     ``largest_cluster_fraction`` and ``diverse_indices`` (indices into the setting's own molecules)."""
     from .models_edm import ValueTarget
     model.eval()
@@ -179,7 +185,7 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
                       em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library, patterns,
                       pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold=cluster_threshold,
-                      diverse=diverse, reactivity=reactivity)
+                      diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
@@ -187,13 +193,13 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
            prop_dist=None, with_atoms=False, valence_check=False, similarity=False, patterns=None, pattern_options=None,
-           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, diverse=None, reactivity=False):
+           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, diverse=None, reactivity=False, ppp_dscf=False):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought.  similarity (with with_atoms): the seeds go
     through rings_to_atoms as well, and the dict gains ``diversity`` and ``similarity_to_seed`` [B], the similarity of every
     refined molecule with its own seed (0.0 where either was not built): how far the refinement moved.  patterns /
-    pattern_options: as design takes them, on the refined molecules.  huckel, ppp, ppp_cis, aromaticity, ring_currents, reactivity: as design takes them, on
+    pattern_options: as design takes them, on the refined molecules.  huckel, ppp, ppp_cis, aromaticity, ring_currents, reactivity, ppp_dscf: as design takes them, on
     the refined molecules.  diverse: as design takes it, on the refined molecules."""
     model.eval()
     cond_predictor.eval()
@@ -208,7 +214,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
                     seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
-                    diverse=diverse, reactivity=reactivity)
+                    diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     if similarity:
         from .similarity import fingerprints, rowwise_similarity
@@ -221,7 +227,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
 
 def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None,
            patterns=None, pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-           cluster_threshold=None, diverse=None, reactivity=False):
+           cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -270,13 +276,17 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
         from .reactivity import most_reactive
         ext = most_reactive(recs, dataset, bonds=False, engine=engine)
         out.update(min_para_localization=ext["min_para_localization"], min_atom_localization=ext["min_atom_localization"])
+    if ppp_dscf:
+        from .ppp import dscf_fields
+        ext = dscf_fields(recs, dataset, engine=engine)
+        out.update(ppp_ip_dscf=ext["ppp_ip_dscf"], ppp_ea_dscf=ext["ppp_ea_dscf"])
     return out
 
 
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
               with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None, patterns=None,
               pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-              cluster_threshold=None, diverse=None, reactivity=False):
+              cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     if patterns is not None and not with_atoms:
         raise ValueError("patterns need with_atoms=True")
@@ -292,6 +302,8 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
         raise ValueError("ring_currents needs with_atoms=True")
     if reactivity and not with_atoms:
         raise ValueError("reactivity needs with_atoms=True")
+    if ppp_dscf and not with_atoms:
+        raise ValueError("ppp_dscf needs with_atoms=True")
     if (similarity or train_library is not None) and not with_atoms:
         raise ValueError("similarity / train_library need with_atoms=True")
     if train_library is not None and not similarity:
@@ -317,7 +329,7 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
     if with_atoms:
         out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library,
                           patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold, diverse,
-                          reactivity))
+                          reactivity, ppp_dscf))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

@@ -12,7 +12,12 @@ values are recalled, not verified: ``parameters=`` replaces any of it, and no ac
 
 ``excited_states`` / ``optical`` / ``spectrum`` go one step further (csrc/ppp_cis.inc): configuration
 interaction over single excitations on that ground state, in an active window of at most 8 occupied and 8 empty levels -- the
-lowest singlet and triplet excitation energies, the singlet-triplet gap, oscillator strengths and the lowest bright singlet."""
+lowest singlet and triplet excitation energies, the singlet-triplet gap, oscillator strengths and the lowest bright singlet.
+
+``states`` / ``ionization`` / ``triplet`` take open shells (csrc/ppp_open.inc): Dewar's half-electron method --
+one restricted SCF with occupations 2 / 1 / 0 and a closed-form energy correction -- for radical ions, neutral radicals and
+triplets; delta-SCF ionisation potentials and electron affinities (orbital relaxation included) next to the Koopmans values, and
+the spin density of the unpaired electrons."""
 from __future__ import annotations
 
 import copy
@@ -22,7 +27,8 @@ import os
 import numpy as np
 
 from ._lib import (HUCKEL_MAX_CLASSES, PPP_CIS_FLAGS, PPP_CIS_JACOBI_CAP, PPP_CIS_TRIPLET_UNSTABLE, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE,
-                   PPP_DEGENERATE, PPP_JACOBI_CAP, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, PPP_SCF_CAP, GaudiError, PPPTables)
+                   PPP_DEGENERATE, PPP_JACOBI_CAP, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, PPP_OPEN_TIE, PPP_SCF_CAP, GaudiError,
+                   PPPTables)
 from .analyze import _engine
 from .huckel import _charges
 
@@ -171,7 +177,7 @@ def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="ma
       n_pi, n_electrons, n_excluded, iterations (SCF), sweeps (Jacobi, all iterations), delta_p (the last max |P_new - P|)
       levels         [n_pi] float32, eV, ascending;  occupation: [n_pi] 0 or 2
       homo, lumo, gap = lumo - homo, ip = -homo, ea = -lumo (Koopmans), e_electronic, e_core, e_total = their sum: eV
-      open_shell     status 7: an odd electron count, nothing solved
+      open_shell     status 7: an odd electron count, nothing solved (``states`` solves these)
       degenerate     the frontier levels are closer than 1e-3 eV: charges and bond orders are returned but not unique
       flags          degenerate (2); why the status is 1: the iteration cap (4), a Jacobi solve at its cap (8)
       pi_charge      [n] float32 = z - P_rr, zero on hydrogens and excluded atoms;  pi_bond_order: [m] float32, zero on bonds not
@@ -181,6 +187,104 @@ def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="ma
         return []
     raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
     return [_orbital_record(raw, i, na, nb) for i in range(len(na))]
+
+
+def _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine):
+    """One gaudi_ppp_open call for the list: a row is (molecule, charge, multiplicity)."""
+    elem, na, bonds, nb, xyz = _pack(molecules)
+    mult = _charges(multiplicity, len(na))
+    raw = _engine(engine).ppp_open(c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)), mult,
+                                   _repulsion(repulsion), float(damping))
+    return raw, na, nb
+
+
+def states(molecules, dataset="cata", charge=0, multiplicity=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25,
+           engine=None) -> list:
+    """``orbitals`` for open and closed shells alike, by the half-electron method (gaudi_ppp_open): one
+    launch per capacity tier for the whole list.  A row is (molecule, charge, multiplicity); ``charge`` and ``multiplicity`` are
+    one integer or one per molecule.  ``multiplicity``: 1, 2 or 3; 0 is the lowest the electron count allows (1 for an even count,
+    2 for an odd one); a multiplicity the electron count cannot have is status 2.  Returns one dict per row with every key of
+    ``orbitals`` (``occupation`` holds 2 / 1 / 0; ``homo`` is the highest occupied level, the singly occupied one where there is
+    one, ``lumo`` the first empty one; ``open_shell`` is never set) and
+      e_state        float (float64): the energy of the state in eV, electronic and core, the half-electron correction included --
+                     differences of these are ionisation potentials, electron affinities and triplet energies
+      he_correction  float (float64): -J_mm / 4 for a doublet, -(J_mm + J_nn) / 4 - K_mn / 2 for a triplet, 0 for a singlet
+      spin_density   [n] float32: the sum over the singly occupied orbitals of v_r^2 per atom (it sums to n_open)
+      n_open, somo   the number of singly occupied levels and their ranks in ``levels`` (a list of n_open integers)
+      multiplicity   n_open + 1
+      open_tie       a level within 1e-3 eV of the singly occupied set on either side, in some iteration or in the result: which
+                     orbital of a degenerate pair holds the unpaired electron was arbitrary (the benzene cation), and charges, bond
+                     orders and spin densities depend on it"""
+    molecules = list(molecules)
+    if not molecules:
+        return []
+    raw, na, nb = _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine)
+    out = []
+    for i in range(len(na)):
+        rec = _orbital_record(raw, i, na, nb)
+        k = int(raw["n_open"][i])
+        rec.update(e_state=float(raw["e_state"][i]), he_correction=float(raw["he_correction"][i]),
+                   spin_density=raw["spin_density"][i, :na[i]].copy(), n_open=k, somo=[int(v) for v in raw["somo"][i, :k]],
+                   multiplicity=k + 1 if rec["status"] in (0, 1) else 0, open_tie=bool(rec["flags"] & PPP_OPEN_TIE))
+        out.append(rec)
+    return out
+
+
+def _ionization(raw, B) -> dict:
+    """ip, ea, ... from the raw arrays of a 3B-row call: neutral, cation, anion."""
+    ok = (raw["status"] == 0).reshape(3, B)
+    e = raw["e_state"].reshape(3, B)
+    tie = ((raw["flags"] & PPP_OPEN_TIE) != 0).reshape(3, B)
+    ip = np.where(ok[0] & ok[1], e[1] - e[0], np.nan)
+    ea = np.where(ok[0] & ok[2], e[0] - e[2], np.nan)
+    return dict(ip=ip, ea=ea, fundamental_gap=ip - ea, ip_koopmans=np.where(ok[0], -raw["homo"][:B].astype(np.float64), np.nan),
+                ea_koopmans=np.where(ok[0], -raw["lumo"][:B].astype(np.float64), np.nan), open_tie=tie.any(0),
+                status=raw["status"].reshape(3, B).copy())
+
+
+def ionization(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
+    """Delta-SCF ionisation potential and electron affinity at the fixed geometry, in ONE call of 3B rows: every molecule at
+    ``charge`` (its "neutral" form), with one electron less and with one more, each at its lowest multiplicity -- so a neutral
+    radical works too.  Returns float64 [B] arrays in eV: ``ip`` = e_state(cation) - e_state(neutral), ``ea`` = e_state(neutral) -
+    e_state(anion), ``fundamental_gap`` = ip - ea, and the Koopmans values of the neutral form ``ip_koopmans`` = -homo,
+    ``ea_koopmans`` = -lumo (for a radical both are read off the half-electron levels); NaN where a state needed is not solved.
+    ``open_tie`` bool [B]: one of the three states chose its singly occupied orbital within a degenerate pair (the energies are
+    still those of one valid choice).  ``status`` int32 [3, B]: the rows' statuses, neutral / cation / anion."""
+    molecules = list(molecules)
+    B = len(molecules)
+    if not B:
+        return dict({k: np.zeros(0) for k in ("ip", "ea", "fundamental_gap", "ip_koopmans", "ea_koopmans")}, open_tie=np.zeros(0, bool),
+                    status=np.zeros((3, 0), np.int32))
+    q = _charges(charge, B)
+    q = np.zeros(B, np.int32) if q is None else q
+    raw, _, _ = _raw_open(molecules * 3, dataset, np.concatenate([q, q + 1, q - 1]).astype(np.int32), 0, parameters, repulsion, damping,
+                          engine)
+    return _ionization(raw, B)
+
+
+def triplet(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
+    """The delta-SCF triplet energy of even-electron molecules in ONE call of 2B rows (singlet, triplet): ``t1`` float64 [B] =
+    e_state(triplet) - e_state(singlet) in eV, next to ``optical``'s CIS ``t1``; NaN where either state is not solved (an odd
+    electron count among them).  ``open_tie`` bool [B] as ``ionization`` gives it; ``status`` int32 [2, B]."""
+    molecules = list(molecules)
+    B = len(molecules)
+    if not B:
+        return dict(t1=np.zeros(0), open_tie=np.zeros(0, bool), status=np.zeros((2, 0), np.int32))
+    q = _charges(charge, B)
+    q = np.zeros(B, np.int32) if q is None else q
+    raw, _, _ = _raw_open(molecules * 2, dataset, np.concatenate([q, q]).astype(np.int32),
+                          np.concatenate([np.ones(B, np.int32), np.full(B, 3, np.int32)]), parameters, repulsion, damping, engine)
+    ok = (raw["status"] == 0).reshape(2, B)
+    e = raw["e_state"].reshape(2, B)
+    return dict(t1=np.where(ok[0] & ok[1], e[1] - e[0], np.nan), open_tie=((raw["flags"] & PPP_OPEN_TIE) != 0).reshape(2, B).any(0),
+                status=raw["status"].reshape(2, B).copy())
+
+
+def dscf_fields(molecules, dataset="cata", engine=None) -> dict:
+    """What the keyword ppp_dscf=True adds: {"ppp_ip_dscf", "ppp_ea_dscf"} float64 [B] (``ionization``'s ip and ea, NaN where not
+    solved) and "ppp_dscf_status" int [B], the largest of the three states' statuses (0: all solved)."""
+    ion = ionization(molecules, dataset, engine=engine)
+    return dict(ppp_ip_dscf=ion["ip"], ppp_ea_dscf=ion["ea"], ppp_dscf_status=ion["status"].max(0) if ion["status"].size else np.zeros(0, np.int32))
 
 
 def gap(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> np.ndarray:

@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get, gaudi_fp_neighbours, gaudi_fp_cluster, gaudi_fp_pick_diverse, gaudi_host_fp_neighbours, gaudi_host_fp_cluster, gaudi_host_fp_pick_diverse, gaudi_fp_select_stages_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get, gaudi_fp_neighbours, gaudi_fp_cluster, gaudi_fp_pick_diverse, gaudi_host_fp_neighbours, gaudi_host_fp_cluster, gaudi_host_fp_pick_diverse, gaudi_fp_select_stages_get, gaudi_ppp_open, gaudi_host_ppp_open, gaudi_ppp_open_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -850,6 +850,57 @@ int gaudi_host_ppp(const gaudi_ppp_tables* tables, int B, int A, int M, const in
  * (HIP events; uploads and downloads are outside). */
 int gaudi_ppp_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
+/* ---- PPP for open shells: radical ions, delta-SCF IP / EA and triplets (csrc/ppp_open.inc). ----
+ * Dewar's half-electron method on gaudi_ppp's machinery.  Everything of gaudi_ppp stays: sites, table, beta, gamma_rs, H, the Fock
+ * formula, P0 = diag(z), damping, the 2^-16 stopping rule, the iteration cap, the Jacobi threshold rule, ranking by counting with
+ * ties going to the smaller index.  What is new:
+ *   A row is (molecule, charge, multiplicity).  multiplicity [B] int32 (NULL: all zero) is 1, 2 or 3; 0 means the lowest the parity
+ *   allows (1 for even n_electrons, 2 for odd).  n_open = multiplicity - 1, n_c = (n_electrons - n_open) / 2.  BAD_INPUT where
+ *   n_electrons - n_open is odd or negative, where n_c + n_open > n_pi, or where the multiplicity is outside 0..3 (after the
+ *   refusals of the graph, NO_PI and OVERFLOW).  GAUDI_PPP_OPEN_SHELL is never returned.
+ *   Density: P = sum over the ranked columns of occ_k v_k v_k^T, occ = 2 for ranks below n_c, 1 for the next n_open, 0 above --
+ *   in the loop (ranks of the rotated diagonal) and in the result (ranks of the Rayleigh quotients).  F(P) is gaudi_ppp's formula
+ *   unchanged: the half-electron operator.
+ *   Energy: E_he = 1/2 sum over r, s of P_rs (H_rs + F_rs).  For an open orbital m: J_mm = sum over r, s of v_rm^2 v_sm^2 gamma_rs
+ *   (gamma_rr on the diagonal); for two open orbitals K_mn = sum over r, s of v_rm v_rn v_sm v_sn gamma_rs.
+ *     doublet: E = E_he - J_mm / 4;    triplet: E = E_he - (J_mm + J_nn) / 4 - K_mn / 2;    e_state = E + e_core.
+ *   (So a single pi centre with one electron has e_state = -I, and triplet ethylene e_state = -2 I_C.)
+ *   E_he, the J and K sums and e_core are accumulated in fp64 from the fp32 elements (P_rs, H_rs + F_rs, v, gamma_rs, z_r z_s
+ *   gamma_rs), by columns over r ascending and then over the columns ascending; nothing is rounded to fp32.
+ * Outputs: the eighteen of gaudi_ppp -- occupation_out holds 2 / 1 / 0; homo_out is the highest occupied level (the open one when
+ * there is one) and lumo_out the first empty one -- and then
+ *   spin_density_out [B][A] fp32 = sum over the open orbitals of v_rm^2, zero on hydrogens and excluded atoms;
+ *   e_state_out, he_correction_out [B] fp64: E + e_core and E - E_he in eV;
+ *   n_open_out [B] int32;  somo_out [B][2] int32: the ranks of the open levels, -1 where there is none.
+ * flags gains GAUDI_PPP_OPEN_TIE (rows with n_open > 0 only): in some iteration's ranking or in the result the two levels on
+ * either boundary of the open set (ranks n_c - 1 | n_c, or n_c + n_open - 1 | n_c + n_open) differ by less than 1e-3 eV -- the
+ * choice of singly occupied orbital was arbitrary within a degenerate pair (the benzene cation); the values are still returned, and
+ * per-atom quantities depend on that choice.  GAUDI_PPP_DEGENERATE is lumo - homo below 1e-3 eV as in gaudi_ppp.
+ * On a row of multiplicity 1 the eighteen outputs are gaudi_ppp's bit for bit and the flag is never set.  A refused row is zero.
+ * Tiers, launches, LDS and scratch as gaudi_ppp; bit for bit what gaudi_host_ppp_open returns, the doubles included.
+ * Not here: UHF and ROHF coupling operators, open-shell singlets, CIS / ring currents / localization on an open-shell reference. */
+#define GAUDI_PPP_OPEN_TIE 256
+int gaudi_ppp_open(gaudi_handle* h, const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                   const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge,
+                   const int32_t* multiplicity, int repulsion, float damping, float* levels_out, uint8_t* occupation_out,
+                   float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out, int32_t* n_pi_out,
+                   int32_t* n_electrons_out, int32_t* n_excluded_out, int32_t* iterations_out, int32_t* sweeps_out,
+                   int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out, float* gap_out,
+                   float* e_electronic_out, float* e_core_out, float* delta_p_out, float* spin_density_out, double* e_state_out,
+                   double* he_correction_out, int32_t* n_open_out, int32_t* somo_out);
+/* gaudi_ppp_open without a handle: the same source text compiled for the host and run serially.  Test surface, not a fallback. */
+int gaudi_host_ppp_open(const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                        const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge,
+                        const int32_t* multiplicity, int repulsion, float damping, float* levels_out, uint8_t* occupation_out,
+                        float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out, int32_t* n_pi_out,
+                        int32_t* n_electrons_out, int32_t* n_excluded_out, int32_t* iterations_out, int32_t* sweeps_out,
+                        int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out, float* gap_out,
+                        float* e_electronic_out, float* e_core_out, float* delta_p_out, float* spin_density_out,
+                        double* e_state_out, double* he_correction_out, int32_t* n_open_out, int32_t* somo_out);
+/* Number of gaudi_ppp_open launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed
+ * duration. */
+int gaudi_ppp_open_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
 /* ---- PPP-CIS excited states: S1, T1 and oscillator strengths (csrc/ppp_cis.inc). ----
  * gaudi_ppp, then configuration interaction over single excitations on its ground state.  After a solve with status OK: the levels
  * eps by rank, the normalised eigenvector columns C, n_occ = n_electrons / 2, n = n_pi, the centres' coordinates and gamma.
@@ -987,7 +1038,7 @@ int gaudi_kekule_profile_get(gaudi_handle* h, int32_t* n_launches, double* total
  * One 64-lane wave per molecule, tiers and launches as gaudi_huckel, whose Jacobi routine and Rayleigh pass it runs.  Individually
  * rounded fp32 in a fixed order, no atomics: the outputs are a function of the molecule's own arrays and bit for bit what
  * gaudi_host_ring_currents returns.  B * max(A, M, 192) <= 2^31.
- * Not here: coupled (PPP) currents, open shells, current-density maps, NICS, non-planar corrections. */
+ * Not here: coupled (PPP) currents, ring currents of open shells, current-density maps, NICS, non-planar corrections. */
 #define GAUDI_RING_CURRENT_MAX_RINGS 32
 #define GAUDI_RING_CURRENT_MAX_SIZE 6
 #define GAUDI_RING_CURRENT_SMALL_GAP 9       /* a status, after GAUDI_PPP_BAD_GEOMETRY */
