@@ -210,6 +210,9 @@ EXPORTS = {
     "gaudi_ppp_open": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP]),
     "gaudi_host_ppp_open": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP]),
     "gaudi_ppp_open_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gaudi_ppp_scf": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_int32, C.c_int32, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP, FP, IP]),
+    "gaudi_host_ppp_scf": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, IP, C.c_int, C.c_int32, C.c_int32, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [FP, C.POINTER(C.c_double), C.POINTER(C.c_double), IP, IP, FP, IP]),
+    "gaudi_ppp_scf_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gaudi_ppp_cis": (C.c_int, [C.c_void_p, C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_host_ppp_cis": (C.c_int, [C.POINTER(PPPTables)] + [C.c_int] * 3 + [IP] * 4 + [FP, IP, C.c_int, C.c_float] + [FP, U8P, FP, FP, C.POINTER(C.c_int8)] + [IP] * 7 + [FP] * 6 + [C.c_int] + [FP] * 4 + [U8P, FP] + [IP] * 4),
     "gaudi_ppp_cis_profile_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -303,7 +306,7 @@ _FP_EXPORTS = ("gaudi_circular_fingerprint", "gaudi_fp_library_set", "gaudi_fp_n
 _SUB_EXPORTS = ("gaudi_substructure_search", "gaudi_substructure_profile_get")  # ... and the substructure search
 _HUCKEL_EXPORTS = ("gaudi_huckel", "gaudi_huckel_profile_get")  # ... and the Hueckel levels
 _PPP_EXPORTS = ("gaudi_ppp", "gaudi_ppp_profile_get", "gaudi_ppp_cis", "gaudi_ppp_cis_profile_get", "gaudi_ppp_open",
-                "gaudi_ppp_open_profile_get")  # ... and the PPP levels and excited states
+                "gaudi_ppp_open_profile_get", "gaudi_ppp_scf", "gaudi_ppp_scf_profile_get")  # ... and the PPP levels and excited states
 _KEKULE_EXPORTS = ("gaudi_kekule", "gaudi_kekule_profile_get")  # ... and the Kekule structure counts
 _RING_CURRENT_EXPORTS = ("gaudi_ring_currents", "gaudi_ring_currents_profile_get")  # ... and the ring currents
 _REACTIVITY_EXPORTS = ("gaudi_reactivity", "gaudi_reactivity_profile_get")  # ... and the localization energies
@@ -856,6 +859,36 @@ def host_ppp_open(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, multi
     rc = lib.gaudi_host_ppp_open(*ppp_open_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, damping, out))
     if rc != 0:
         raise GaudiError(f"gaudi_host_ppp_open failed ({rc})")
+    return out
+
+
+PPP_SCF_ARRAYS = PPP_OPEN_ARRAYS + ("diis_error", "n_extrapolated")
+PPP_DIIS_MAX, PPP_DIIS_ERROR = 8, 2.0 ** -10
+
+
+def ppp_scf_outputs(B: int, A: int, M: int) -> dict:
+    """The twenty-five output arrays of gaudi_ppp_scf / gaudi_host_ppp_scf, in argument order."""
+    out = ppp_open_outputs(B, A, M)
+    out.update(diis_error=np.zeros(B, np.float32), n_extrapolated=np.zeros(B, np.int32))
+    return out
+
+
+def ppp_scf_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, diis_size, diis_start, damping, out):
+    """ppp_open_args with the history's length and its first iteration in front of the damping and the two further outputs at the end."""
+    base = ppp_open_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, damping, out)
+    assert out["diis_error"].shape == out["n_extrapolated"].shape == (elem.shape[0],)
+    return base[:12] + (int(diis_size), int(diis_start)) + base[12:] + (out["diis_error"].ctypes.data_as(FP), out["n_extrapolated"].ctypes.data_as(IP))
+
+
+def host_ppp_scf(tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, multiplicity=None, repulsion=PPP_MATAGA_NISHIMOTO, diis_size=6,
+                 diis_start=3, damping=0.25) -> dict:
+    """gaudi_host_ppp_scf (needs no device): the kernel's source text run serially on the host.  Test surface only."""
+    lib = load_library()
+    out = ppp_scf_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+    rc = lib.gaudi_host_ppp_scf(*ppp_scf_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity, repulsion, diis_size,
+                                              diis_start, damping, out))
+    if rc != 0:
+        raise GaudiError(f"gaudi_host_ppp_scf failed ({rc})")
     return out
 
 

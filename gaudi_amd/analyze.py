@@ -169,7 +169,7 @@ def positions2adj(x, ring_type, tol=0.1, dataset="cata", engine=None):
 def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fingerprints=None, engine=None, valence_check=False,
                                 exact=False, train_keys=None, similarity=False, train_library=None, patterns=None,
                                 pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False,
-                                ring_currents=False, cluster_threshold=None, reactivity=False, ppp_dscf=False):
+                                ring_currents=False, cluster_threshold=None, reactivity=False, ppp_dscf=False, ppp_scf=None):
     """The call shape of analyze_rdkit_validity_for_molecules (analyze/analyze.py:180-231) on top of gaudi_rings_to_atoms: every
     molecule is converted to its graph of atoms (gaudi_amd.gor2goa.rings_to_atoms, one launch for the whole list) and counted.
 
@@ -246,7 +246,10 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
     ppp_dscf: one more call (gaudi_amd.ppp.ionization) solves every built molecule as neutral, cation and
     anion by the half-electron method.  The dict gains ``mol_ppp_ip_dscf`` and ``mol_ppp_ea_dscf``, float64 arrays over the BUILT
     molecules in list order with the delta-SCF ionisation potential and electron affinity in eV (NaN where a state was not solved).
-    With ``ppp_dscf=False`` nothing changes and no launch is made."""
+    With ``ppp_dscf=False`` nothing changes and no launch is made.
+
+    ppp_scf: "diis" sends the calls of ``ppp=True`` and ``ppp_dscf=True`` to gaudi_ppp_scf (Pulay's DIIS); the
+    keys are the same.  Absent (None) or "damped": what it was.  It launches nothing by itself."""
     from .gor2goa import rings_to_atoms
     if train_library is not None and not similarity:
         raise ValueError("train_library needs similarity=True")
@@ -270,6 +273,8 @@ def analyze_atoms_for_molecules(molecule_list, tol=0.1, dataset="cata", train_fi
         extra["reactivity"] = True
     if ppp_dscf:
         extra["ppp_dscf"] = True
+    if ppp_scf is not None:
+        extra["ppp_scf"] = ppp_scf
     recs = rings_to_atoms(molecule_list, dataset, tol, fingerprint=True, engine=engine, **extra)
     if not recs:
         raise GaudiError("empty molecule list")  # as analyze_validity_for_molecules: no fractions of nothing

@@ -143,6 +143,7 @@ struct gaudi_handle {
   DevBuf d_ppp[38];     // gaudi_ppp (ppp.inc): its six inputs, the tier lists, the table, its eighteen outputs and the density scratch;
                         // gaudi_ppp_cis (ppp_cis.inc): the hand-over rows and its ten outputs
   DevBuf d_ppp_open[33];  // gaudi_ppp_open (ppp_open.inc): gaudi_ppp's inputs and the multiplicity, its twenty-three outputs, the density scratch
+  DevBuf d_ppp_scf[35];   // gaudi_ppp_scf (ppp_scf.inc): gaudi_ppp_open's inputs, its twenty-five outputs, the scratch of one launch
   DevBuf d_kekule[14];  // gaudi_kekule (kekule.inc): its four inputs, the tables and its nine outputs
   DevBuf d_ring[23];    // gaudi_ring_currents (ring_current.inc): its six inputs, the tier lists, the table and its fifteen outputs
   DevBuf d_react[21];   // gaudi_reactivity (reactivity.inc): its five inputs, the tier lists, the table, its thirteen outputs and the job words
@@ -240,7 +241,7 @@ struct gaudi_handle {
       ms = 0.0;
       n = 0;
     }
-  } prof_log, stab_log, atoms_log, rings_log, bonds_log, canon_log, fp_log, sub_log, huckel_log, ppp_log, ppp_cis_log, ppp_open_log, kekule_log, ring_log, react_log;
+  } prof_log, stab_log, atoms_log, rings_log, bonds_log, canon_log, fp_log, sub_log, huckel_log, ppp_log, ppp_cis_log, ppp_open_log, ppp_scf_log, kekule_log, ring_log, react_log;
   long long prof_steps = 0;
 #ifdef GAUDI_STAMPS
   DevBuf d_stamps;
@@ -1632,6 +1633,7 @@ void gaudi_destroy(gaudi_handle* h) {
   h->ppp_log.reset(true);
   h->ppp_cis_log.reset(true);
   h->ppp_open_log.reset(true);
+  h->ppp_scf_log.reset(true);
   h->kekule_log.reset(true);
   h->ring_log.reset(true);
   h->react_log.reset(true);
@@ -1651,6 +1653,7 @@ void gaudi_destroy(gaudi_handle* h) {
   for (DevBuf& b : h->d_huckel) b.release();
   for (DevBuf& b : h->d_ppp) b.release();
   for (DevBuf& b : h->d_ppp_open) b.release();
+  for (DevBuf& b : h->d_ppp_scf) b.release();
   for (DevBuf& b : h->d_kekule) b.release();
   for (DevBuf& b : h->d_ring) b.release();
   for (DevBuf& b : h->d_react) b.release();
@@ -2147,6 +2150,7 @@ int gaudi_profile_reset(gaudi_handle* h, int enable) {
   h->ppp_log.reset(false);
   h->ppp_cis_log.reset(false);
   h->ppp_open_log.reset(false);
+  h->ppp_scf_log.reset(false);
   h->kekule_log.reset(false);
   h->ring_log.reset(false);
   h->react_log.reset(false);
@@ -2195,6 +2199,7 @@ int gaudi_set_steps_per_launch(gaudi_handle* h, int steps) {
 #include "huckel.inc"
 #include "ppp.inc"
 #include "ppp_open.inc"
+#include "ppp_scf.inc"
 #include "ppp_cis.inc"
 #include "kekule.inc"
 #include "ring_current.inc"

@@ -25,6 +25,10 @@
 // occupations 2 / 1 / 0 -- a row is (molecule, charge, multiplicity) -- and, after the eighteen outputs, the state energy in fp64,
 // the spin density and the singly occupied ranks.  Every addition stands behind `if constexpr (Open)`: ppp_molecule<P, false> is
 // operation for operation what it was.
+// PULAY'S DIIS (ppp_scf.inc, gaudi_ppp_scf; DESIGN.md section 8t): ppp_molecule<P, true, true> is the same text again with a ring of
+// Fock matrices and commutators behind the density in the scratch row ([1 + 2 * diis_size][P * P] floats, every matrix under the
+// density's own rule: a lane reads only the columns it wrote).  Every addition stands behind `if constexpr (Diis)`:
+// ppp_molecule<P, *, false> is operation for operation what it was.
 
 namespace gaudi {
 
@@ -33,6 +37,8 @@ constexpr float kPppCoulomb = 14.397f;         // e^2 / (4 pi eps0) in eV Angstr
 constexpr float kPppDeltaP = 1.52587890625e-5f;  // 2^-16
 constexpr float kPppTooClose2 = 0.25f;         // (0.5 Angstrom)^2
 constexpr float kPppDegenerate = 1e-3f;        // eV
+constexpr int kPppDiisMax = GAUDI_PPP_DIIS_MAX;  // the longest history of ppp_molecule<P, Open, true>
+constexpr float kPppDiisError = GAUDI_PPP_DIIS_ERROR;  // eV: the commutator a converged row may be left with (section 8t)
 static_assert(GAUDI_PPP_OPEN_TIE == 2 * GAUDI_PPP_CIS_TRIPLET_UNSTABLE, "the next free bit of flags");
 // The hand-over to the CIS stage (ppp_cis.inc): a row of global scratch per molecule, in floats.  n and n_occ as their bits, the
 // separation of the window's edge level from the level just outside it on either side (-1: no level outside), the centres'
@@ -72,6 +78,8 @@ struct PppSmem {
   signed char vcls[kCanonMaxHeavy];    // vertex -> site class, -1 for an excluded atom
   double xd[P];                        // per-column partial sums in fp64 (ppp_molecule<P, true> only; last, so that every other
                                        // member keeps the offset it had)
+  double db[kPppDiisMax][kPppDiisMax];          // ppp_molecule<P, true, true> only (ppp_scf.inc): B by ring slot, and the bordered
+  double dm[kPppDiisMax + 1][kPppDiisMax + 2];  // system with its right-hand side
 };
 static_assert(sizeof(PppSmem<128>) <= 160 * 1024, "the largest tier fits the LDS of a CU");
 
@@ -98,6 +106,10 @@ struct PppParams {
   float* spin_density;      // [B][A]
   double *e_state, *he_correction;  // [B]
   int *n_open, *somo;       // [B]; [B][2]
+  // gaudi_ppp_scf only (ppp_molecule<P, true, true>); scratch is then [workgroups of the launch][1 + 2 * diis_size][P * P]
+  int diis_size, diis_start;
+  float* diis_error;    // [B]
+  int* n_extrapolated;  // [B]
 };
 
 // gamma_rs, r != s: symmetric in its bits.  S is any work space with xyz and gam (ppp_cis.inc has one).
@@ -199,7 +211,16 @@ __host__ __device__ inline void ppp_cis_handover(const PppParams& Q, const PppSm
 }
 
 // One molecule; `pm` is its scratch row.  Every branch around a fence or a reduction is lane-uniform.
-template <int P, bool Open = false>
+template <int P>
+__host__ __device__ inline float ppp_diis_error(PppSmem<P>& s, const float* pm, float* f_slot, float* e_slot, int n, int lane);
+template <int P>
+__host__ __device__ inline void ppp_diis_products(PppSmem<P>& s, const float* es, int size, int head, int len, int n, int lane);
+template <int P>
+__host__ __device__ inline int ppp_diis_solve(PppSmem<P>& s, int size, int& head, int& len, int lane);
+template <int P>
+__host__ __device__ inline void ppp_diis_combine(PppSmem<P>& s, const float* fs, int size, int head, int len, int n, int lane);
+
+template <int P, bool Open = false, bool Diis = false>
 __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, float* pm, int b, int lane) {
 #pragma clang fp contract(off)
   const int A = Q.in.A, M = Q.in.M;
@@ -335,8 +356,32 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
   float threshold = 0.0f, delta = 0.0f;
   int iterations = 0, sweeps = 0;
   bool converged = false, jacobi_ok = true;
+  [[maybe_unused]] int head = 0, len = 0, n_extrapolated = 0;  // the ring: its oldest slot and its length
+  [[maybe_unused]] float diis_error = 0.0f;
   for (;;) {
     ppp_fock(s, pm, n, lane, repulsion);
+    if constexpr (Diis) {
+      static_assert(Open, "the DIIS path is built on the open-shell text");
+      if (iterations + 1 >= Q.diis_start) {  // (lane-uniform: the iteration, the ring's length and the retries belong to the row)
+        const int size = Q.diis_size;
+        float* fs = pm + P * P;
+        float* es = fs + (size_t)size * (P * P);
+        rw_fence();
+        if (len == size) {  // the oldest entry leaves
+          head = head + 1 == size ? 0 : head + 1;
+          --len;
+        }
+        const int slot = (head + len) % size;
+        diis_error = ppp_diis_error(s, pm, fs + (size_t)slot * (P * P), es + (size_t)slot * (P * P), n, lane);
+        ++len;
+        ppp_diis_products(s, es, size, head, len, n, lane);
+        const int used = ppp_diis_solve(s, size, head, len, lane);
+        if (used >= 2) {
+          ppp_diis_combine(s, fs, size, head, len, n, lane);
+          ++n_extrapolated;
+        }
+      }
+    }
     for (int r = 0; r < n; ++r)
       for (int c = lane; c < n; c += kRwLanes) s.v[r][c] = r == c ? 1.0f : 0.0f;
     rw_fence();
@@ -380,13 +425,16 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
       for (int r = 0; r < n; ++r) {
         const float fresh_p = ppp_density<P, Open>(s, r, c, n_occ, n_open), old = pm[r * P + c], d = fabsf(fresh_p - old);
         worst = d > worst ? d : worst;
-        const float mixed = fresh * fresh_p + damping * old;
+        float mixed = fresh * fresh_p + damping * old;
+        if constexpr (Diis)
+          if (iterations >= Q.diis_start) mixed = fresh_p;  // no damping once the history runs
         pm[r * P + c] = mixed;
         if (r == c) s.pd[c] = mixed;
       }
     delta = __builtin_bit_cast(float, -rw_min(-huckel_bits(worst)));
     rw_fence();
     converged = delta <= kPppDeltaP;
+    if constexpr (Diis) converged = converged && diis_error <= kPppDiisError;  // (a stagnant history reads delta_p = 0)
     if (converged || iterations == kPppIterations) break;
   }
   // ---- 3. P = P_new of the last eigenvectors; a = F(P); levels = v^T F v
@@ -504,6 +552,10 @@ __host__ __device__ inline void ppp_molecule(const PppParams& Q, PppSmem<P>& s, 
     Q.sweeps[b] = sweeps;
     Q.flags[b] = flags;
     Q.status[b] = converged && jacobi_ok ? GAUDI_HUCKEL_OK : GAUDI_HUCKEL_NOT_CONVERGED;
+    if constexpr (Diis) {
+      Q.diis_error[b] = diis_error;
+      Q.n_extrapolated[b] = n_extrapolated;
+    }
   }
   const int n_atoms = Q.in.n_atoms[b], n_bonds = Q.in.n_bonds[b];
   for (int a = lane; a < n_atoms; a += kRwLanes) {

@@ -917,6 +917,24 @@ class Engine:
         self._check(rc, "gaudi_ppp_open")
         return out
 
+    def ppp_scf_profile_get(self):
+        """(launches, summed milliseconds) of gaudi_ppp_scf since profile_reset(True): one launch per capacity tier present, more
+        where a tier's scratch is split."""
+        n, ms = C.c_int32(0), C.c_double(0.0)
+        self._check(self.lib.gaudi_ppp_scf_profile_get(self.h, C.byref(n), C.byref(ms)), "gaudi_ppp_scf_profile_get")
+        return int(n.value), float(ms.value)
+
+    def ppp_scf(self, tables, elem, n_atoms, bonds, n_bonds, xyz, charge=None, multiplicity=None, repulsion=0, diis_size=6, diis_start=3,
+                damping=0.25):
+        """gaudi_ppp_scf on packed arrays: ``ppp_open``'s arguments with the DIIS history's length (2..8) and its first iteration
+        (at least 2) in front of the damping -> dict of ``ppp_open``'s twenty-three arrays and diis_error [B] float32, n_extrapolated
+        [B] int32 (_lib.PPP_SCF_ARRAYS).  gaudi_amd.ppp.states(..., scf="diis") is the interface on top."""
+        out = _lib.ppp_scf_outputs(elem.shape[0], elem.shape[1], bonds.shape[1])
+        rc = self.lib.gaudi_ppp_scf(self.h, *_lib.ppp_scf_args(tables, elem, n_atoms, bonds, n_bonds, xyz, charge, multiplicity,
+                                                               repulsion, diis_size, diis_start, damping, out))
+        self._check(rc, "gaudi_ppp_scf")
+        return out
+
     def ring_currents_profile_get(self):
         """(launches, summed milliseconds) of gaudi_ring_currents since profile_reset(True): one launch per capacity tier present."""
         n, ms = C.c_int32(0), C.c_double(0.0)

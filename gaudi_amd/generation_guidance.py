@@ -55,7 +55,7 @@ def eval_stability(x, one_hot, node_mask, edge_mask, dataset="cata", engine=None
 def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, scale, n_nodes, n_steps=None, with_atoms=False,
            valence_check=False, exact=False, similarity=False, train_library=None, patterns=None, pattern_options=None, huckel=False,
            ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, cluster_threshold=None, diverse=None, reactivity=False,
-           ppp_dscf=False):
+           ppp_dscf=False, ppp_scf=None):
     """generation_guidance.py:83-184: sample with guidance, check stability, evaluate the target and the predicted
     properties at t=0, rank all / stable molecules by target value.  Returns a dict instead of plotting.  n_steps: reverse
     steps per molecule (None: all T).  with_atoms: also convert every molecule to its graph of atoms (gaudi_amd.gor2goa, hydrogens
@@ -94,6 +94,8 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     ``ppp_ea_dscf`` float64 [B]: the delta-SCF ionisation potential and electron affinity of every molecule in eV -- orbital
     relaxation included, next to the Koopmans ``ppp_ip`` / ``ppp_ea`` (NaN where the molecule was not built or a state was not
     solved).  With ``ppp_dscf=False`` nothing is launched.
+    ppp_scf: "diis" sends what ``ppp`` and ``ppp_dscf`` compute to gaudi_ppp_scf (Pulay's DIIS) -- more rows
+    solved, the same keys; absent or "damped": what it was.  design_sweep and refine take it too.
     cluster_threshold (with with_atoms and similarity): Butina clusters of the built molecules at that similarity
     (gaudi_amd.similarity.cluster), and the dict gains ``n_clusters`` and ``largest_cluster_fraction`` =
     the largest cluster / built molecules -- whether the batch collapsed onto a few skeletons, which the one mean ``diversity``
@@ -110,13 +112,13 @@ def design(args, model, cond_predictor, target_function, nodes_dist, prop_dist, 
     print(f"Generated {x.shape[0]} molecules in {seconds:.2f} seconds")
     return _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
                      with_atoms, valence_check, exact, similarity, train_library, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
-                     cluster_threshold=cluster_threshold, diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
+                     cluster_threshold=cluster_threshold, diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf, ppp_scf=ppp_scf)
 
 
 def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, prop_dist, n_nodes, target=None, scale=1.0,
                  n_steps=None, with_atoms=False, valence_check=False, similarity=False, train_library=None, patterns=None,
                  pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-                 cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
+                 cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False, ppp_scf=None):
     """A sweep of the guidance strength and / or the aimed-at values in ONE sampling call: setting j runs on molecules
     j * batch_size .. (j + 1) * batch_size of a single batch whose value-target parameters differ per molecule
     (gaudi_sample_target), so the chip is filled once instead of len(settings) times.
@@ -185,7 +187,7 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
         d = _evaluate(args, model, cond_predictor, t, prop_dist, float(scale) * mult, x[lo:hi], one_hot[lo:hi], node_mask[lo:hi],
                       em[lo:hi].reshape(-1, 1), seconds, with_atoms, valence_check, False, similarity, train_library, patterns,
                       pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold=cluster_threshold,
-                      diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
+                      diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf, ppp_scf=ppp_scf)
         d["molecules_per_second"] = x.shape[0] / seconds
         out.append(d)
     return out
@@ -193,7 +195,7 @@ def design_sweep(args, model, cond_predictor, targets_or_scales, nodes_dist, pro
 
 def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, edge_mask, t_start, scale, n_steps=None,
            prop_dist=None, with_atoms=False, valence_check=False, similarity=False, patterns=None, pattern_options=None,
-           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, diverse=None, reactivity=False, ppp_dscf=False):
+           huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, diverse=None, reactivity=False, ppp_dscf=False, ppp_scf=None):
     """Guided refinement of given molecules: noise them to time index t_start and run the guided reverse process from there
     (GaudiModel.refine), then evaluate as design does.  Returns design's dict plus ``seed_target_function_values``, the target
     of the molecules that went in, so the caller sees what the refinement bought.  similarity (with with_atoms): the seeds go
@@ -214,7 +216,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
     print(f"Refined {bs} molecules in {seconds:.2f} seconds")
     out = _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, xr, h["categorical"], _like_ref(nm), _like_ref(em),
                     seconds, with_atoms, valence_check, False, similarity, None, patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents,
-                    diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf)
+                    diverse=diverse, reactivity=reactivity, ppp_dscf=ppp_dscf, ppp_scf=ppp_scf)
     out["seed_target_function_values"] = _like_ref(seed_vals)
     if similarity:
         from .similarity import fingerprints, rowwise_similarity
@@ -227,7 +229,7 @@ def refine(args, model, cond_predictor, target_function, x, one_hot, node_mask, 
 
 def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=False, similarity=False, train_library=None,
            patterns=None, pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-           cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
+           cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False, ppp_scf=None):
     """The graph of atoms of every molecule (hydrogens placed, fingerprints; with valence_check bond orders and charges too): what
     the reference's eval_stability gets from gor2goa + xyz2mol + RDKit (generation_guidance.py:69-80), as far as it goes without
     RDKit."""
@@ -261,10 +263,10 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
         out["huckel_gap"] = gap(recs, dataset, engine=engine)
     if ppp and not ppp_cis:
         from .ppp import frontier
-        out.update({"ppp_" + k: v for k, v in frontier(recs, dataset, engine=engine).items()})
+        out.update({"ppp_" + k: v for k, v in frontier(recs, dataset, engine=engine, scf=ppp_scf).items() if k in ("gap", "ip", "ea")})
     if ppp_cis:
         from .ppp import summary_fields
-        out.update(summary_fields(recs, dataset, engine=engine, ppp=bool(ppp)))
+        out.update(summary_fields(recs, dataset, engine=engine, ppp=bool(ppp), scf=ppp_scf))
     if aromaticity:
         from .aromaticity import summary_fields as resonance_summary
         out.update(resonance_summary(recs, dataset, engine=engine))
@@ -278,7 +280,7 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
         out.update(min_para_localization=ext["min_para_localization"], min_atom_localization=ext["min_atom_localization"])
     if ppp_dscf:
         from .ppp import dscf_fields
-        ext = dscf_fields(recs, dataset, engine=engine)
+        ext = dscf_fields(recs, dataset, engine=engine, scf=ppp_scf)
         out.update(ppp_ip_dscf=ext["ppp_ip_dscf"], ppp_ea_dscf=ext["ppp_ea_dscf"])
     return out
 
@@ -286,7 +288,7 @@ def _atoms(x, one_hot, node_mask, dataset, engine, valence_check=False, exact=Fa
 def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x, one_hot, node_mask, edge_mask, seconds,
               with_atoms=False, valence_check=False, exact=False, similarity=False, train_library=None, patterns=None,
               pattern_options=None, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False,
-              cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False):
+              cluster_threshold=None, diverse=None, reactivity=False, ppp_dscf=False, ppp_scf=None):
     """The part of design after sampling (generation_guidance.py:96-184)."""
     if patterns is not None and not with_atoms:
         raise ValueError("patterns need with_atoms=True")
@@ -329,7 +331,7 @@ def _evaluate(args, model, cond_predictor, target_function, prop_dist, scale, x,
     if with_atoms:
         out.update(_atoms(x, one_hot, node_mask, args.dataset, model.engine, valence_check, exact, similarity, train_library,
                           patterns, pattern_options, huckel, ppp, ppp_cis, aromaticity, ring_currents, cluster_threshold, diverse,
-                          reactivity, ppp_dscf))
+                          reactivity, ppp_dscf, ppp_scf))
         print(f"{out['mol_unique']=:.2%} of the built molecules")
         if valence_check:
             out["best_valid"] = order[out["valid"][order]]

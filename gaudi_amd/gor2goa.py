@@ -143,7 +143,7 @@ def _is_packed(molecules) -> bool:
 
 def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fingerprint=False, engine=None, bond_orders=False,
                    canonical=False, huckel=False, ppp=False, ppp_cis=False, aromaticity=False, ring_currents=False, reactivity=False,
-                   ppp_dscf=False):
+                   ppp_dscf=False, ppp_scf="damped"):
     """gor2goa for a batch in one launch.  ``molecules``: a list of ``(positions [n,3], ring_type [n] or one-hot [n,R])`` pairs as
     analyze_validity_for_molecules takes them, or packed arrays ``(x [B,N,3], ring_type [B,N], n_nodes [B])`` with every
     molecule's valid nodes first.  For datasets other than "cata" the second half of a molecule's nodes are its orientation nodes.
@@ -184,7 +184,9 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
     ppp_dscf: a call of gaudi_ppp_open (gaudi_amd.ppp.ionization; three rows per molecule: neutral, cation,
     anion) on the records' atoms3d adds ppp_ip_dscf and ppp_ea_dscf (the delta-SCF ionisation potential and electron affinity in eV,
     NaN where a state was not solved) and ppp_dscf_status (the largest status of the three states, gaudi_amd.ppp.STATUS_NAMES; 4 for
-    a molecule that was not built) to every record.  With ppp_dscf=False nothing changes and no launch is made."""
+    a molecule that was not built) to every record.  With ppp_dscf=False nothing changes and no launch is made.
+    ppp_scf: "damped" (the default: what it was) or "diis" -- the calls that ppp=True and ppp_dscf=True make go to gaudi_ppp_scf
+    (Pulay's DIIS) instead; the keys they add are the same.  It launches nothing by itself."""
     if _is_packed(molecules):
         X = np.ascontiguousarray(_np(molecules[0]), dtype=np.float32)
         B, N = X.shape[0], X.shape[1]
@@ -227,7 +229,7 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
             rec.update(extra)
     if ppp or ppp_cis:
         from .ppp import record_fields as ppp_fields
-        for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng, **({"ppp": bool(ppp), "ppp_cis": True} if ppp_cis else {}))):
+        for rec, extra in zip(out, ppp_fields(out, dataset, engine=eng, scf=ppp_scf, **({"ppp": bool(ppp), "ppp_cis": True} if ppp_cis else {}))):
             rec.update(extra)
     if aromaticity:
         from .aromaticity import record_fields as resonance_fields
@@ -243,7 +245,7 @@ def rings_to_atoms(molecules, dataset="cata", tol=0.1, place_hydrogens=False, fi
             rec.update(extra)
     if ppp_dscf:
         from .ppp import dscf_fields
-        extra = dscf_fields(out, dataset, engine=eng)
+        extra = dscf_fields(out, dataset, engine=eng, scf=ppp_scf)
         for i, rec in enumerate(out):
             rec.update(ppp_ip_dscf=float(extra["ppp_ip_dscf"][i]), ppp_ea_dscf=float(extra["ppp_ea_dscf"][i]),
                        ppp_dscf_status=int(extra["ppp_dscf_status"][i]))

@@ -17,7 +17,13 @@ lowest singlet and triplet excitation energies, the singlet-triplet gap, oscilla
 ``states`` / ``ionization`` / ``triplet`` take open shells (csrc/ppp_open.inc): Dewar's half-electron method --
 one restricted SCF with occupations 2 / 1 / 0 and a closed-form energy correction -- for radical ions, neutral radicals and
 triplets; delta-SCF ionisation potentials and electron affinities (orbital relaxation included) next to the Koopmans values, and
-the spin density of the unpaired electrons."""
+the spin density of the unpaired electrons.
+
+``scf="diis"`` on ``orbitals`` / ``frontier`` / ``gap`` / ``states`` / ``ionization`` / ``triplet`` runs the same model with Pulay's
+DIIS (csrc/ppp_scf.inc, gaudi_ppp_scf): the Fock matrix is extrapolated from a ring of ``diis_size`` earlier
+ones from iteration ``diis_start`` on -- the same fixed points in about half the iterations, and nearly every row the damped
+iteration leaves NOT_CONVERGED solved.  The default, ``scf="damped"``, is what it was; ``excited_states`` and the CIS hand-over take
+the damped ground state only."""
 from __future__ import annotations
 
 import copy
@@ -27,7 +33,7 @@ import os
 import numpy as np
 
 from ._lib import (HUCKEL_MAX_CLASSES, PPP_CIS_FLAGS, PPP_CIS_JACOBI_CAP, PPP_CIS_TRIPLET_UNSTABLE, PPP_CIS_TRUNCATED, PPP_CIS_WINDOW_EDGE,
-                   PPP_DEGENERATE, PPP_JACOBI_CAP, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, PPP_OPEN_TIE, PPP_SCF_CAP, GaudiError,
+                   PPP_DEGENERATE, PPP_DIIS_MAX, PPP_JACOBI_CAP, PPP_MATAGA_NISHIMOTO, PPP_OHNO, PPP_OPEN_SHELL, PPP_OPEN_TIE, PPP_SCF_CAP, GaudiError,
                    PPPTables)
 from .analyze import _engine
 from .huckel import _charges
@@ -146,8 +152,31 @@ def _pack(molecules):
     return elem, na, bonds, nb, xyz
 
 
-def _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, window=None):
-    """One gaudi_ppp call, or with a window one gaudi_ppp_cis call, for the list."""
+SCF = ("damped", "diis")
+
+
+def _scf(scf, diis_size, diis_start) -> bool:
+    """Whether the DIIS entry point serves the call."""
+    scf = "damped" if scf is None else scf
+    if scf not in SCF:
+        raise GaudiError(f"scf must be one of {list(SCF)}, got {scf!r}")
+    if scf == "diis" and not (2 <= int(diis_size) <= PPP_DIIS_MAX and int(diis_start) >= 2):
+        raise GaudiError(f"diis_size must be 2..{PPP_DIIS_MAX} and diis_start at least 2, got {diis_size} and {diis_start}")
+    return scf == "diis"
+
+
+def _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, window=None, scf="damped", diis_size=6, diis_start=3):
+    """One gaudi_ppp call, or with a window one gaudi_ppp_cis call, for the list; with scf="diis" (no window) one gaudi_ppp_scf call
+    of multiplicity 1, the rows of an odd electron count set to OPEN_SHELL as gaudi_ppp has them."""
+    if _scf(scf, diis_size, diis_start):
+        raw, na, nb = _raw_open(molecules, dataset, charge, 1, parameters, repulsion, damping, engine, scf, diis_size, diis_start)
+        odd = np.flatnonzero(raw["status"] == 2)
+        if len(odd):  # BAD_INPUT at multiplicity 1 and anything else at the lowest multiplicity: the parity was the reason
+            q = _charges(charge, len(na))
+            again, _, _ = _raw_open([molecules[i] for i in odd], dataset, 0 if q is None else q[odd], 0, parameters, repulsion, damping,
+                                    engine, scf, diis_size, diis_start)
+            raw["status"][odd[again["status"] != 2]] = PPP_OPEN_SHELL
+        return raw, na, nb
     elem, na, bonds, nb, xyz = _pack(molecules)
     args = (c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)), _repulsion(repulsion), float(damping))
     raw = _engine(engine).ppp(*args) if window is None else _engine(engine).ppp_cis(*args, int(window))
@@ -164,10 +193,12 @@ def _orbital_record(raw, i, na, nb) -> dict:
                open_shell=rec["status"] == PPP_OPEN_SHELL, degenerate=bool(flags & PPP_DEGENERATE),
                pi_charge=raw["pi_charge"][i, :na[i]].copy(), pi_bond_order=raw["pi_bond_order"][i, :nb[i]].copy(),
                site_class=raw["site_class"][i, :na[i]].copy())
+    if "diis_error" in raw:
+        rec.update(diis_error=float(raw["diis_error"][i]), n_extrapolated=int(raw["n_extrapolated"][i]))
     return rec
 
 
-def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> list:
+def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None, scf="damped", diis_size=6, diis_start=3) -> list:
     """One launch per capacity tier (32 / 64 / 128 pi centres) for the whole list.  ``molecules``: records of rings_to_atoms (their
     ``atoms3d`` is the geometry) or ``(atom_types [n], bonds [m,2], xyz [n,3])`` triples in Angstrom, with or without placed
     hydrogens; a molecule without coordinates raises.  ``charge``: one integer or one per molecule (n_electrons = sum of z - charge,
@@ -181,25 +212,31 @@ def orbitals(molecules, dataset="cata", charge=0, parameters=None, repulsion="ma
       degenerate     the frontier levels are closer than 1e-3 eV: charges and bond orders are returned but not unique
       flags          degenerate (2); why the status is 1: the iteration cap (4), a Jacobi solve at its cap (8)
       pi_charge      [n] float32 = z - P_rr, zero on hydrogens and excluded atoms;  pi_bond_order: [m] float32, zero on bonds not
-                     between pi centres;  site_class: [n] index into ``tables(...)["classes"]``, -1 = none"""
+                     between pi centres;  site_class: [n] index into ``tables(...)["classes"]``, -1 = none
+    ``scf``: "damped" (gaudi_ppp) or "diis" (gaudi_ppp_scf at multiplicity 1, DESIGN.md section 8t: the same model and fixed points,
+    not the same bits), with a history of ``diis_size`` Fock matrices (2..8) from iteration ``diis_start`` (at least 2) on.  With
+    "diis" a record also has ``diis_error`` (the last iteration's max |F P - P F| in eV) and ``n_extrapolated`` (the iterations whose
+    Fock matrix was a combination)."""
     molecules = list(molecules)
     if not molecules:
         return []
-    raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
+    raw, na, nb = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, None, scf, diis_size, diis_start)
     return [_orbital_record(raw, i, na, nb) for i in range(len(na))]
 
 
-def _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine):
-    """One gaudi_ppp_open call for the list: a row is (molecule, charge, multiplicity)."""
+def _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine, scf="damped", diis_size=6, diis_start=3):
+    """One gaudi_ppp_open call, or with scf="diis" one gaudi_ppp_scf call, for the list: a row is (molecule, charge, multiplicity)."""
+    diis = _scf(scf, diis_size, diis_start)
     elem, na, bonds, nb, xyz = _pack(molecules)
     mult = _charges(multiplicity, len(na))
-    raw = _engine(engine).ppp_open(c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)), mult,
-                                   _repulsion(repulsion), float(damping))
-    return raw, na, nb
+    args = (c_ppp_tables(dataset, parameters), elem, na, bonds, nb, xyz, _charges(charge, len(na)), mult, _repulsion(repulsion))
+    if diis:
+        return _engine(engine).ppp_scf(*args, int(diis_size), int(diis_start), float(damping)), na, nb
+    return _engine(engine).ppp_open(*args, float(damping)), na, nb
 
 
 def states(molecules, dataset="cata", charge=0, multiplicity=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25,
-           engine=None) -> list:
+           engine=None, scf="damped", diis_size=6, diis_start=3) -> list:
     """``orbitals`` for open and closed shells alike, by the half-electron method (gaudi_ppp_open): one
     launch per capacity tier for the whole list.  A row is (molecule, charge, multiplicity); ``charge`` and ``multiplicity`` are
     one integer or one per molecule.  ``multiplicity``: 1, 2 or 3; 0 is the lowest the electron count allows (1 for an even count,
@@ -214,11 +251,13 @@ def states(molecules, dataset="cata", charge=0, multiplicity=0, parameters=None,
       multiplicity   n_open + 1
       open_tie       a level within 1e-3 eV of the singly occupied set on either side, in some iteration or in the result: which
                      orbital of a degenerate pair holds the unpaired electron was arbitrary (the benzene cation), and charges, bond
-                     orders and spin densities depend on it"""
+                     orders and spin densities depend on it
+    ``scf``, ``diis_size``, ``diis_start``: as ``orbitals`` takes them (gaudi_ppp_scf); with "diis" a record also has ``diis_error``
+    and ``n_extrapolated``."""
     molecules = list(molecules)
     if not molecules:
         return []
-    raw, na, nb = _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine)
+    raw, na, nb = _raw_open(molecules, dataset, charge, multiplicity, parameters, repulsion, damping, engine, scf, diis_size, diis_start)
     out = []
     for i in range(len(na)):
         rec = _orbital_record(raw, i, na, nb)
@@ -237,70 +276,97 @@ def _ionization(raw, B) -> dict:
     tie = ((raw["flags"] & PPP_OPEN_TIE) != 0).reshape(3, B)
     ip = np.where(ok[0] & ok[1], e[1] - e[0], np.nan)
     ea = np.where(ok[0] & ok[2], e[0] - e[2], np.nan)
-    return dict(ip=ip, ea=ea, fundamental_gap=ip - ea, ip_koopmans=np.where(ok[0], -raw["homo"][:B].astype(np.float64), np.nan),
-                ea_koopmans=np.where(ok[0], -raw["lumo"][:B].astype(np.float64), np.nan), open_tie=tie.any(0),
-                status=raw["status"].reshape(3, B).copy())
+    out = dict(ip=ip, ea=ea, fundamental_gap=ip - ea, ip_koopmans=np.where(ok[0], -raw["homo"][:B].astype(np.float64), np.nan),
+               ea_koopmans=np.where(ok[0], -raw["lumo"][:B].astype(np.float64), np.nan), open_tie=tie.any(0),
+               status=raw["status"].reshape(3, B).copy())
+    if "diis_error" in raw:
+        out.update(diis_error=raw["diis_error"].reshape(3, B).copy(), n_extrapolated=raw["n_extrapolated"].reshape(3, B).copy())
+    return out
 
 
-def ionization(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
+def ionization(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None, scf="damped", diis_size=6, diis_start=3) -> dict:
     """Delta-SCF ionisation potential and electron affinity at the fixed geometry, in ONE call of 3B rows: every molecule at
     ``charge`` (its "neutral" form), with one electron less and with one more, each at its lowest multiplicity -- so a neutral
     radical works too.  Returns float64 [B] arrays in eV: ``ip`` = e_state(cation) - e_state(neutral), ``ea`` = e_state(neutral) -
     e_state(anion), ``fundamental_gap`` = ip - ea, and the Koopmans values of the neutral form ``ip_koopmans`` = -homo,
     ``ea_koopmans`` = -lumo (for a radical both are read off the half-electron levels); NaN where a state needed is not solved.
     ``open_tie`` bool [B]: one of the three states chose its singly occupied orbital within a degenerate pair (the energies are
-    still those of one valid choice).  ``status`` int32 [3, B]: the rows' statuses, neutral / cation / anion."""
+    still those of one valid choice).  ``status`` int32 [3, B]: the rows' statuses, neutral / cation / anion.  ``scf``,
+    ``diis_size``, ``diis_start``: as ``orbitals`` takes them; with "diis" also ``diis_error`` float32 and ``n_extrapolated`` int32
+    [3, B]."""
     molecules = list(molecules)
     B = len(molecules)
+    diis = _scf(scf, diis_size, diis_start)
     if not B:
-        return dict({k: np.zeros(0) for k in ("ip", "ea", "fundamental_gap", "ip_koopmans", "ea_koopmans")}, open_tie=np.zeros(0, bool),
-                    status=np.zeros((3, 0), np.int32))
+        out = dict({k: np.zeros(0) for k in ("ip", "ea", "fundamental_gap", "ip_koopmans", "ea_koopmans")}, open_tie=np.zeros(0, bool),
+                   status=np.zeros((3, 0), np.int32))
+        if diis:
+            out.update(diis_error=np.zeros((3, 0), np.float32), n_extrapolated=np.zeros((3, 0), np.int32))
+        return out
     q = _charges(charge, B)
     q = np.zeros(B, np.int32) if q is None else q
     raw, _, _ = _raw_open(molecules * 3, dataset, np.concatenate([q, q + 1, q - 1]).astype(np.int32), 0, parameters, repulsion, damping,
-                          engine)
+                          engine, scf, diis_size, diis_start)
     return _ionization(raw, B)
 
 
-def triplet(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
+def triplet(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None, scf="damped", diis_size=6, diis_start=3) -> dict:
     """The delta-SCF triplet energy of even-electron molecules in ONE call of 2B rows (singlet, triplet): ``t1`` float64 [B] =
     e_state(triplet) - e_state(singlet) in eV, next to ``optical``'s CIS ``t1``; NaN where either state is not solved (an odd
-    electron count among them).  ``open_tie`` bool [B] as ``ionization`` gives it; ``status`` int32 [2, B]."""
+    electron count among them).  ``open_tie`` bool [B] as ``ionization`` gives it; ``status`` int32 [2, B].  ``scf``, ``diis_size``,
+    ``diis_start``: as ``orbitals`` takes them; with "diis" also ``diis_error`` float32 and ``n_extrapolated`` int32 [2, B]."""
     molecules = list(molecules)
     B = len(molecules)
+    diis = _scf(scf, diis_size, diis_start)
     if not B:
-        return dict(t1=np.zeros(0), open_tie=np.zeros(0, bool), status=np.zeros((2, 0), np.int32))
+        out = dict(t1=np.zeros(0), open_tie=np.zeros(0, bool), status=np.zeros((2, 0), np.int32))
+        if diis:
+            out.update(diis_error=np.zeros((2, 0), np.float32), n_extrapolated=np.zeros((2, 0), np.int32))
+        return out
     q = _charges(charge, B)
     q = np.zeros(B, np.int32) if q is None else q
     raw, _, _ = _raw_open(molecules * 2, dataset, np.concatenate([q, q]).astype(np.int32),
-                          np.concatenate([np.ones(B, np.int32), np.full(B, 3, np.int32)]), parameters, repulsion, damping, engine)
+                          np.concatenate([np.ones(B, np.int32), np.full(B, 3, np.int32)]), parameters, repulsion, damping, engine,
+                          scf, diis_size, diis_start)
     ok = (raw["status"] == 0).reshape(2, B)
     e = raw["e_state"].reshape(2, B)
-    return dict(t1=np.where(ok[0] & ok[1], e[1] - e[0], np.nan), open_tie=((raw["flags"] & PPP_OPEN_TIE) != 0).reshape(2, B).any(0),
-                status=raw["status"].reshape(2, B).copy())
+    out = dict(t1=np.where(ok[0] & ok[1], e[1] - e[0], np.nan), open_tie=((raw["flags"] & PPP_OPEN_TIE) != 0).reshape(2, B).any(0),
+               status=raw["status"].reshape(2, B).copy())
+    if diis:
+        out.update(diis_error=raw["diis_error"].reshape(2, B).copy(), n_extrapolated=raw["n_extrapolated"].reshape(2, B).copy())
+    return out
 
 
-def dscf_fields(molecules, dataset="cata", engine=None) -> dict:
+def dscf_fields(molecules, dataset="cata", engine=None, scf="damped") -> dict:
     """What the keyword ppp_dscf=True adds: {"ppp_ip_dscf", "ppp_ea_dscf"} float64 [B] (``ionization``'s ip and ea, NaN where not
     solved) and "ppp_dscf_status" int [B], the largest of the three states' statuses (0: all solved)."""
-    ion = ionization(molecules, dataset, engine=engine)
+    ion = ionization(molecules, dataset, engine=engine, scf=scf)
     return dict(ppp_ip_dscf=ion["ip"], ppp_ea_dscf=ion["ea"], ppp_dscf_status=ion["status"].max(0) if ion["status"].size else np.zeros(0, np.int32))
 
 
-def gap(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> np.ndarray:
-    """float64 [B]: the HOMO-LUMO gap in eV, NaN where the status is not 0."""
-    return frontier(molecules, dataset, charge, parameters, repulsion, damping, engine)["gap"]
+def gap(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None, scf="damped", diis_size=6, diis_start=3) -> np.ndarray:
+    """float64 [B]: the HOMO-LUMO gap in eV, NaN where the status is not 0.  ``scf``, ``diis_size``, ``diis_start``: as ``orbitals``
+    takes them."""
+    return frontier(molecules, dataset, charge, parameters, repulsion, damping, engine, scf, diis_size, diis_start)["gap"]
 
 
-def frontier(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None) -> dict:
-    """One call -> {"gap", "ip", "ea"}: float64 [B] in eV (ip = -homo, ea = -lumo), NaN where the status is not 0."""
+def frontier(molecules, dataset="cata", charge=0, parameters=None, repulsion="mataga-nishimoto", damping=0.25, engine=None, scf="damped", diis_size=6, diis_start=3) -> dict:
+    """One call -> {"gap", "ip", "ea"}: float64 [B] in eV (ip = -homo, ea = -lumo), NaN where the status is not 0.  ``scf``,
+    ``diis_size``, ``diis_start``: as ``orbitals`` takes them; with "diis" also ``diis_error`` float32 and ``n_extrapolated`` int32 [B]."""
     molecules = list(molecules)
+    diis = _scf(scf, diis_size, diis_start)
     if not molecules:
-        return dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
-    raw, _, _ = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine)
+        out = dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
+        if diis:
+            out.update(diis_error=np.zeros(0, np.float32), n_extrapolated=np.zeros(0, np.int32))
+        return out
+    raw, _, _ = _raw(molecules, dataset, charge, parameters, repulsion, damping, engine, None, scf, diis_size, diis_start)
     ok = raw["status"] == 0
-    return dict(gap=np.where(ok, raw["gap"].astype(np.float64), np.nan), ip=np.where(ok, -raw["homo"].astype(np.float64), np.nan),
-                ea=np.where(ok, -raw["lumo"].astype(np.float64), np.nan))
+    out = dict(gap=np.where(ok, raw["gap"].astype(np.float64), np.nan), ip=np.where(ok, -raw["homo"].astype(np.float64), np.nan),
+               ea=np.where(ok, -raw["lumo"].astype(np.float64), np.nan))
+    if diis:
+        out.update(diis_error=raw["diis_error"].copy(), n_extrapolated=raw["n_extrapolated"].copy())
+    return out
 
 
 def _frontier(raw) -> dict:
@@ -388,16 +454,21 @@ def spectrum(states, grid_ev, width=0.3) -> np.ndarray:
     return out
 
 
-def summary_fields(molecules, dataset="cata", engine=None, ppp=False, ppp_cis=True) -> dict:
+def summary_fields(molecules, dataset="cata", engine=None, ppp=False, ppp_cis=True, scf="damped") -> dict:
     """What design(..., ppp_cis=True) adds: {"ppp_s1", "ppp_t1", "ppp_bright"} float64 [B]; with ``ppp`` also ``frontier``'s
-    ppp_gap / ppp_ip / ppp_ea from the same call."""
+    ppp_gap / ppp_ip / ppp_ea from the same call -- or with scf="diis" from a gaudi_ppp_scf call of their own (the CIS stage takes
+    the damped ground state only)."""
     molecules = list(molecules)
     raw = None
-    if molecules:
+    diis = _scf(scf, 6, 3) and ppp
+    if molecules and (ppp_cis or not diis):
         raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, 8 if ppp_cis else None)
     out = {}
     if ppp:
-        front = _frontier(raw) if molecules else dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
+        if diis:
+            front = {k: v for k, v in frontier(molecules, dataset, engine=engine, scf=scf).items() if k in ("gap", "ip", "ea")}
+        else:
+            front = _frontier(raw) if molecules else dict(gap=np.zeros(0), ip=np.zeros(0), ea=np.zeros(0))
         out.update({"ppp_" + k: v for k, v in front.items()})
     if ppp_cis:
         opt = _optical(raw, 0.01) if molecules else {k: np.zeros(0) for k in ("s1", "t1", "bright")}
@@ -405,20 +476,25 @@ def summary_fields(molecules, dataset="cata", engine=None, ppp=False, ppp_cis=Tr
     return out
 
 
-def record_fields(molecules, dataset="cata", engine=None, ppp=True, ppp_cis=False) -> list:
+def record_fields(molecules, dataset="cata", engine=None, ppp=True, ppp_cis=False, scf="damped") -> list:
     """What rings_to_atoms(..., ppp=True) adds to every record -- ppp_gap, ppp_homo, ppp_lumo, ppp_flags, ppp_status -- and / or
     what ppp_cis=True adds -- ppp_s1, ppp_t1, ppp_s1_f, ppp_bright (eV; NaN without a solved state) and ppp_cis_flags; asked for
-    together, one gaudi_ppp_cis call serves both."""
+    together, one gaudi_ppp_cis call serves both.  scf="diis": the first five come from a gaudi_ppp_scf call (the CIS stage takes
+    the damped ground state only, in a call of its own)."""
     molecules = list(molecules)
     if not molecules:
         return []
-    raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, 8 if ppp_cis else None)
+    diis = _scf(scf, 6, 3) and ppp
+    raw = None
+    if ppp_cis or not diis:
+        raw, _, _ = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, 8 if ppp_cis else None)
     out = [{} for _ in molecules]
     if ppp:
-        status = _scf_status(raw)
+        ground = _raw(molecules, dataset, 0, None, "mataga-nishimoto", 0.25, engine, None, scf)[0] if diis else raw
+        status = _scf_status(ground)
         for i, rec in enumerate(out):
-            rec.update(ppp_gap=float(raw["gap"][i]), ppp_homo=float(raw["homo"][i]), ppp_lumo=float(raw["lumo"][i]),
-                       ppp_flags=int(raw["flags"][i]) & ~PPP_CIS_FLAGS, ppp_status=int(status[i]))
+            rec.update(ppp_gap=float(ground["gap"][i]), ppp_homo=float(ground["homo"][i]), ppp_lumo=float(ground["lumo"][i]),
+                       ppp_flags=int(ground["flags"][i]) & ~PPP_CIS_FLAGS, ppp_status=int(status[i]))
     if ppp_cis:
         opt = _optical(raw, 0.01)
         for i, rec in enumerate(out):

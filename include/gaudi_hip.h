@@ -96,7 +96,7 @@ int gaudi_kernel_key_log(const gaudi_handle* h, char* buf, int n);
 int gaudi_host_kernel_keys(char* buf, int n);
 /* Bumped whenever an exported signature or a config struct changes (round 6: 6; 7: gaudi_edm_config.sin_embedding appended).  gaudi_amd/_lib.py refuses to bind the host-side packers of a
  * diagnostic library (GAUDI_LIB) whose version differs: round 5 inserted an argument into gaudi_host_pack_matrix_split. */
-/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get, gaudi_fp_neighbours, gaudi_fp_cluster, gaudi_fp_pick_diverse, gaudi_host_fp_neighbours, gaudi_host_fp_cluster, gaudi_host_fp_pick_diverse, gaudi_fp_select_stages_get, gaudi_ppp_open, gaudi_host_ppp_open, gaudi_ppp_open_profile_get -- change no existing
+/* (Entry points ADDED since -- the NLL / training calls, the time grids, the value targets, gaudi_rings_to_atoms, gaudi_host_eigh3, gaudi_atoms_to_rings, gaudi_bond_orders, gaudi_kernel_key_log, gaudi_host_kernel_keys, gaudi_canonical_order, gaudi_circular_fingerprint, gaudi_host_circular_fingerprint, gaudi_fp_library_set, gaudi_fp_nearest, gaudi_fp_common, gaudi_host_fp_nearest, gaudi_fp_profile_get, gaudi_substructure_search, gaudi_host_substructure_search, gaudi_host_substructure_root_steps, gaudi_substructure_profile_get, gaudi_huckel, gaudi_host_huckel, gaudi_huckel_profile_get, gaudi_ppp, gaudi_host_ppp, gaudi_ppp_profile_get, gaudi_fp_neighbours, gaudi_fp_cluster, gaudi_fp_pick_diverse, gaudi_host_fp_neighbours, gaudi_host_fp_cluster, gaudi_host_fp_pick_diverse, gaudi_fp_select_stages_get, gaudi_ppp_open, gaudi_host_ppp_open, gaudi_ppp_open_profile_get, gaudi_ppp_scf, gaudi_host_ppp_scf, gaudi_ppp_scf_profile_get -- change no existing
  * signature and keep the version.) */
 #define GAUDI_ABI_VERSION 7
 int gaudi_abi_version(void);
@@ -900,6 +900,59 @@ int gaudi_host_ppp_open(const gaudi_ppp_tables* tables, int B, int A, int M, con
 /* Number of gaudi_ppp_open launches (one per capacity tier present in a call) since gaudi_profile_reset(h, 1) and their summed
  * duration. */
 int gaudi_ppp_open_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
+
+/* ---- The PPP SCF with Pulay's DIIS (csrc/ppp_scf.inc). ----
+ * gaudi_ppp_open's model, rows, statuses and outputs; the self-consistent iteration extrapolates the Fock matrix.  Opt-in: no other
+ * entry point changes.  Per iteration k (1-based), after F = F(P) of the input density P:
+ *   While k >= diis_start the commutator e = F P - P F (fp32; G = F P with every sum over the inner index ascending, e = G - G^T)
+ *   and F enter a ring of diis_size entries (the oldest leaves a full ring); diis_error = max |e_rc| in eV.  P0 = diag(z) never
+ *   enters (diis_start >= 2): it commutes with every F of an all-carbon molecule.
+ *   B_ij = sum over r, c of e_i e_j in fp64 from the fp32 elements (by columns over r ascending, then over the columns ascending),
+ *   computed once per pair; B is scaled by its largest diagonal element and [[B, 1], [1^T, 0]] (c, lambda) = (0, 1) is solved by
+ *   Gaussian elimination with partial pivoting (the first largest element of a column) in fp64.  A pivot below 2^-40 (or B = 0)
+ *   drops the oldest entry for good and the rest is solved again; one entry left: F goes on as it is.
+ *   F <- sum over the entries, oldest to newest, of c_i F_i (fp32 elements, the coefficients rounded once to fp32).  Then gaudi_ppp's
+ *   path unchanged: Jacobi, normalise, rank, P_new, delta_p = max |P_new - P|.
+ *   From iteration diis_start on P = P_new (no damping); before it, the damped update.
+ *   Stop: delta_p <= 2^-16 and diis_error <= GAUDI_PPP_DIIS_ERROR (the second condition only rejects a stagnant history, which
+ *   reads delta_p = 0 while the commutator is of order 0.1 eV), or GAUDI_PPP_MAX_ITERATIONS.
+ * The levels, energies, charges and the fp64 state energy are those of F(P_new) of the last eigenvectors, never of an extrapolated
+ * matrix, exactly as in gaudi_ppp_open.
+ * diis_size outside 2..GAUDI_PPP_DIIS_MAX or diis_start outside 2..GAUDI_PPP_MAX_ITERATIONS: every row GAUDI_HUCKEL_BAD_INPUT and
+ * zero (behind BAD_TABLE, which a table, damping or repulsion formula that cannot be used gives every row); 0 does not select the
+ * damped iteration.  Every other refusal and its order are gaudi_ppp_open's.
+ * Outputs: the twenty-three of gaudi_ppp_open and then
+ *   diis_error_out [B] fp32: the last iteration's max |e_rc| in eV (0 where the iteration ended before diis_start);
+ *   n_extrapolated_out [B] int32: the iterations whose F was a combination of two or more entries (<= iterations - diis_start + 1).
+ * A row of multiplicity 1 solves gaudi_ppp's model but is not gaudi_ppp's bits: it stops elsewhere on the way to the same fixed point.
+ * Tiers and LDS as gaudi_ppp; the scratch row is (1 + 2 diis_size) P^2 floats, and a tier's rows are split into launches that hold at
+ * most 512 MiB of it.  Bit for bit what gaudi_host_ppp_scf returns, the doubles included.
+ * Not here: DIIS for gaudi_ppp_cis's ground state, ring currents and localization energies; level shifting, EDIIS / ADIIS,
+ * second-order SCF; stability analysis (DIIS can stop on a saddle); following a state through exact ties; UHF / ROHF. */
+#define GAUDI_PPP_DIIS_MAX 8
+#define GAUDI_PPP_DIIS_ERROR 9.765625e-4f /* 2^-10 eV (DESIGN.md section 8t says where it comes from) */
+int gaudi_ppp_scf(gaudi_handle* h, const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                  const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge, const int32_t* multiplicity,
+                  int repulsion, int32_t diis_size, int32_t diis_start, float damping, float* levels_out, uint8_t* occupation_out,
+                  float* pi_charge_out, float* pi_bond_order_out, int8_t* site_class_out, int32_t* n_pi_out,
+                  int32_t* n_electrons_out, int32_t* n_excluded_out, int32_t* iterations_out, int32_t* sweeps_out,
+                  int32_t* flags_out, int32_t* status_out, float* homo_out, float* lumo_out, float* gap_out,
+                  float* e_electronic_out, float* e_core_out, float* delta_p_out, float* spin_density_out, double* e_state_out,
+                  double* he_correction_out, int32_t* n_open_out, int32_t* somo_out, float* diis_error_out,
+                  int32_t* n_extrapolated_out);
+/* gaudi_ppp_scf without a handle: the same source text compiled for the host and run serially.  Test surface, not a fallback. */
+int gaudi_host_ppp_scf(const gaudi_ppp_tables* tables, int B, int A, int M, const int32_t* elem, const int32_t* n_atoms,
+                       const int32_t* bonds, const int32_t* n_bonds, const float* xyz, const int32_t* charge,
+                       const int32_t* multiplicity, int repulsion, int32_t diis_size, int32_t diis_start, float damping,
+                       float* levels_out, uint8_t* occupation_out, float* pi_charge_out, float* pi_bond_order_out,
+                       int8_t* site_class_out, int32_t* n_pi_out, int32_t* n_electrons_out, int32_t* n_excluded_out,
+                       int32_t* iterations_out, int32_t* sweeps_out, int32_t* flags_out, int32_t* status_out, float* homo_out,
+                       float* lumo_out, float* gap_out, float* e_electronic_out, float* e_core_out, float* delta_p_out,
+                       float* spin_density_out, double* e_state_out, double* he_correction_out, int32_t* n_open_out,
+                       int32_t* somo_out, float* diis_error_out, int32_t* n_extrapolated_out);
+/* Number of gaudi_ppp_scf launches (one per capacity tier present in a call, more where a tier's scratch is split) since
+ * gaudi_profile_reset(h, 1) and their summed duration. */
+int gaudi_ppp_scf_profile_get(gaudi_handle* h, int32_t* n_launches, double* total_ms);
 
 /* ---- PPP-CIS excited states: S1, T1 and oscillator strengths (csrc/ppp_cis.inc). ----
  * gaudi_ppp, then configuration interaction over single excitations on its ground state.  After a solve with status OK: the levels
