@@ -51,7 +51,8 @@ enum { ST_NODE = 0, ST_EDGE = 1, ST_EDGE_EPI = 2, ST_BARRIER = 3, ST_MISC = 4, S
        ST_BWD_COL = 7, ST_BWD_BARRIER = 8, ST_STASH = 9, ST_B_V = 10, ST_B_EV = 11, ST_B_CP = 12, ST_B_DCP = 13,
        ST_B_DE = 14, ST_B_DV = 15, ST_B_DT1 = 16, ST_B_DU = 17, ST_STAGE = 18, ST_GEO = 19,
        ST_EDM_IO = 20, ST_UPDATE = 21, ST_PRED_IO = 22, ST_GUIDE = 23, ST_X0 = 24, ST_X1 = 25, ST_X2 = 26, ST_X3 = 27,
-       ST_N = 28 };
+       ST_B_DX = 28, ST_F_COORD = 29,  // the reverse pass's dx sum, the predictor's forward coord_update (w8_pred.h)
+       ST_N = 30 };                    // (the host's buffer has 32 entries; 30 and 31 carry the launch's clock counters)
 struct Stamps {
   unsigned long long acc[ST_N];
   unsigned long long last;

@@ -1027,7 +1027,8 @@ static int launch(gaudi_handle* h, const KParams& P, int hpe, int hpp, long long
       static const char* nm[] = {"node_gemm", "edge_gemm", "edge_epilogue", "barrier", "misc", "bwd_node", "bwd_stash_reload",
                                  "bwd_colsum_tail", "pub_wait", "stash", "pub_write", "colsum_loop", "colsum_barrier", "b_dcp",
                                  "b_gemm_de", "b_dv", "b_gemm_dt1", "b_du", "stage_vectors", "geo", "edm_embed_head", "noise_update",
-                                 "bwd_reload_loads", "bwd_vec_commit", "pred_readout", "bwd_prologue", "x2", "x3"};
+                                 "bwd_reload_loads", "bwd_vec_commit", "pred_readout", "bwd_prologue", "x2", "x3", "b_dx_sum", "f_coord_update"};
+      static_assert(sizeof(nm) / sizeof(nm[0]) == ST_N, "one name per stamp id");
       unsigned long long tot = 0;
       for (int i = 0; i < ST_N; ++i) tot += h->stamp_acc[i];
       fprintf(stderr, "[stamps] cumulative shares (block 0, wave 0):");

@@ -14,6 +14,20 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "lds_fold.h"
+
+// The per-node sums of the resident single-round N1 kernels that fetch their rows a batch at a time (lds_fold.h; round 15, DESIGN
+// section 8) -- bit 0: the reverse pass's du -> dP / dQ gather (A); bit 1: its dx sum (B); bit 2: the coordinate update of the
+// predictor's forward pass and of the denoiser (C); 0: the plain loops everywhere (A/B builds).  Same additions in the same order.
+#ifndef GAUDI_LDS_BATCH
+#define GAUDI_LDS_BATCH 7
+#endif
+#ifndef GAUDI_LDS_BATCH_ROWS
+#define GAUDI_LDS_BATCH_ROWS 5  // rows per batch: cata's runs are 10 long, an N1 launch holds runs of up to 15
+#endif
+#ifndef GAUDI_LDS_BATCH_PLAIN
+#define GAUDI_LDS_BATCH_PLAIN 0  // 1: the plain resident split kernel batches too (the stamped diagnostic build runs that one)
+#endif
 
 namespace gaudi {
 namespace w8 {

@@ -86,16 +86,26 @@ __device__ __forceinline__ void compute_geo(const SM& sm, const MolGraph& mg, fl
 }
 
 // x <- (x + sum_j trans_ij / normf) * mask     (egnn_new.py:132-155), fixed ascending-j order
-template <class SM>
+// BATCH: the run's rows are fetched GAUDI_LDS_BATCH_ROWS at a time and folded in the same order (lds_fold.h)
+template <bool BATCH = false, class SM>
 __device__ __forceinline__ void coord_update(const SM& sm, const MolGraph& mg, float normf, int tid) {
   for (int idx = tid; idx < mg.N * 3; idx += kThreads) {  // strided: small hidden sizes fit N > 170 nodes in LDS
     const int n = idx / 3, d = idx % 3;
     const uint32_t sg = mg.seg[n];
     const int st = sg >> 16, len = sg & 0xffff;
     float s = 0.f;
-    for (int k = 0; k < len; ++k) s += sm.trans[(st + k) * 4 + d];
+    if constexpr (BATCH) {
+      s = fold_run<GAUDI_LDS_BATCH_ROWS, float>(s, sm.trans + d, 4, st, len);
+    } else {
+      for (int k = 0; k < len; ++k) s += sm.trans[(st + k) * 4 + d];
+    }
     sm.x[4 * n + d] = (sm.x[4 * n + d] + s / normf) * mg.mask[n];
   }
+}
+// The kernels whose per-node sums are batched (w8_common.h: GAUDI_LDS_BATCH): the resident single-round N1 form -- the condition of
+// the reverse pass's stash rides (w8_pred.h: kRide) without its K-tail clause
+__host__ __device__ constexpr bool lds_batch_form(int SP, bool MR, int GN, int FL) {
+  return SP == 1 && !MR && GN == 0 && (node_one_tile(FL) || (GAUDI_LDS_BATCH_PLAIN && FL != kNodeFresh));
 }
 
 // The lane's view of its 16-edge tile in one round
@@ -365,7 +375,7 @@ __device__ __forceinline__ void edm_forward(const EdmDev& W, const MolGraph& mg,
       if (l + 1 < W.L) vec_prefetch<NV, kThreads>(vpf, wb, lay.gcl(l + 1, 0) + 6 * PK, 7 * HP + 16, tid);
       __syncthreads();
       STAMP(ST_BARRIER);
-      coord_update(sm, mg, W.normf, tid);
+      coord_update<lds_batch_form(SP, false, GN, FL) && (GAUDI_LDS_BATCH & 4)>(sm, mg, W.normf, tid);
       __syncthreads();
       STAMP(ST_MISC);
     }

@@ -339,8 +339,9 @@ __device__ __forceinline__ void pred_forward(const PredDev& W, const MolGraph& m
     }
     node_gemm_x<HP, EPI_RESIDUAL_MASK, false, GN, NH, kAheadOne, kAheadOne, FL>(wb, wbe, Lw.Wn2, p, xs0, true, -1, nullptr, nullptr, Lw.bn2, h, h, mg.mask, mg.NC, wave,
                                                      lane, tw, hctx(), pf, l + 1 < W.L ? lay.layer(l + 1) : -1);
-    if (!last) coord_update(sm, mg, 1.0f, tid);
     STAMP(ST_NODE);
+    if (!last) coord_update<lds_batch_form(SP, MR, GN, FL) && (GAUDI_LDS_BATCH & 4)>(sm, mg, 1.0f, tid);
+    STAMP(ST_F_COORD);
     __syncthreads();
     STAMP(ST_BARRIER);
   }
@@ -399,6 +400,10 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
   constexpr bool kRide = SP == 1 && !MR && GN == 0 && SplitGeo<HP, SP == 1 ? 1 : 2>::kTailOK &&
                          (node_one_tile(FL) || (GAUDI_STASH_RIDE_PLAIN && FL != kNodeFresh));
   constexpr bool kRideA = kRide && (GAUDI_STASH_RIDE & 1), kRideB = kRide && (GAUDI_STASH_RIDE & 2);
+  // ... and in the same kernels the per-node sums behind the edge pass fetch their rows a batch at a time (round 15; lds_fold.h)
+  constexpr bool kBatchForm = lds_batch_form(SP, MR, GN, FL);
+  constexpr bool kBatchA = kBatchForm && (GAUDI_LDS_BATCH & 1), kBatchB = kBatchForm && (GAUDI_LDS_BATCH & 2);
+  constexpr int kBatch = GAUDI_LDS_BATCH_ROWS;
   constexpr int kHookTiles = GAUDI_HOOK_TILES < T ? GAUDI_HOOK_TILES : T;
   constexpr int kRideTiles = GAUDI_RIDE_TILES < T ? GAUDI_RIDE_TILES : T;
   constexpr int kRideTrip = SplitGeo<HP, SP == 1 ? 1 : 2>::kTripsTail - 2;
@@ -726,9 +731,25 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
           const uint32_t sg = mg.seg[n];
           const int rs = sg >> 16, rl = sg & 0xffff;
           f4 sp = splat(0.f), sq = splat(0.f);
-          for (int k = 0; k < rl; ++k) sp += *(const f4*)(pub + (rs + k) * PLD + f);
-          const int s0 = mg.soff[n], s1 = mg.soff[n + 1];
-          for (int k = s0; k < s1; ++k) sq += *(const f4*)(pub + (int)mg.sidx[k] * PLD + f);
+          if constexpr (kBatchA) {
+            // a batch of both chains at a time: the indices of the Q chain's rows, the P chain's rows, the Q chain's rows, then the
+            // folds -- two LDS round trips per batch where every slot of either chain took one (two) of its own (lds_fold.h)
+            const int s0 = mg.soff[n], ql = mg.soff[n + 1] - s0, nk = rl > ql ? rl : ql;
+            for (int k0 = 0; k0 < nk; k0 += kBatch) {
+              FoldBatch<kBatch, f4> bp, bq;
+              int rp[kBatch], rq[kBatch];
+              bq.rows_of_list(rq, mg.sidx, s0, k0, ql);
+              bp.rows_of_run(rp, rs, k0, rl);
+              bp.load(pub + f, PLD, rp);
+              bq.load(pub + f, PLD, rq);
+              sp = bp.add(sp, k0, rl);
+              sq = bq.add(sq, k0, ql);
+            }
+          } else {
+            for (int k = 0; k < rl; ++k) sp += *(const f4*)(pub + (rs + k) * PLD + f);
+            const int s0 = mg.soff[n], s1 = mg.soff[n + 1];
+            for (int k = s0; k < s1; ++k) sq += *(const f4*)(pub + (int)mg.sidx[k] * PLD + f);
+          }
           *(f4*)(B2 + n * LD + 16 * t0 + f) = sp;  // dP_n
           *(f4*)(B4 + n * LD + 16 * t0 + f) = sq;  // dQ_n
         }
@@ -747,11 +768,28 @@ __device__ __forceinline__ void pred_backward(const PredDev& W, const MolGraph& 
       const uint32_t sg = mg.seg[n];
       const int rs = sg >> 16, rl = sg & 0xffff;
       float acc = sm.dx[4 * n + d];
-      for (int k = 0; k < rl; ++k) acc += sm.trans[4 * (rs + k) + d];
-      const int s0 = mg.soff[n], s1 = mg.soff[n + 1];
-      for (int k = s0; k < s1; ++k) acc -= sm.trans[4 * (int)mg.sidx[k] + d];
+      if constexpr (kBatchB) {
+        // one chain, the run then the list: the list's first batch is requested ahead of the run's folds (lds_fold.h)
+        const int s0 = mg.soff[n], ql = mg.soff[n + 1] - s0;
+        FoldBatch<kBatch, float> bq;
+        int rq[kBatch];
+        bq.rows_of_list(rq, mg.sidx, s0, 0, ql);
+        bq.load(sm.trans + d, 4, rq);
+        acc = fold_run<kBatch, float>(acc, sm.trans + d, 4, rs, rl);
+        acc = bq.sub(acc, 0, ql);
+        for (int k0 = kBatch; k0 < ql; k0 += kBatch) {
+          bq.rows_of_list(rq, mg.sidx, s0, k0, ql);
+          bq.load(sm.trans + d, 4, rq);
+          acc = bq.sub(acc, k0, ql);
+        }
+      } else {
+        for (int k = 0; k < rl; ++k) acc += sm.trans[4 * (rs + k) + d];
+        const int s0 = mg.soff[n], s1 = mg.soff[n + 1];
+        for (int k = s0; k < s1; ++k) acc -= sm.trans[4 * (int)mg.sidx[k] + d];
+      }
       sm.dx[4 * n + d] = acc;
     }
+    STAMP(ST_B_DX);
     // (f) dh += A^T dP + Bm^T dQ
     vec_prefetch<NV, kThreads>(vpf, wb, PredLayerW::vec_off(lay.layer(l > 0 ? l - 1 : 0), HP), PredLayerW::vec_count(HP), tid);
     if constexpr (STG) {  // (the publish loop ended on a barrier: dP / dQ are complete, the ring is free)
